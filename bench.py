@@ -63,7 +63,14 @@ def parse():
     ap.add_argument("--no-kernel-profile", action="store_true",
                     help="skip the per-layer / per-phase event profile behind `roofline` (for rocprofv3 traces: the last steps "
                          "of the trace are then timed steps, not the single-stream profiling passes)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0): "
+                         "infer_probabilities; train_stats (sum of loss*n, number correct) and train_state (the parameters "
+                         "and BatchNorm statistics after the optimizer step).  Arrays above 4 Mi elements are a fixed, "
+                         "seeded sample, so the files stay under 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.precision is None:
         # the fastest mode that holds the parity tolerance: ResNets - calibrated single pass (tests/test_gpu_calibrated.py);
         # EfficientNets - `mixed`, which splits none of their convs (the weight rounding does not show beside the fp16
@@ -241,6 +248,32 @@ def replicas_equal(net, dist):
     return len(set(digests)) == 1
 
 
+DUMP_MAX_ELEMS = 1 << 22   # per array (16 MB of float32): the three arrays stay under 64 MB together
+
+
+def dump_sample(a):
+    """`a` itself if it is small enough, else a fixed seeded sample: whole rows of a 2-D array, elements of a 1-D one
+    (the same indices on every run with the same shape)."""
+    if a.size <= DUMP_MAX_ELEMS:
+        return a
+    rng = np.random.default_rng(0)
+    if a.ndim == 2:
+        rows = max(1, DUMP_MAX_ELEMS // a.shape[1])
+        return a[np.sort(rng.choice(a.shape[0], size=rows, replace=False))]
+    return a[np.sort(rng.choice(a.size, size=DUMP_MAX_ELEMS, replace=False))]
+
+
+def last_step_outputs(mode, net, last):
+    """What a caller of the timed path holds after its last step, as host float arrays.  infer: the probabilities the
+    step returned.  train: the step's (sum of loss*n, number correct) (`read_stats`, reset before that step) and the
+    model state its optimizer step left, every floating-point entry of `state_dict()` flattened in its order."""
+    if mode == "infer":
+        return {"infer_probabilities": dump_sample(last.float().cpu().numpy())}
+    state = np.concatenate([v.numpy().ravel() for v in net.state_dict().values() if v.is_floating_point()])
+    return {"train_stats": np.array(net.read_stats(), dtype=np.float64),
+            "train_state": dump_sample(state.astype(np.float32, copy=False))}
+
+
 def run_mode(mode, args, net, x, y, dist, dev, rank, world):
     """Times K steps of one mode; returns the result dict on rank 0."""
     parity_gpu = None
@@ -293,13 +326,21 @@ def run_mode(mode, args, net, x, y, dist, dev, rank, world):
     # per-step times from events on the launch stream (the library enqueues on torch's current stream); the
     # headline stays the wall time of the K steps between the two fences
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    dump = bool(args.dump_outputs) and rank == 0
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
-        step()
+        if dump and mode == "train" and i == args.steps - 1:
+            net.reset_stats()      # the loss statistics of the last step alone (an 8-byte fill on the launch stream)
+        last = step()
         marks[i + 1].record()
     fence()
     dt = time.perf_counter() - t0
+    if dump:
+        out_dir = Path(args.dump_outputs)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        for name, a in last_step_outputs(mode, net, last).items():
+            np.save(out_dir / f"{name}.npy", a)
     if mode == "infer" and world == 1 and not args.no_cpu_baseline:
         parity_gpu = step()[:PARITY_N].float().cpu()     # one more forward of the timed configuration (two streams)
     uncal_ms = None

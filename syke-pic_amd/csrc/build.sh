@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds libsykepic_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU).
-# The host-side sanitizer build lives in build_asan.sh (CPU only; that script does not travel to the GPU box).
+# The host-side sanitizer build lives in build_asan.sh (CPU only: build() runs it on hosts without an AMD GPU).
 set -e
 cd "$(dirname "$0")"
 OUT=../sykepic_hip/libsykepic_hip.so

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Host-side sanitizer build (CPU ONLY): every translation unit again with AddressSanitizer + UBSan on the HOST pass
 # (GPU sanitizers are not available on this pool), linked with asan_driver.hip into build/asan/asan_driver, which
-# tests/test_abi.py runs on the CPU.  Listed in .gpurunignore: neither this script nor its output goes to a GPU box.
+# tests/test_abi.py runs on the CPU.  __graft_entry__.build() runs this script only on hosts without an AMD GPU.
 set -e
 cd "$(dirname "$0")"
 mkdir -p build/asan

@@ -15,6 +15,7 @@ Only data (inputs are generator-seeded, outputs are arrays) is written.
 """
 
 import contextlib
+import copy
 import io
 import json
 import shutil
@@ -180,6 +181,9 @@ def golden_net_pass_diverse():
         out[f"{tag}_row_scale"] = row_scale.numpy()
         out[f"{tag}_rois_out"] = np.array([r for r, _ in res], dtype=np.int64)
         out[f"{tag}_probs"] = np.array([p for _, p in res], dtype=np.float32)
+        # the same pass in float64: fp32 rounding (about 2e-6 here) differs between hosts, this one does not
+        res64 = net_pass(copy.deepcopy(net).double(), [(x[:3].double(), paths[:3]), (x[3:].double(), paths[3:])], "cpu")
+        out[f"{tag}_probs64"] = np.array([p for _, p in res64], dtype=np.float64)
         distinct = len(set(out[f"{tag}_probs"].argmax(1).tolist()))
         print(tag, "top1", out[f"{tag}_probs"].argmax(1), "distinct", distinct)
         assert distinct >= 6, "fixture must have at least 6 distinct arg-max classes"

@@ -52,8 +52,8 @@ def test_host_code_under_address_and_ub_sanitizers():
     import subprocess
     csrc = ROOT / "syke-pic_amd" / "csrc"
     recipe = csrc / "build_asan.sh"
-    if not recipe.is_file():
-        pytest.skip("build_asan.sh is not shipped to GPU boxes (.gpurunignore): the sanitizer pass is a CPU-container test")
+    if os.path.exists("/dev/kfd"):
+        pytest.skip("an AMD GPU is present: the sanitizer pass runs on hosts without one (every HIP call fails there)")
     exe = csrc / "build" / "asan" / "asan_driver"
     srcs = list(csrc.glob("*.hip")) + list(csrc.glob("*.h"))
     if not exe.is_file() or any(f.stat().st_mtime > exe.stat().st_mtime for f in srcs):

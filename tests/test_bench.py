@@ -1,0 +1,46 @@
+"""bench.py --dump-outputs: what the last timed step computed, written as .npy files (a fixed, seeded sample of an array
+that is too large), so that two builds of the project can be compared output for output; --steps sets the number of
+timed steps."""
+
+import json
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import bench
+
+ROOT = Path(__file__).resolve().parent.parent
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    small = np.arange(12, dtype=np.float32).reshape(3, 4)
+    assert bench.dump_sample(small) is small
+    flat = np.arange(bench.DUMP_MAX_ELEMS + 1000, dtype=np.float32)
+    a = bench.dump_sample(flat)
+    assert a.size == bench.DUMP_MAX_ELEMS and np.array_equal(a, bench.dump_sample(flat)) and (np.diff(a) > 0).all()
+    rows = np.arange((bench.DUMP_MAX_ELEMS // 50 + 10) * 50, dtype=np.float32).reshape(-1, 50)
+    r = bench.dump_sample(rows)
+    assert r.shape == (bench.DUMP_MAX_ELEMS // 50, 50) and np.array_equal(r, bench.dump_sample(rows))
+    assert np.array_equal(r, rows[(r[:, 0] // 50).astype(np.int64)])        # whole rows, in their order
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_last_timed_step(tmp_path):
+    out_dir = tmp_path / "outputs"
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+           "--size", "64", "--network", "resnet18", "--no-cpu-baseline", "--no-kernel-profile", "--dump-outputs", str(out_dir)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    res = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
+    assert res["steps"] == 3 and res["ms_per_step"] > 0 and res["train"]["ms_per_step"] > 0
+    d = {p.stem: np.load(p) for p in out_dir.glob("*.npy")}
+    assert set(d) == {"infer_probabilities", "train_stats", "train_state"}
+    p = d["infer_probabilities"]
+    assert p.dtype == np.float32 and p.shape == (8, 50) and np.allclose(p.sum(1), 1.0, atol=1e-4)
+    loss, correct = d["train_stats"]
+    assert d["train_stats"].dtype == np.float64 and loss > 0 and 0 <= correct <= 8
+    s = d["train_state"]
+    assert s.dtype == np.float32 and s.size == bench.DUMP_MAX_ELEMS and np.isfinite(s).all()   # ResNet-18: 11.4 M values

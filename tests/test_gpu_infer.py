@@ -194,7 +194,7 @@ def test_split_weight_modes_and_per_op_mask():
     assert torch.equal(net.forward(x), torch.from_numpy(by_mode[3]).cuda())
 
 
-def test_every_main_loop_flavour_gives_the_same_network_output():
+def test_every_main_loop_flavour_gives_the_same_network_output(tmp_path):
     """Each main-loop flavour of the implicit-GEMM kernel (register-staged, LDS-DMA 3-4 stages, 2 stages,
     hybrid, 32-deep K steps, single stage) forced for every conv of ResNet-50: all accumulate each output
     element in the same K order, so the logits are bit-identical whichever the autotuner picks."""
@@ -217,7 +217,7 @@ def test_every_main_loop_flavour_gives_the_same_network_output():
     for cfg, dma in ((3, 3), (3, 0), (0, 1), (0, 4), (3, 5), (0, 5), (3, 6), (4, 6), (2, 3)):
         env = dict(os.environ)
         env["SPK_CONV_CFG"], env["SPK_CONV_DMA"] = str(cfg), str(dma)
-        path = f"/tmp/flavour_{cfg}_{dma}.npy"
+        path = str(tmp_path / f"flavour_{cfg}_{dma}.npy")
         subprocess.run([sys.executable, "-c", code, path], check=True, env=env)
         outs[(cfg, dma)] = np.load(path)
     ref = outs[(3, 3)]

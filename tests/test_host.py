@@ -233,7 +233,7 @@ def test_roi_number_equals_the_reference_expression():
             prob.roi_number(p)
 
 
-def test_tune_cache_environment_rules(monkeypatch):
+def test_tune_cache_environment_rules(monkeypatch, tmp_path):
     """lib._default_tune_cache: an explicit file is kept, `off` / `0` / empty mean "this process only" (the variable is
     removed before the library reads it), and a host without an AMD GPU gets no cache directory."""
     import os
@@ -246,12 +246,13 @@ def test_tune_cache_environment_rules(monkeypatch):
         lib._default_tune_cache()
         assert "SPK_TUNE_CACHE" not in os.environ
     monkeypatch.delenv("SPK_TUNE_CACHE", raising=False)
-    monkeypatch.setenv("XDG_CACHE_HOME", "/tmp/spk_test_cache_home")
+    home = tmp_path / "cache_home"
+    monkeypatch.setenv("XDG_CACHE_HOME", str(home))
     lib._default_tune_cache()
     if os.path.exists("/dev/kfd"):
-        assert os.environ["SPK_TUNE_CACHE"].startswith("/tmp/spk_test_cache_home/sykepic_hip/tune-")
+        assert os.environ["SPK_TUNE_CACHE"].startswith(f"{home}/sykepic_hip/tune-")
     else:
-        assert "SPK_TUNE_CACHE" not in os.environ and not os.path.exists("/tmp/spk_test_cache_home")
+        assert "SPK_TUNE_CACHE" not in os.environ and not home.exists()
     monkeypatch.delenv("SPK_TUNE_CACHE", raising=False)
 
 
