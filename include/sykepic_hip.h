@@ -296,6 +296,14 @@ int spk_op_conv_dgrad_bn_backward(const void* dy, const float* w_ohwi, void* dx,
                                   const unsigned char* mask, const float* mean, const float* invstd, const float* gamma,
                                   float* dgamma, float* dbeta, void* dy_prod, int n, int h, int w, int cin, int cout, int k,
                                   int pad, int relu, const void* res_src, const unsigned char* res_bits, void* stream);
+/* Pins the implicit-GEMM candidate (csrc/conv_igemm.hip) of every later convolution of the process: tile config
+ * cfg 0..6 with main-loop flavour dma 0..6 (0 register-staged, 1 LDS-DMA 3-4 stage, 3 LDS-DMA 2 stage, 4 hybrid,
+ * 5 BK-32, 6 one stage), and the weight-gradient pipeline depth wgrad_nbuf 1 / 2 (csrc/conv_wgrad.hip).  -1 in a field:
+ * not pinned, the tuner decides as without the call (cfg and dma are pinned together or not at all).  A pinned launch
+ * reads and appends nothing of the tune cache and runs exactly that candidate; the single-operator hooks above and
+ * spk_op_conv1x1 / spk_op_conv3x3 (cfg < 0) fail with SPK_ERR_UNSUPPORTED ("does not fit") when the flavour is not
+ * instantiated for the problem's tile (configs 5 -> 4 -> 3 are still narrowed when Cout % 256 / % 128).  For tests. */
+int spk_op_conv_pin(int cfg, int dma, int wgrad_nbuf);
 /* Conv2d weight gradient: dw [Cout][kh][kw][Cin] float32 from x [n,h,w,cin] and dy [n,ho,wo,cout]. */
 int spk_op_conv_wgrad(const void* x_dev, const void* dy_dev, float* dw_dev, int n, int h, int w, int cin, int cout,
                       int k, int stride, int pad, void* hip_stream);

@@ -939,6 +939,20 @@ const std::pair<int, int>* find_tuned_locked(const TuneKey& key, int n) {
 }
 }  // namespace
 
+// Test-hook pin (spk_op_conv_pin): one (tile config, main-loop flavour) for every implicit-GEMM launch of the process
+// and one pipeline depth for the weight gradient; -1 = not pinned.  Process-wide, like the tuner's tables.
+namespace {
+std::atomic<int> g_pin_cfg{-1}, g_pin_dma{-1}, g_pin_wgrad_nbuf{-1};
+}  // namespace
+
+void spk_conv_set_pin(int cfg, int dma, int wgrad_nbuf) {
+  g_pin_cfg.store(cfg);
+  g_pin_dma.store(dma);
+  g_pin_wgrad_nbuf.store(wgrad_nbuf);
+}
+
+int spk_conv_pinned_wgrad_nbuf() { return g_pin_wgrad_nbuf.load(); }
+
 int spk_conv_launch(const ConvArgs& a_in, int mode, hipStream_t s, int* m_tiles_out) {
   if (a_in.K % BK || a_in.Cout % 64) return -2;
   if (mode == CONV_MODE_DGRAD && a_in.stride != 1 && a_in.cls_ph < 0) return -2;  // stride 2 goes by parity class
@@ -951,6 +965,12 @@ int spk_conv_launch(const ConvArgs& a_in, int mode, hipStream_t s, int* m_tiles_
     }
   }
   ConvArgs a = a_in;
+  if (const int pin_cfg = g_pin_cfg.load(); pin_cfg >= 0) {
+    // pinned: exactly this candidate - no tuner, no tune cache, no fall-back to another flavour (-3: not instantiated)
+    a.cfg = pin_cfg;
+    a.dma = g_pin_dma.load();
+    return launch_with(a, mode, pin_cfg, s, m_tiles_out);
+  }
   if (env_cfg() >= 0 || !autotune_on() || a.cfg >= 0) {
     const int cfg = a.cfg >= 0 ? a.cfg : (env_cfg() >= 0 ? env_cfg() : pick_cfg(a.M, a.Cout));
     if (a.dma < 0 && getenv("SPK_CONV_DMA")) a.dma = atoi(getenv("SPK_CONV_DMA"));  // flavour 0..4

@@ -274,7 +274,8 @@ void wg_cache_load_locked() {
 template <int BCO, int BCI, bool STEM>
 int launch(const WgradArgs& a, int splits, hipStream_t s) {
   static const int forced = getenv("SPK_WGRAD_NBUF") ? atoi(getenv("SPK_WGRAD_NBUF")) : 0;
-  int nbuf = forced;
+  const int pinned = spk_conv_pinned_wgrad_nbuf();   // test hook: no tuner, no tune cache
+  int nbuf = pinned == 1 || pinned == 2 ? pinned : forced;
   if (nbuf != 1 && nbuf != 2) {
     const WgKey key(a.M, a.Cin, a.Cout, a.kh, a.stride, (int)STEM, splits, BCO * 1000 + BCI);
     bool have = false;

@@ -36,6 +36,25 @@ bool stem_shape(int cin, int cout, int k, int stride, int pad) {
     if ((expr) != 0) return ofail(SPK_ERR_HIP, std::string(what) + " failed");    \
   } while (0)
 
+// an implicit-GEMM launch: -3 is a candidate pinned by spk_op_conv_pin that is not instantiated for the problem
+#define O_CONV(expr, what)                                                                                      \
+  do {                                                                                                          \
+    const int rc_ = (expr);                                                                                     \
+    if (rc_ == -3) return ofail(SPK_ERR_UNSUPPORTED, std::string(what) + ": the pinned candidate does not fit this problem"); \
+    if (rc_ != 0) return ofail(SPK_ERR_HIP, std::string(what) + " failed");                                    \
+  } while (0)
+
+// Pins the implicit-GEMM candidate (tile config 0..6, main-loop flavour 0..6) and the weight-gradient pipeline depth
+// (1 or 2) for every later launch of the process; -1 leaves that choice to the tuner.  The tile and the flavour go
+// together: both pinned or neither.
+extern "C" int spk_op_conv_pin(int cfg, int dma, int wgrad_nbuf) {
+  if (cfg < -1 || cfg > 6 || dma < -1 || dma > 6 || (cfg < 0) != (dma < 0) ||
+      (wgrad_nbuf != -1 && wgrad_nbuf != 1 && wgrad_nbuf != 2))
+    return ofail(SPK_ERR_ARG, "op_conv_pin: cfg 0..6 and flavour 0..6 together (or both -1), wgrad_nbuf 1, 2 or -1");
+  spk_conv_set_pin(cfg, dma, wgrad_nbuf);
+  return SPK_OK;
+}
+
 extern "C" int spk_op_conv_bn_train_forward(const void* x, const float* w_ohwi, const float* gamma, const float* beta,
                                             float* running_mean, float* running_var, const void* res, void* out,
                                             void* raw, unsigned char* mask, float* mean_invstd, int n, int h, int w,
@@ -69,7 +88,7 @@ extern "C" int spk_op_conv_bn_train_forward(const void* x, const float* w_ohwi, 
   a.w_bytes = (unsigned)((size_t)cout * kpad * 2);
   a.stats = part;
   int m_tiles = 0;
-  O_TRY(spk_conv_launch(a, stem ? CONV_MODE_STEM : CONV_MODE_GENERIC, s, &m_tiles), "conv launch");
+  O_CONV(spk_conv_launch(a, stem ? CONV_MODE_STEM : CONV_MODE_GENERIC, s, &m_tiles), "conv launch");
   O_TRY(spk_launch_bn_finalize(part, m_tiles, cout, (double)M, gamma, beta, running_mean, running_var, mean_invstd,
                                mean_invstd + cout, st, st + cout, 1e-5f, 0.1f, tmp, s), "bn_finalize");
   O_TRY(spk_launch_bn_apply((const bf16_t*)raw, st, st + cout, (const bf16_t*)res, (bf16_t*)out, mask,
@@ -264,7 +283,8 @@ extern "C" int spk_op_conv1x1(const void* x, const float* w, const float* bn_sca
     a.kh = a.kw = 1; a.stride = stride; a.M = M; a.K = cin; a.relu = relu; a.dt = DT_F16; a.splitw = split != 0;
     a.x_bytes = (unsigned)((size_t)n * h * wd * cin * 2);
     a.w_bytes = (unsigned)((size_t)cout * cin * 2 * (split ? 2 : 1));
-    r = spk_conv_launch(a, CONV_MODE_GENERIC, s, nullptr);
+    O_CONV(spk_conv_launch(a, CONV_MODE_GENERIC, s, nullptr), "conv1x1 launch");
+    r = 0;
   } else {
     O_TRY(spk_launch_pack_pw(w, nullptr, wp, cout, cin, DT_F16, split ? 2 : 1, s), "pack_pw");
     PwConvArgs q;
@@ -385,7 +405,8 @@ extern "C" int spk_op_conv3x3(const void* x, const float* w_ohwi, const float* b
     a.kh = a.kw = 3; a.stride = 1; a.pad = 1; a.M = M; a.K = 9 * cin; a.relu = relu; a.dt = DT_F16; a.splitw = split != 0;
     a.x_bytes = (unsigned)((size_t)M * cin * 2);
     a.w_bytes = (unsigned)((size_t)cout * 9 * cin * 2 * (split ? 2 : 1));
-    r = spk_conv_launch(a, CONV_MODE_GENERIC, s, nullptr);
+    O_CONV(spk_conv_launch(a, CONV_MODE_GENERIC, s, nullptr), "conv3x3 launch");
+    r = 0;
   } else {
     O_TRY(spk_launch_pack_c3(w_ohwi, wp, cout, cin, split ? 2 : 1, s), "pack_c3");
     C3Args q;

@@ -145,8 +145,12 @@ static inline void spk_set_gate(ConvArgs& a, const float* gate, int gate_stride)
 }
 
 // returns 0 on success; fills *m_tiles with the number of row tiles used
-// (needed to size/finalize the stats partials)
+// (needed to size/finalize the stats partials).  -3: the pinned candidate (spk_conv_set_pin) is not instantiated
 int spk_conv_launch(const ConvArgs& a, int mode, hipStream_t s, int* m_tiles_out);
+// test hook (spk_op_conv_pin): every later spk_conv_launch runs tile config `cfg` with main-loop flavour `dma`, and
+// every weight-gradient launch `wgrad_nbuf` LDS stages; -1 = not pinned (the tuner decides)
+void spk_conv_set_pin(int cfg, int dma, int wgrad_nbuf);
+int spk_conv_pinned_wgrad_nbuf();
 int spk_conv_m_tiles(int M, int Cout, int mode);
 int spk_conv_stem_launch(const ConvArgs& a, hipStream_t s, int* m_tiles_out);  // conv_stem.hip
 const char* spk_conv_last_config();

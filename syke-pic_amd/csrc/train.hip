@@ -404,6 +404,13 @@ static void fill_conv(ConvArgs& a, const bf16_t* x, const bf16_t* w, bf16_t* y, 
 // Backward of one convolution, shared by the training step below and by the single-operator test hooks
 // (ops_abi.hip), so that the isolation tests exercise exactly the launches a training step makes.
 // ---------------------------------------------------------------------------
+// -3 from spk_conv_launch: the candidate pinned by spk_op_conv_pin is not instantiated for this problem
+static int dgrad_rc(int r, const char* what) {
+  if (r == -3) return tfail(SPK_ERR_UNSUPPORTED, std::string(what) + ": the pinned candidate does not fit this problem");
+  if (r) return tfail(SPK_ERR_HIP, std::string(what) + " launch failed");
+  return SPK_OK;
+}
+
 // dx (+)= conv_transpose(dy, w): dy [n,oh,ow,cout], wdg = the [Cin][kh][kw][Cout] bf16 image, dx [n,ih,iw,cin]
 int spk_conv_dgrad_all(const bf16_t* dy, const bf16_t* wdg, bf16_t* dx, bool accumulate, int n, int oh, int ow,
                        int cout, int ih, int iw, int cin, int k, int stride, int pad, hipStream_t s, BnbFuse* fuse) {
@@ -415,8 +422,7 @@ int spk_conv_dgrad_all(const bf16_t* dy, const bf16_t* wdg, bf16_t* dx, bool acc
       spk_set_bnb(a, fuse->partials, fuse->raw, fuse->mask, fuse->mean, fuse->invstd, fuse->res_src ? fuse->res_bits : nullptr);
       if (fuse->res_src) a.res = fuse->res_src;
     }
-    K_TRY(spk_conv_launch(a, CONV_MODE_DGRAD, s, fuse ? &fuse->tiles : nullptr), "conv dgrad");
-    return SPK_OK;
+    return dgrad_rc(spk_conv_launch(a, CONV_MODE_DGRAD, s, fuse ? &fuse->tiles : nullptr), "conv dgrad");
   }
   if (fuse) return tfail(SPK_ERR_ARG, "the fused BatchNorm reduction needs a single-launch (stride 1) data gradient");
   if (stride != 2) return tfail(SPK_ERR_UNSUPPORTED, "conv stride must be 1 or 2 on the training path");
@@ -441,7 +447,7 @@ int spk_conv_dgrad_all(const bf16_t* dy, const bf16_t* wdg, bf16_t* dx, bool acc
     c.Ho = h2; c.Wo = w2;
     c.M = n * h2 * w2;
     c.kt_count = nr * ns * (cout / 64);
-    K_TRY(spk_conv_launch(c, CONV_MODE_DGRAD, s, nullptr), "conv dgrad (parity class)");
+    if (const int r = dgrad_rc(spk_conv_launch(c, CONV_MODE_DGRAD, s, nullptr), "conv dgrad (parity class)")) return r;
   }
   return SPK_OK;
 }

@@ -7,6 +7,7 @@ parity test can feed a kernel known operands.  Tensor conventions: activations a
 storage), weights as float32 OIHW (handed over as [Cout][kh][kw][Cin]).  No CPU fallback.
 """
 
+import contextlib
 import ctypes as C
 
 import torch
@@ -55,8 +56,9 @@ def conv_bn_train_forward(x, weight, gamma, beta, running_mean, running_var, res
     xh = _stem_input(x) if stem else _nhwc(x.to(torch.bfloat16))
     wk = weight.float().permute(0, 2, 3, 1).contiguous()
     oh, ow = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
-    out = torch.empty((n, oh, ow, cout), dtype=torch.bfloat16, device=dev)
-    raw = torch.empty_like(out)
+    # poison: every element must be written by the launches
+    out = torch.full((n, oh, ow, cout), float("nan"), dtype=torch.bfloat16, device=dev)
+    raw = torch.full_like(out, float("nan"))
     mask = torch.zeros((n * oh * ow, cout // 8), dtype=torch.uint8, device=dev)
     stats = torch.empty((2, cout), dtype=torch.float32, device=dev)
     resh = _nhwc(res.to(torch.bfloat16)) if res is not None else None
@@ -133,6 +135,20 @@ def conv_dgrad_bn_backward(dy, weight, in_hw, raw, mask, mean, invstd, gamma, pa
             _p(dyh), _p(wk), _p(dx), int(accumulate_into is not None), _p(rawh), _p(mask), _p(mean), _p(invstd), _p(gamma),
             _p(dgamma), _p(dbeta), _p(dyp), n, h, w, cin, cout, k, pad, int(bool(relu)), _p(rsh), _p(res_bits), _stream(dev)))
     return {"g": _nchw(dx), "dy": _nchw(dyp), "dgamma": dgamma, "dbeta": dbeta}
+
+
+@contextlib.contextmanager
+def pinned_conv(cfg, dma, nbuf=-1):
+    """Every implicit-GEMM convolution inside the block runs tile config `cfg` with main-loop flavour `dma`, every weight
+    gradient `nbuf` LDS stages (spk_op_conv_pin; -1: the tuner decides).  A flavour that the tile does not instantiate
+    makes the hooks raise RuntimeError "does not fit".  The pin is process-wide and is lifted on exit, however the block
+    ends."""
+    so = lib.load()
+    lib.check(so.spk_op_conv_pin(int(cfg), int(dma), int(nbuf)))
+    try:
+        yield
+    finally:
+        lib.check(so.spk_op_conv_pin(-1, -1, -1))
 
 
 def conv_wgrad(x, dy, k, stride=1, pad=0):
