@@ -118,6 +118,12 @@ const char* spk_version(void);
  * spk_model_load_param. */
 int spk_model_create(const spk_layer_desc* layers, int n_layers, int in_chans,
                      int num_classes, int device, spk_model** out);
+/* The same with one Conv2d `groups` value per layer (torchvision ResNeXt: conv2 of every bottleneck has groups > 1);
+ * groups == NULL is spk_model_create.  A layer with groups > 1 must be a conv with k 3, pad 1, stride 1 or 2,
+ * cin == cout a multiple of 16 and 4, 8, 16, 32 or 64 channels per group, no shortcut operand and no activation but
+ * ReLU (else SPK_ERR_UNSUPPORTED).  Its weight tensor is [cout][cin / groups][k][k], as in the state_dict. */
+int spk_model_create_grouped(const spk_layer_desc* layers, const int32_t* groups, int n_layers, int in_chans,
+                             int num_classes, int device, spk_model** out);
 void spk_model_destroy(spk_model* m);
 /* net.to(device) has no counterpart (the handle lives on one GPU); the
  * stream is a hipStream_t (0 = default stream). */
@@ -307,6 +313,21 @@ int spk_op_conv_pin(int cfg, int dma, int wgrad_nbuf);
 /* Conv2d weight gradient: dw [Cout][kh][kw][Cin] float32 from x [n,h,w,cin] and dy [n,ho,wo,cout]. */
 int spk_op_conv_wgrad(const void* x_dev, const void* dy_dev, float* dw_dev, int n, int h, int w, int cin, int cout,
                       int k, int stride, int pad, void* hip_stream);
+/* Grouped 3x3 pad-1 convolution, stride 1 or 2 (csrc/conv_group.hip: the conv2 of a ResNeXt bottleneck, Conv2d(c, c, 3,
+ * stride, 1, groups) in `net(x)` and in the training step, sykepic/train/train.py:240,242).  NHWC activations, fp32 weights
+ * and weight gradients [c][3][3][c / groups] (as the other single-operator hooks: input channel innermost); h, w are the conv INPUT size; c a multiple of 16 and
+ * 4 / 8 / 16 / 32 / 64 channels per group, else SPK_ERR_UNSUPPORTED.  Synchronous.
+ * spk_op_conv_group: y = relu?(conv * bn_scale + bn_bias), x / y fp16 (bf16 == 0) or bf16; bn_scale == bn_bias == NULL:
+ *   the raw conv output, as the training forward stores it before its BatchNorm.
+ * spk_op_conv_group_dgrad: dx [n,h,w,c] (= or, accumulate != 0, +=) conv_transpose(dy), bf16.
+ * spk_op_conv_group_wgrad: dw from x [n,h,w,c] and dy [n,ho,wo,c], bf16. */
+int spk_op_conv_group(const void* x_dev, const float* w_dev, const float* bn_scale_dev, const float* bn_bias_dev,
+                      void* y_dev, int n, int h, int w, int c, int groups, int stride, int relu, int bf16,
+                      void* hip_stream);
+int spk_op_conv_group_dgrad(const void* dy_dev, const float* w_dev, void* dx_dev, int accumulate, int n, int h, int w,
+                            int c, int groups, int stride, void* hip_stream);
+int spk_op_conv_group_wgrad(const void* x_dev, const void* dy_dev, float* dw_dev, int n, int h, int w, int c, int groups,
+                            int stride, void* hip_stream);
 /* fp8 pointwise conv (the 1x1 convs of the fp8 EfficientNet mode): y = act((e4m3(A) . e4m3(W)^T) * factor + bias)
  * (+ res).  x: [m_rows][cin] fp16 (a_fp8 = 0: converted as x / a_scale) or e4m3 bytes (a_fp8 = 1: value = byte *
  * a_scale; gate, optional: fp32 [m_rows / hw][cin] multiplied in and re-rounded); w: float32 [cout][cin];

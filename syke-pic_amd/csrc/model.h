@@ -32,6 +32,7 @@ struct TDim {
 struct Layer {
   spk_layer_desc d;
   int mode = 0;     // CONV_MODE_*
+  int groups = 1;   // Conv2d groups (> 1: CONV_MODE_GROUP, weights [cout][cin / groups][k][k])
   int kpad = 0;     // GEMM K of the packed weights
   int p_w = -1, p_g = -1, p_b = -1, p_mean = -1, p_var = -1, p_nbt = -1;
   int p_w2 = -1, p_b2 = -1;       // SE: fc2 (p_w / p_b hold fc1)

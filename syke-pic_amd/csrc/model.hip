@@ -62,7 +62,22 @@ static int add_param(spk_model* m, const std::string& key, int kind, int layer, 
 
 extern "C" int spk_model_create(const spk_layer_desc* layers, int n_layers, int in_chans,
                                 int num_classes, int device, spk_model** out) {
+  return spk_model_create_grouped(layers, nullptr, n_layers, in_chans, num_classes, device, out);
+}
+
+extern "C" int spk_model_create_grouped(const spk_layer_desc* layers, const int32_t* groups, int n_layers, int in_chans,
+                                        int num_classes, int device, spk_model** out) {
   if (!layers || n_layers <= 0 || !out) return fail(SPK_ERR_ARG, "spk_model_create: bad arguments");
+  for (int i = 0; groups && i < n_layers; ++i) {
+    const spk_layer_desc& d = layers[i];
+    if (groups[i] < 1) return fail(SPK_ERR_ARG, "spk_model_create_grouped: groups must be >= 1");
+    if (groups[i] == 1) continue;
+    if (d.kind != SPK_OP_CONV || d.cin != d.cout || d.res >= 0 || d.relu > SPK_ACT_RELU ||
+        !spk_group_conv_ok(d.cin, groups[i], d.k, d.stride, d.pad))
+      return fail(SPK_ERR_UNSUPPORTED, std::string("grouped conv ") + d.name +
+                                           ": needs k 3, pad 1, stride 1 or 2, cin == cout a multiple of 16, 4 / 8 / 16 / 32 / "
+                                           "64 channels per group, no shortcut, no activation but ReLU");
+  }
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev)
@@ -99,6 +114,7 @@ extern "C" int spk_model_create(const spk_layer_desc* layers, int n_layers, int 
   for (int i = 0; i < n_layers; ++i) {
     Layer& L = m->layers[i];
     L.d = layers[i];
+    L.groups = groups ? groups[i] : 1;
     L.d.name[sizeof L.d.name - 1] = 0;
     L.d.bn[sizeof L.d.bn - 1] = 0;
     m->n_tensors = std::max(m->n_tensors, std::max(L.d.dst, std::max(L.d.src, L.d.res)) + 1);
@@ -120,6 +136,10 @@ extern "C" int spk_model_create(const spk_layer_desc* layers, int n_layers, int 
       if (stem) L.cin_p = 4;
       L.mode = stem7 ? CONV_MODE_STEM : (stem3 ? CONV_MODE_STEM3 : CONV_MODE_GENERIC);
       L.kpad = stem7 ? 256 : L.d.k * L.d.k * L.cin_p;
+      if (L.groups > 1) {   // conv_group.hip, on the fp32 master weights: no packed image, no dense or fused kernel
+        L.mode = CONV_MODE_GROUP;
+        L.kpad = L.d.k * L.d.k * (L.d.cin / L.groups);
+      }
       if (stem3 || (!stem && L.cin_p != L.d.cin) || L.cout_p != L.d.cout || L.d.relu == SPK_ACT_SILU) m->effnet = true;
     } else if (L.d.kind == SPK_OP_DWCONV) {
       if ((L.d.k != 3 && L.d.k != 5) || L.d.cin != L.d.cout || L.d.pad != (L.d.k - 1) / 2) {
@@ -181,7 +201,7 @@ extern "C" int spk_model_create(const spk_layer_desc* layers, int n_layers, int 
     const std::string nm = L.d.name, bn = L.d.bn;
     if (L.d.kind == SPK_OP_CONV) {
       L.p_w = add_param(m, nm + ".weight", PK_CONV_W, oi, SPK_DTYPE_F32,
-                        {L.d.cout, L.d.cin, L.d.k, L.d.k}, true);
+                        {L.d.cout, L.d.cin / L.groups, L.d.k, L.d.k}, true);
       L.p_g = add_param(m, bn + ".weight", PK_BN_W, oi, SPK_DTYPE_F32, {L.d.cout}, true);
       L.p_b = add_param(m, bn + ".bias", PK_BN_B, oi, SPK_DTYPE_F32, {L.d.cout}, true);
       L.p_mean = add_param(m, bn + ".running_mean", PK_BN_MEAN, oi, SPK_DTYPE_F32, {L.d.cout}, false);
@@ -269,6 +289,8 @@ extern "C" int spk_model_create(const spk_layer_desc* layers, int n_layers, int 
       L.wpack_off = dwp;  // fp32 fc2 weights transposed: [squeeze][cout_p]
       dwp += (size_t)L.d.k * L.cout_p;
       continue;
+    } else if (L.d.kind == SPK_OP_CONV && L.mode == CONV_MODE_GROUP) {
+      // (reads the fp32 master weights: scale / shift only)
     } else if (L.d.kind == SPK_OP_CONV) {
       L.wpack_off = wpack;
       wpack += (size_t)2 * L.cout_p * L.kpad;  // room for the hi + lo halves
@@ -620,6 +642,7 @@ int spk_commit(spk_model* m) {
     if (L.d.kind == SPK_OP_CONV && (L.mode == CONV_MODE_STEM || L.mode == CONV_MODE_STEM3) &&
         spk_launch_scale_inplace(sc, 1.0f / SPK_INPUT_SCALE, L.d.cout, m->stream))
       return fail(SPK_ERR_HIP, "stem scale launch failed");
+    if (L.mode == CONV_MODE_GROUP) continue;   // fp32 master weights, no image (and no zero-sum rounding: nothing is rounded)
     int r;
     // the weights every image of this layer is packed from: the fp32 master, or its zero-sum rounded copy (values that
     // ARE fp16 numbers, so each pack kernel's own conversion is exact): master layout [cout][tap][cin], one balanced
@@ -1294,6 +1317,13 @@ static int run_conv_eval(spk_model* m, Layer& L, int nb) {
                            (bf16_t*)m->TI(L.d.dst), nb, in.h, in.w, in.w, o.h, o.w, L.d.cout, L.cout_p, L.d.relu,
                            m->infer_dt, m->stream))
       return fail(SPK_ERR_HIP, std::string("stem launch failed for ") + L.d.name);
+    return SPK_OK;
+  }
+  if (L.mode == CONV_MODE_GROUP) {
+    const float* sc = m->scale_bias + L.sb_off;
+    if (spk_launch_group_fwd((const bf16_t*)m->TI(L.d.src), m->P(L.p_w), sc, sc + L.cout_p, (bf16_t*)m->TI(L.d.dst), nb,
+                             in.h, in.w, L.d.cin, L.groups, L.d.stride, L.d.relu, m->infer_dt, m->stream))
+      return fail(SPK_ERR_HIP, std::string("grouped conv launch failed for ") + L.d.name);
     return SPK_OK;
   }
   ConvArgs a;
@@ -2059,7 +2089,7 @@ extern "C" int spk_model_profile_infer(spk_model* m, const void* x, int n, int h
     char nm[96];
     if (L.d.kind == SPK_OP_CONV) {
       const int cin = L.d.cin;
-      fl = 2.0 * nb * o.h * o.w * (double)L.d.cout * cin * L.d.k * L.d.k;
+      fl = 2.0 * nb * o.h * o.w * (double)L.d.cout * cin * L.d.k * L.d.k / L.groups;
       const double real_in = L.mode == CONV_MODE_STEM ? (double)nb * in.h * in.w * 8 : in_b;
       by = real_in + out_b + (L.d.res >= 0 ? out_b : 0) + (double)L.d.cout * L.kpad * 2;
       snprintf(nm, sizeof nm, "%s", L.d.name);

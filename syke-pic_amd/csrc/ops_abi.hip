@@ -526,3 +526,47 @@ extern "C" int spk_op_zero_sum_round(const float* w, const float* mu, float* out
   if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "zero-sum rounding kernel failed");
   return SPK_OK;
 }
+
+// Grouped 3x3 pad-1 convolution (conv_group.hip: conv2 of a ResNeXt bottleneck) - the launches the eval forward, the
+// training forward and the training backward make for such a layer.  Weights fp32 [c][3][3][c / groups].
+extern "C" int spk_op_conv_group(const void* x, const float* w, const float* bn_scale, const float* bn_bias, void* y, int n,
+                                 int h, int wd, int c, int groups, int stride, int relu, int bf16, void* stream) {
+  if (!x || !w || !y || n < 1 || h < 1 || wd < 1 || (!bn_scale) != (!bn_bias)) return ofail(SPK_ERR_ARG, "op_conv_group: bad arguments");
+  if (!spk_group_conv_ok(c, groups, 3, stride, 1))
+    return ofail(SPK_ERR_UNSUPPORTED, "op_conv_group: c a multiple of 16, 4 / 8 / 16 / 32 / 64 channels per group, stride 1 or 2");
+  hipStream_t s = (hipStream_t)stream;
+  O_TRY(spk_launch_group_fwd((const bf16_t*)x, w, bn_scale, bn_bias, (bf16_t*)y, n, h, wd, c, groups, stride, relu,
+                             bf16 ? DT_BF16 : DT_F16, s), "grouped conv");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_conv_group: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_conv_group_dgrad(const void* dy, const float* w, void* dx, int accumulate, int n, int h, int wd, int c,
+                                       int groups, int stride, void* stream) {
+  if (!dy || !w || !dx || n < 1 || h < 1 || wd < 1) return ofail(SPK_ERR_ARG, "op_conv_group_dgrad: bad arguments");
+  if (!spk_group_conv_ok(c, groups, 3, stride, 1))
+    return ofail(SPK_ERR_UNSUPPORTED, "op_conv_group_dgrad: c a multiple of 16, 4 / 8 / 16 / 32 / 64 channels per group, stride 1 or 2");
+  hipStream_t s = (hipStream_t)stream;
+  O_TRY(spk_launch_group_dgrad((const bf16_t*)dy, w, (bf16_t*)dx, accumulate != 0, n, h, wd, c, groups, stride, DT_BF16, s),
+        "grouped conv dgrad");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_conv_group_dgrad: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_conv_group_wgrad(const void* x, const void* dy, float* dw, int n, int h, int wd, int c, int groups,
+                                       int stride, void* stream) {
+  if (!x || !dy || !dw || n < 1 || h < 1 || wd < 1) return ofail(SPK_ERR_ARG, "op_conv_group_wgrad: bad arguments");
+  if (!spk_group_conv_ok(c, groups, 3, stride, 1))
+    return ofail(SPK_ERR_UNSUPPORTED, "op_conv_group_wgrad: c a multiple of 16, 4 / 8 / 16 / 32 / 64 channels per group, stride 1 or 2");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t M = (int64_t)n * ((h - 1) / stride + 1) * ((wd - 1) / stride + 1);
+  Scratch sc;
+  float* slabs = sc.get<float>(spk_group_wgrad_slab_floats(M, c, groups));
+  if (!slabs) return ofail(SPK_ERR_HIP, "hipMalloc failed");
+  int chunks = 0;
+  O_TRY(spk_launch_group_wgrad((const bf16_t*)x, (const bf16_t*)dy, slabs, n, h, wd, c, groups, stride, DT_BF16, &chunks, s),
+        "grouped conv wgrad");
+  O_TRY(spk_launch_slab_reduce(slabs, dw, (size_t)c * 9 * (c / groups), chunks, s), "grouped conv wgrad reduce");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_conv_group_wgrad: kernel failed");
+  return SPK_OK;
+}

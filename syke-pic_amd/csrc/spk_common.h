@@ -81,7 +81,8 @@ template <int DT> __device__ __forceinline__ f32x4_t mfma16(const u32x4_t a, con
 // Epilogue: v = acc*scale[c] + bias[c] (+ residual) (ReLU) -> bf16.
 // ---------------------------------------------------------------------------
 enum { CONV_MODE_GENERIC = 0, CONV_MODE_STEM = 1, CONV_MODE_DGRAD = 2, CONV_MODE_STEM3 = 3 /* 3x3/2 direct stem */,
-       CONV_MODE_DGRAD_BNB = 4 /* kernel-internal: DGRAD + the BatchNorm-backward sums of the producer (spk_set_bnb) */ };
+       CONV_MODE_DGRAD_BNB = 4 /* kernel-internal: DGRAD + the BatchNorm-backward sums of the producer (spk_set_bnb) */,
+       CONV_MODE_GROUP = 5 /* grouped 3x3 conv (conv_group.hip): never an implicit-GEMM or fused dense kernel */ };
 
 struct ConvArgs {
   const bf16_t* x;      // [N,H,W,Cin]   (stem mode: Cin stored = 4)
@@ -397,3 +398,17 @@ void spk_wgrad_plan(int M, int Cout, int Ktot, int* splits, int* pix_per_split);
 int spk_wgrad_launch(const bf16_t* x, const bf16_t* dy, float* slabs, int N, int H, int W, int Cin,
                      int Ho, int Wo, int Cout, int k, int stride, int pad, int stem, int splits,
                      int pix_per_split, hipStream_t s);
+
+// Grouped 3x3 pad-1 convolution, stride 1 / 2 (conv_group.hip: the ResNeXt bottleneck conv2).  x / y / dy / dx NHWC
+// 16-bit (dt DT_F16 / DT_BF16), w fp32 [c][3][3][c / groups] (the master layout).  Channels per group 4, 8, 16, 32 or 64,
+// c a multiple of 16; -3: a shape these kernels do not take.  fwd: scale == nullptr stores the raw sums, else
+// act(sum * scale + bias).  wgrad: per-chunk slabs in w's layout, reduced by spk_launch_slab_reduce(slabs, dw,
+// c * 9 * c / groups, *chunks).
+bool spk_group_conv_ok(int c, int groups, int k, int stride, int pad);
+int spk_launch_group_fwd(const bf16_t* x, const float* w, const float* scale, const float* bias, bf16_t* y, int n, int h,
+                         int wd, int c, int groups, int stride, int relu, int dt, hipStream_t s);
+int spk_launch_group_dgrad(const bf16_t* dy, const float* w, bf16_t* dx, bool accumulate, int n, int h, int wd, int c,
+                           int groups, int stride, int dt, hipStream_t s);
+size_t spk_group_wgrad_slab_floats(int64_t M, int c, int groups);
+int spk_launch_group_wgrad(const bf16_t* x, const bf16_t* dy, float* slabs, int n, int h, int wd, int c, int groups,
+                           int stride, int dt, int* chunks, hipStream_t s);

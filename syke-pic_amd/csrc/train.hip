@@ -252,6 +252,8 @@ static int plan_train(spk_model* m, int n, int h, int w) {
       const int M = n * o.h * o.w;
       if (L.d.kind == SPK_OP_DWCONV) {
         max_slab = std::max(max_slab, (size_t)spk_dw_wgrad_rows(M, C) * L.d.cout * L.d.k * L.d.k);
+      } else if (L.mode == CONV_MODE_GROUP) {
+        max_slab = std::max(max_slab, spk_group_wgrad_slab_floats(M, L.d.cout, L.groups));
       } else if (L.mode == CONV_MODE_STEM3) {
         int ppb;
         max_slab = std::max(max_slab, (size_t)spk_stem3_wgrad_blocks(M, &ppb) * L.d.cout * 9 * L.d.cin);
@@ -353,7 +355,8 @@ static int repack_weights(spk_model* m) {
       K_TRY(padd(m->params[L.p_w].off, t->conv[i].dwt_off, L.d.cout, L.d.k * L.d.k, 0, L.cout_p, 0, 2), "dw_pack");
       continue;
     }
-    if (L.d.kind != SPK_OP_CONV || L.mode == CONV_MODE_STEM3) continue;   // the 3x3 stem reads the master weights
+    // the 3x3 stem and the grouped convs read the master weights
+    if (L.d.kind != SPK_OP_CONV || L.mode == CONV_MODE_STEM3 || L.mode == CONV_MODE_GROUP) continue;
     if (m->effnet) {   // channel-padded GEMM images, zeros outside the layer's own widths
       for (int kind = 0; kind < 2; ++kind)
         K_TRY(padd(m->params[L.p_w].off, kind ? t->conv[i].wdg_off : t->conv[i].wfwd_off, L.d.cout, L.d.k * L.d.k, L.d.cin,
@@ -542,6 +545,10 @@ extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, in
           K_TRY(spk_launch_stem3_train_fwd((const bf16_t*)m->T(0), m->P(L.p_w), t->RAW(i), n, in.h, w, in.w, L.d.cin,
                                            L.d.cout, C, o.h, o.w, s, 1.0f / SPK_INPUT_SCALE), "stem3 fwd");
           K_TRY(spk_launch_col_stats(t->RAW(i), part, M, C, &m_tiles, s), "col_stats");
+        } else if (L.mode == CONV_MODE_GROUP) {
+          K_TRY(spk_launch_group_fwd((const bf16_t*)m->T(L.d.src), m->P(L.p_w), nullptr, nullptr, t->RAW(i), n, in.h, in.w,
+                                     C, L.groups, L.d.stride, 0, DT_BF16, s), "grouped conv fwd");
+          K_TRY(spk_launch_col_stats(t->RAW(i), part, M, C, &m_tiles, s), "col_stats");
         } else {
           ConvArgs a;
           fill_conv(a, (const bf16_t*)m->T(L.d.src), t->wpack + t->conv[i].wfwd_off, t->RAW(i), n, in.h, in.w,
@@ -705,7 +712,7 @@ extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, in
   float* fpart = (float*)((char*)t->arena + t->fpart_off);
   auto fuse_target = [&](int i) -> int {   // producer layer whose reduction dgrad(i) can carry, or -1
     const Layer& L = m->layers[i];
-    if (!bnb_on || m->effnet || L.d.stride != 1 || fpart_owner >= 0) return -1;
+    if (!bnb_on || m->effnet || L.d.stride != 1 || fpart_owner >= 0 || L.mode == CONV_MODE_GROUP) return -1;
     const int cat = L.d.k == 1 ? (has_grad[L.d.src] || deferred[L.d.src] >= 0 ? 1 : 2) : 4;
     if (!(bnb_mask & cat)) return -1;
     int prod = -1;
@@ -864,6 +871,31 @@ extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, in
                 HIP_TRY(hipEventRecord(t->ev_dy_free[slot], ws));
                 t->dy_busy[slot] = true;
               }
+            }
+            mark(m, PH_WGRAD_REDUCE);
+          }
+          break;
+        }
+        if (L.mode == CONV_MODE_GROUP) {   // conv_group.hip on the fp32 master weights
+          if (needs[L.d.src]) {
+            if (deferred[L.d.src] >= 0)
+              return tfail(SPK_ERR_STATE, std::string("deferred shortcut gradient cannot land in grouped conv ") + L.d.name);
+            K_TRY(spk_launch_group_dgrad(dy, m->P(L.p_w), (bf16_t*)t->G(L.d.src), has_grad[L.d.src] != 0, n, in.h, in.w, C,
+                                         L.groups, L.d.stride, DT_BF16, s), "grouped conv dgrad");
+            mark(m, PH_CONV_DGRAD);
+            has_grad[L.d.src] = 1;
+          }
+          if (pw.requires_grad) {
+            const hipStream_t ws = side_on ? t->side : s;
+            if (side_on) HIP_TRY(hipStreamWaitEvent(ws, t->ev_dy_ready[slot], 0));
+            int chunks = 0;
+            K_TRY(spk_launch_group_wgrad((const bf16_t*)m->T(L.d.src), dy, slabs, n, in.h, in.w, C, L.groups, L.d.stride,
+                                         DT_BF16, &chunks, ws), "grouped conv wgrad");
+            mark(m, PH_CONV_WGRAD);
+            K_TRY(spk_launch_slab_reduce(slabs, t->gbuf + pw.off, (size_t)pw.numel, chunks, ws), "grouped conv wgrad reduce");
+            if (side_on && !t->conv[i].dy_off) {
+              HIP_TRY(hipEventRecord(t->ev_dy_free[slot], ws));
+              t->dy_busy[slot] = true;
             }
             mark(m, PH_WGRAD_REDUCE);
           }

@@ -23,6 +23,20 @@ _RESNETS = {
     "resnet50": ("bottleneck", (3, 4, 6, 3)),
     "resnet101": ("bottleneck", (3, 4, 23, 3)),
     "resnet152": ("bottleneck", (3, 8, 36, 3)),
+    "resnext50_32x4d": ("bottleneck", (3, 4, 6, 3)),
+    "resnext101_32x8d": ("bottleneck", (3, 4, 23, 3)),
+    "resnext101_64x4d": ("bottleneck", (3, 4, 23, 3)),
+    "wide_resnet50_2": ("bottleneck", (3, 4, 6, 3)),
+    "wide_resnet101_2": ("bottleneck", (3, 4, 23, 3)),
+}
+# torchvision ResNet(groups, width_per_group) of the bottleneck variants (default 1, 64): the middle width of a block is
+# int(planes * width_per_group / 64) * groups and its 3x3 conv has `groups` groups; everything else is ResNet-50/101's
+_RESNET_WIDTH = {
+    "resnext50_32x4d": (32, 4),
+    "resnext101_32x8d": (32, 8),
+    "resnext101_64x4d": (64, 4),
+    "wide_resnet50_2": (1, 128),
+    "wide_resnet101_2": (1, 128),
 }
 
 
@@ -77,6 +91,7 @@ class Op:
     child: int = -1       # index of the owning child of ``base`` (-1: head)
     last_bn: bool = False  # last BN of a residual block (synthetic init only)
     p: float = 0.0        # dropout probability; on a block-closing conv with a shortcut: stochastic-depth probability
+    groups: int = 1       # Conv2d groups (ResNeXt: the 3x3 conv of every bottleneck)
 
 
 @dataclass
@@ -177,6 +192,7 @@ def build_graph(network, num_classes, head=(256, 128), dropout=(), in_chans=3, s
             f"network {network!r} has no MI355X path yet; supported: {supported_networks()}"
         )
     kind, depths = _RESNETS[network]
+    groups, width_per_group = _RESNET_WIDTH.get(network, (1, 64))
     expansion = 1 if kind == "basic" else 4
     g = Graph(network, in_chans, num_classes, 512 * expansion)
     ops = g.ops
@@ -215,18 +231,19 @@ def build_graph(network, num_classes, head=(256, 128), dropout=(), in_chans=3, s
                 ops.append(Op(OP_CONV, f"{pre}.conv2", f"{pre}.bn2", planes, planes, 3, 1, 1,
                               True, a, o, ident, child, True))
             else:
+                width = int(planes * (width_per_group / 64.0)) * groups
                 a = new_t()
-                ops.append(Op(OP_CONV, f"{pre}.conv1", f"{pre}.bn1", inplanes, planes, 1, 1, 0,
+                ops.append(Op(OP_CONV, f"{pre}.conv1", f"{pre}.bn1", inplanes, width, 1, 1, 0,
                               True, cur, a, -1, child))
                 b2 = new_t()
-                ops.append(Op(OP_CONV, f"{pre}.conv2", f"{pre}.bn2", planes, planes, 3, stride,
-                              1, True, a, b2, -1, child))
+                ops.append(Op(OP_CONV, f"{pre}.conv2", f"{pre}.bn2", width, width, 3, stride,
+                              1, True, a, b2, -1, child, groups=groups))
                 if need_ds:
                     ident = new_t()
                     ops.append(Op(OP_CONV, f"{pre}.downsample.0", f"{pre}.downsample.1",
                                   inplanes, outp, 1, stride, 0, False, cur, ident, -1, child))
                 o = new_t()
-                ops.append(Op(OP_CONV, f"{pre}.conv3", f"{pre}.bn3", planes, outp, 1, 1, 0,
+                ops.append(Op(OP_CONV, f"{pre}.conv3", f"{pre}.bn3", width, outp, 1, 1, 0,
                               True, b2, o, ident, child, True))
             cur = o
             inplanes = outp
@@ -308,7 +325,7 @@ def param_specs(g):
     for item in ordered:
         group = [item] if isinstance(item, Op) else sorted(blocks[item], key=order_key)
         for op in group:
-            specs.append((f"{op.name}.weight", (op.cout, op.cin, op.k, op.k), "conv_w"))
+            specs.append((f"{op.name}.weight", (op.cout, op.cin // op.groups, op.k, op.k), "conv_w"))
             bn(op.bn, op.cout, op.last_bn)
     lin = [op for op in g.ops if op.kind == OP_LINEAR]
     for op in lin:
@@ -329,7 +346,7 @@ def conv_flops_per_image(g, h, w):
             ow = (iw + 2 * op.pad - op.k) // op.stride + 1
             dims[op.dst] = (oh, ow)
             if op.kind == OP_CONV:
-                total += 2 * oh * ow * op.cout * op.cin * op.k * op.k
+                total += 2 * oh * ow * op.cout * (op.cin // op.groups) * op.k * op.k
             elif op.kind == OP_DWCONV:
                 total += 2 * oh * ow * op.cout * op.k * op.k
         elif op.kind == OP_GAVGPOOL:
@@ -348,7 +365,7 @@ _RESNET_CHILDREN = {"conv1": 0, "bn1": 1, "layer1": 4, "layer2": 5, "layer3": 6,
 def backbone_key(network, key):
     """state_dict key of a torchvision backbone checkpoint (``resnet50-*.pth``: ``conv1.weight``,
     ``layer1.0.conv1.weight``, ``fc.weight`` ...; EfficientNet: ``features.1.0.block...``,
-    ``classifier.1.weight``) -> key of the same tensor under ``TorchVisionNet.base`` (``base.<child>...``),
+    ``classifier.1.weight``; ResNeXt / Wide ResNet: the ResNet layout) -> key of the same tensor under ``TorchVisionNet.base`` (``base.<child>...``),
     or None for the classifier the reference drops (network.py:49-55)."""
     first, _, rest = key.partition(".")
     if network in _EFFNETS:

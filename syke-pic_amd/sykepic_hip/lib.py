@@ -58,6 +58,8 @@ SYMBOLS = {
     "spk_version": (C.c_char_p, []),
     "spk_model_create": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.POINTER(_P)]),
+    "spk_model_create_grouped": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int,
+                                           C.c_int, C.POINTER(_P)]),
     "spk_model_destroy": (None, [_P]),
     "spk_model_set_stream": (C.c_int, [_P, _P]),
     "spk_model_num_params": (C.c_int, [_P]),
@@ -100,6 +102,9 @@ SYMBOLS = {
     "spk_op_bn_backward": (C.c_int, [_P] * 10 + [C.c_int] * 4 + [_P]),
     "spk_op_conv_dgrad": (C.c_int, [_P, _P, _P] + [C.c_int] * 9 + [_P]),
     "spk_op_conv_wgrad": (C.c_int, [_P, _P, _P] + [C.c_int] * 8 + [_P]),
+    "spk_op_conv_group": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 8 + [_P]),
+    "spk_op_conv_group_dgrad": (C.c_int, [_P, _P, _P] + [C.c_int] * 7 + [_P]),
+    "spk_op_conv_group_wgrad": (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [_P]),
     "spk_op_conv_pin": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "spk_op_pw_fp8": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_float, C.c_float, _P]),

@@ -148,8 +148,13 @@ class HipNet:
             d.relu, d.src, d.dst, d.res, d.child, d.p = int(op.relu), op.src, op.dst, op.res, op.child, op.p
             d.name, d.bn = op.name.encode(), op.bn.encode()
         handle = C.c_void_p()
-        lib.check(self._lib.spk_model_create(descs, len(descs), self.graph.in_chans, self.num_classes,
-                                             idx, C.byref(handle)))
+        groups = [op.groups for op in self.graph.ops]
+        if any(gr != 1 for gr in groups):
+            lib.check(self._lib.spk_model_create_grouped(descs, (C.c_int32 * len(groups))(*groups), len(descs),
+                                                         self.graph.in_chans, self.num_classes, idx, C.byref(handle)))
+        else:
+            lib.check(self._lib.spk_model_create(descs, len(descs), self.graph.in_chans, self.num_classes,
+                                                 idx, C.byref(handle)))
         self._h = handle
         eps, momentum = arch.bn_params(name)
         if (eps, momentum) != (1e-5, 0.1):

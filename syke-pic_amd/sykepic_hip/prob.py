@@ -20,6 +20,8 @@ from pathlib import Path
 import numpy as np
 import torch
 
+from . import arch
+
 SOFTMAX_EXP = 1.3
 FILE_SUFFIX = ".prob"
 log = logging.getLogger("prob")
@@ -255,7 +257,7 @@ def arm_auto_calibration(net, model_dir):
     error is activation storage: DESIGN.md section 3) and keep the default.  SYKEPIC_AUTO_CALIBRATE=0 switches it off."""
     if os.environ.get("SYKEPIC_AUTO_CALIBRATE", "1") == "0" or os.environ.get("SYKEPIC_CALIBRATED", "1") == "0":
         return
-    if not net.graph.network.startswith("resnet"):
+    if net.graph.network not in arch._RESNETS:
         return
     net._auto_calibration_dir = Path(model_dir)
 
