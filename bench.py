@@ -10,11 +10,13 @@ Inputs are resident in HBM before the timed region.  Weak scaling: every rank
 runs the same per-GPU batch (inference needs no collective; training
 all-reduces the flat gradient buffer over RCCL).
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernels
-(the conv kernels of the forward: conv_bneck / conv_pw / conv_pwr / conv_c3 / conv_igemm / conv_stem): algorithmic conv FLOPs / their
-HIP-event time.  The
-`cpu_baseline` leg times the oracle (torch fp32 CPU restatement of the
-reference path) on this box's host cores on a bounded sample.
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: set-up, warm-up, the timed
+steps, --dump-outputs, the line (`roofline` null).  `--full` adds everything else, after the timed steps of each mode:
+`roofline` for the dominant kernels (the conv kernels of the forward: conv_bneck / conv_pw / conv_pwr / conv_c3 /
+conv_igemm / conv_stem): algorithmic conv FLOPs / their HIP-event time, from a per-layer / per-phase profile of their own;
+`uncalibrated_ms_per_step`; the `cpu_baseline` leg, which times the oracle (torch fp32 CPU restatement of the reference
+path) on this box's host cores on a bounded sample, and the `parity` of the timed mode against it; `params_equal` of a
+multi-GPU line.
 """
 
 import argparse
@@ -57,12 +59,18 @@ def parse():
                          "only the layers that write the residual trunk (1.3e-3 worst case); fast: plain fp16 "
                          "(1.5e-3); bf16 (5e-3); fp8: e4m3 inside the EfficientNet MBConv blocks (BASELINE config 5; "
                          "EfficientNets only, not a parity mode)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--layers-out", default="", help="write the per-layer table (JSON) here")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the per-layer / per-phase kernel profile "
+                         "behind `roofline`, `uncalibrated_ms_per_step`, the CPU baseline and the parity against the oracle, "
+                         "`params_equal` of a multi-GPU line")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline and parity (and, on one GPU, without the training forward of the "
+                         "parity images before the timed training steps, in a plain run too)")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="--full: time budget of the CPU baseline")
+    ap.add_argument("--layers-out", default="", help="--full: write the per-layer table (JSON) here")
     ap.add_argument("--no-kernel-profile", action="store_true",
-                    help="skip the per-layer / per-phase event profile behind `roofline` (for rocprofv3 traces: the last steps "
-                         "of the trace are then timed steps, not the single-stream profiling passes)")
+                    help="--full without the per-layer / per-phase event profile behind `roofline` and without "
+                         "`uncalibrated_ms_per_step`")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0): "
                          "infer_probabilities; train_stats (sum of loss*n, number correct) and train_state (the parameters "
@@ -71,6 +79,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.layers_out and not (args.full and not args.no_kernel_profile):
+        ap.error("--layers-out needs --full (the table comes from the kernel profile)")
     if args.precision is None:
         # the fastest mode that holds the parity tolerance: ResNets - calibrated single pass (tests/test_gpu_calibrated.py);
         # EfficientNets - `mixed`, which splits none of their convs (the weight rounding does not show beside the fp16
@@ -290,7 +300,9 @@ def run_mode(mode, args, net, x, y, dist, dev, rank, world):
         ar_marks = []   # (before, after) events around the gradient exchange of every step
         if world == 1 and not args.no_cpu_baseline and rank == 0:
             # parity of the training forward in the timed precision (bf16), BEFORE any optimizer step: loss and logits of
-            # the first PARITY_N images against the oracle's first step on them (compared below, next to cpu_baseline)
+            # the first PARITY_N images against the oracle's first step on them (compared below under --full, next to
+            # cpu_baseline).  A plain run makes this pass too: it moves the BatchNorm running statistics, so the timed steps
+            # start from the same state, and --dump-outputs writes the same model state, with and without --full
             net.reset_stats()
             lg = net.forward_backward(x[:PARITY_N], y[:PARITY_N], want_logits=True)
             parity_gpu = (net.read_stats()[0] / PARITY_N, lg.float().cpu())
@@ -341,10 +353,12 @@ def run_mode(mode, args, net, x, y, dist, dev, rank, world):
         out_dir.mkdir(parents=True, exist_ok=True)
         for name, a in last_step_outputs(mode, net, last).items():
             np.save(out_dir / f"{name}.npy", a)
-    if mode == "infer" and world == 1 and not args.no_cpu_baseline:
+    cpu_leg = args.full and world == 1 and not args.no_cpu_baseline
+    profile = args.full and not args.no_kernel_profile
+    if mode == "infer" and cpu_leg:
         parity_gpu = step()[:PARITY_N].float().cpu()     # one more forward of the timed configuration (two streams)
     uncal_ms = None
-    if mode == "infer" and args.precision == "calibrated" and world == 1 and rank == 0 and not args.no_kernel_profile:
+    if mode == "infer" and args.precision == "calibrated" and world == 1 and rank == 0 and profile:
         # what a model directory runs until it has activation means (`prob` measures them on its first batch): the default
         # hi + lo split mode, timed like the headline.  (Here, not at the end: the LAST forward of the process stays one of the
         # timed configuration - the PMC tools take their per-step figures from it.)
@@ -361,9 +375,9 @@ def run_mode(mode, args, net, x, y, dist, dev, rank, world):
                 "allreduce_bytes": int(sync.flat.numel() * sync.flat.element_size()),
                 # time the launch stream spends in the exchange (overlapped: only the wait for slices still in flight)
                 "allreduce_ms": round(ar[len(ar) // 2], 3) if ar else None,
-                "overlap": sync.overlapped,
-                # every replica must hold bit-identical parameters after the timed steps
-                "params_equal": replicas_equal(net, dist)})
+                "overlap": sync.overlapped})
+            if args.full:   # every replica must hold bit-identical parameters after the timed steps
+                dist_rec["params_equal"] = replicas_equal(net, dist)
     if mode == "train" and sync:
         sync.close()   # the per-phase profile below runs on rank 0 alone: no collectives from here on
     if dist is not None:
@@ -373,15 +387,36 @@ def run_mode(mode, args, net, x, y, dist, dev, rank, world):
     if rank != 0:
         return None
 
-    if args.no_kernel_profile:
-        total_images = args.batch * world * args.steps
-        return {"metric": f"IFCB images/sec, {args.network} {args.size}x{args.size} {mode} step",
-                "value": round(total_images / dt, 1), "unit": "images/s", "n_gpus": world, "steps": args.steps,
-                "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "step_ms": step_ms,
-                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
-                "config": {"workload": f"{args.network}_{mode}_b{args.batch}x{world}_{args.size}x{args.size}x3_"
-                                       f"{args.classes}cls_head256-128", "precision": args.precision if mode == "infer" else "bf16"},
-                "roofline": None}
+    total_images = args.batch * world * args.steps
+    out = {
+        "metric": f"IFCB images/sec, {args.network} {args.size}x{args.size} {mode} step",
+        "value": round(total_images / dt, 1), "unit": "images/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "step_ms": step_ms,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype,
+        "data": "synthetic",
+        "config": {"workload": f"{args.network}_{mode}_b{args.batch}x{world}_"
+                               f"{args.size}x{args.size}x3_{args.classes}cls_head256-128",
+                   "per_gpu_batch": args.batch, "global_batch": args.batch * world,
+                   "precision": args.precision if mode == "infer" else "bf16",
+                   "parallelism": f"dp{world}"},
+        "roofline": kernel_roofline(mode, args, net, x, y, dt) if profile else None,
+    }
+    if dist_rec is not None:
+        out["dist"] = dist_rec
+    if uncal_ms is not None:
+        out["uncalibrated_ms_per_step"] = uncal_ms
+    if cpu_leg:
+        out["cpu_baseline"], ref = cpu_baseline(args.network, args.classes, args.size, mode,
+                                                args.cpu_seconds if mode == "infer" else args.cpu_seconds / 2,
+                                                x[:PARITY_N].float().cpu(), y[:PARITY_N].cpu())
+        out["parity"] = infer_parity(parity_gpu, ref) if mode == "infer" else train_parity(*parity_gpu, ref)
+    return out
+
+
+def kernel_roofline(mode, args, net, x, y, dt):
+    """--full: the `roofline` record from a per-layer (infer) / per-phase (train) event profile of the dominant kernels
+    on one stream, taken after the timed steps; writes the table to --layers-out.  `dt`: wall time of the timed steps."""
     # ---- roofline of the dominant kernel, HIP events on the launch stream ----
     layers_out = args.layers_out and (args.layers_out if mode == args.mode or args.mode == "both" and mode == "infer"
                                       else args.layers_out + "." + mode)
@@ -458,32 +493,7 @@ def run_mode(mode, args, net, x, y, dist, dev, rank, world):
     if layers_out:
         Path(layers_out).parent.mkdir(parents=True, exist_ok=True)
         Path(layers_out).write_text(json.dumps(table, indent=1))
-
-    total_images = args.batch * world * args.steps
-    out = {
-        "metric": f"IFCB images/sec, {args.network} {args.size}x{args.size} {mode} step",
-        "value": round(total_images / dt, 1), "unit": "images/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "step_ms": step_ms,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype,
-        "data": "synthetic",
-        "config": {"workload": f"{args.network}_{mode}_b{args.batch}x{world}_"
-                               f"{args.size}x{args.size}x3_{args.classes}cls_head256-128",
-                   "per_gpu_batch": args.batch, "global_batch": args.batch * world,
-                   "precision": args.precision if mode == "infer" else "bf16",
-                   "parallelism": f"dp{world}"},
-        "roofline": roof,
-    }
-    if dist_rec is not None:
-        out["dist"] = dist_rec
-    if uncal_ms is not None:
-        out["uncalibrated_ms_per_step"] = uncal_ms
-    if world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"], ref = cpu_baseline(args.network, args.classes, args.size, mode,
-                                                args.cpu_seconds if mode == "infer" else args.cpu_seconds / 2,
-                                                x[:PARITY_N].float().cpu(), y[:PARITY_N].cpu())
-        out["parity"] = infer_parity(parity_gpu, ref) if mode == "infer" else train_parity(*parity_gpu, ref)
-    return out
+    return roof
 
 
 def uncalibrated_ms(net, x, args):

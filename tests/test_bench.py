@@ -44,3 +44,42 @@ def test_bench_dumps_the_last_timed_step(tmp_path):
     assert d["train_stats"].dtype == np.float64 and loss > 0 and 0 <= correct <= 8
     s = d["train_state"]
     assert s.dtype == np.float32 and s.size == bench.DUMP_MAX_ELEMS and np.isfinite(s).all()   # ResNet-18: 11.4 M values
+
+
+def test_layers_out_needs_full(monkeypatch, capsys):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--layers-out", "layers.json"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    assert "--layers-out needs --full" in capsys.readouterr().err
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--layers-out", "layers.json"])
+    args = bench.parse()
+    assert args.full and args.layers_out == "layers.json"
+
+
+@pytest.mark.gpu
+def test_plain_and_full_runs_time_and_dump_the_same_steps(tmp_path):
+    """A plain run prints the headline without the extras; --full adds them after the timed steps, which start from
+    the same state and compute the same outputs either way."""
+    base = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8",
+            "--size", "64", "--network", "resnet18", "--cpu-seconds", "1"]
+    res, dumps = {}, {}
+    for kind, extra in (("plain", []), ("full", ["--full"])):
+        out = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / kind)], capture_output=True, text=True,
+                             timeout=600)
+        # 4: the line is out but a parity tolerance broke (synthetic weights on 64x64 images are no parity setting)
+        assert out.returncode in ((0, 4) if extra else (0,)), out.stderr[-2000:]
+        res[kind] = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
+        dumps[kind] = {p.stem: np.load(p) for p in (tmp_path / kind).glob("*.npy")}
+    plain, full = res["plain"], res["full"]
+    for r in (plain, plain["train"]):
+        assert r["roofline"] is None and "cpu_baseline" not in r and "parity" not in r
+    assert "uncalibrated_ms_per_step" not in plain
+    for r in (full, full["train"]):
+        assert r["roofline"]["achieved"] > 0 and r["cpu_baseline"]["value"] > 0 and r["parity"]["n"] == 8
+    assert (out.returncode == 0) == (full["parity"]["ok"] and full["train"]["parity"]["ok"])
+    assert "uncalibrated_ms_per_step" in full
+    for k in ("metric", "unit", "higher_is_better", "dtype", "config"):
+        assert plain[k] == full[k] and plain["train"].get(k) == full["train"].get(k)
+    assert set(dumps["plain"]) == set(dumps["full"]) == {"infer_probabilities", "train_stats", "train_state"}
+    for name, a in dumps["plain"].items():
+        assert np.allclose(a, dumps["full"][name], rtol=1e-5, atol=1e-6), name

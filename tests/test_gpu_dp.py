@@ -98,7 +98,7 @@ def test_bench_two_ranks_like_the_driver(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", "2",
            "--steps", "2", "--warmup", "1", "--batch", "16", "--size", "96", "--network", "resnet18",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]      # --full: `params_equal`
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -9,11 +9,11 @@ export TMPDIR=/tmp
 OUT=$PWD/gpurun_out
 for cfg in "0 128" "4 128" "4 64"; do
   set -- $cfg
-  python3 bench.py --network efficientnet_b$1 --mode train --batch $2 --no-cpu-baseline 2> /dev/null | tail -1 > $OUT/${TAG}_bench_effnet_b$1_train_b$2.json
+  python3 bench.py --full --network efficientnet_b$1 --mode train --batch $2 --no-cpu-baseline 2> /dev/null | tail -1 > $OUT/${TAG}_bench_effnet_b$1_train_b$2.json
   echo "bench b$1 batch $2 done"
 done
 D=/tmp/kt_stats_$$
-rocprofv3 --kernel-trace --stats --output-format csv -d $D -- python3 bench.py --network efficientnet_b0 --mode train --batch 128 --no-cpu-baseline --steps 20 --warmup 5 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $D -- python3 bench.py --full --network efficientnet_b0 --mode train --batch 128 --no-cpu-baseline --steps 20 --warmup 5 > /dev/null 2>&1
 cp "$(find $D -name '*kernel_stats.csv' | head -1)" $OUT/${TAG}_effnet_b0_train_kernel_stats.csv
 for cfg in "efficientnet_b0 128 effnet_b0_train" "efficientnet_b4 128 effnet_b4_train" "resnet50 256 resnet50_train"; do
   set -- $cfg

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 mkdir -p gpurun_out
 export SPK_TUNE_CACHE=$PWD/gpurun_out/tune_${TAG}.txt
 [ -f gpurun_out/${TAG}_tune_cache.txt ] && cp gpurun_out/${TAG}_tune_cache.txt $SPK_TUNE_CACHE
-python3 bench.py --mode both --no-cpu-baseline --steps 3 --warmup 2 > /dev/null 2>&1
+python3 bench.py --full --mode both --no-cpu-baseline --steps 3 --warmup 2 > /dev/null 2>&1
 trace() {
   local NAME=$1 MODE=$2; shift 2
   rm -rf gpurun_out/prof_${TAG}_${NAME}

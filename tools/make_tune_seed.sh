@@ -9,7 +9,7 @@ mkdir -p gpurun_out
 export SPK_TUNE_SEED=0
 export SPK_TUNE_CACHE=$PWD/gpurun_out/tune_seed_raw.txt
 rm -f $SPK_TUNE_CACHE
-B="python3 bench.py --no-cpu-baseline --steps 3 --warmup 2"
+B="python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 2"
 $B > gpurun_out/seed_r50.json 2> gpurun_out/seed.err
 $B --network resnet18 > gpurun_out/seed_r18.json 2>> gpurun_out/seed.err
 $B --mode infer --network efficientnet_b0 --batch 128 > gpurun_out/seed_b0.json 2>> gpurun_out/seed.err

@@ -1,7 +1,9 @@
 """Table of the per-kernel SQ counters collected by tools/pmc_sq.sh (three rocprofv3 --pmc passes).
-Usage: python3 tools/pmc_sq_table.py <tag> [out.txt]   (reads gpurun_out/<tag>_pmc_sq_set{1,2,3}.csv)"""
+Usage: python3 tools/pmc_sq_table.py <tag> [out.txt]   (reads $OUT/<tag>_pmc_sq_set{1,2,3}.csv, OUT as in
+tools/pmc_sq.sh)"""
 import collections
 import csv
+import os
 import re
 import sys
 
@@ -23,7 +25,7 @@ def load(path):
 
 def main():
     tag = sys.argv[1]
-    base = f"gpurun_out/{tag}_pmc_sq_set"
+    base = f"{os.environ.get('OUT', 'bench_out')}/{tag}_pmc_sq_set"
     a_all, n_all = load(base + "1.csv")
     b_all, _ = load(base + "2.csv")
     c_all, _ = load(base + "3.csv")
