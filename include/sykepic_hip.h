@@ -45,10 +45,12 @@ extern "C" {
 #define SPK_OP_GAVGPOOL 3  /* AdaptiveAvgPool2d(1) + flatten */
 #define SPK_OP_LINEAR 4    /* Linear with bias, no activation (head) */
 #define SPK_OP_DROPOUT 5   /* Dropout(p) in the head */
-/* EfficientNet (torchvision MBConv; eval and, since round 3, training):
+/* EfficientNet and MobileNetV3 (torchvision MBConv / InvertedResidual; eval and training):
  *   DWCONV: depthwise Conv2d(C, C, k, stride, pad=(k-1)/2, groups=C, bias=False) + BatchNorm2d + activation
- *   SE:     SqueezeExcitation(C, squeeze = `k`): avgpool -> fc1 (1x1 conv, bias) -> SiLU -> fc2 -> Sigmoid -> x * s;
- *           `name` is the module prefix (name.fc1.weight ...), cin = cout = C. */
+ *   SE:     SqueezeExcitation(C, squeeze = `k`): avgpool -> fc1 (1x1 conv, bias) -> act1 -> fc2 -> act2 -> x * s;
+ *           `name` is the module prefix (name.fc1.weight ...), cin = cout = C.  `relu` names the gate pair:
+ *           0 = SiLU, Sigmoid (EfficientNet); SPK_ACT_RELU = ReLU, Hardsigmoid (MobileNetV3); any other value is
+ *           SPK_ERR_UNSUPPORTED at create. */
 #define SPK_OP_DWCONV 6
 #define SPK_OP_SE 7
 
@@ -56,6 +58,7 @@ extern "C" {
 #define SPK_ACT_NONE 0
 #define SPK_ACT_RELU 1
 #define SPK_ACT_SILU 2
+#define SPK_ACT_HSWISH 3  /* Hardswish x * clamp(x + 3, 0, 6) / 6 (MobileNetV3; CONV and DWCONV layers) */
 
 /* input layouts / dtypes of the image batch */
 #define SPK_LAYOUT_NCHW 0
@@ -159,7 +162,8 @@ int spk_model_set_infer_dtype(spk_model* m, int bf16);
  * split_weights = 1: every conv weight is carried as
  * hi + lo fp16 halves and both products are accumulated (2x MFMA work, weight
  * rounding error ~2^-22) — weight rounding is the dominant logit error at
- * 16-bit storage.  precise_residual: shortcut tensors keep their fp16
+ * 16-bit storage.  MobileNetV3 graphs (Hardswish / Hardsigmoid): split_weights = 3
+ * splits every conv, and split_weights = 5 returns SPK_ERR_UNSUPPORTED.  precise_residual: shortcut tensors keep their fp16
  * rounding remainder for the residual add (+2 B/element of shortcut traffic). */
 int spk_model_set_precision(spk_model* m, int split_weights, int precise_residual);
 /* Per-op choice of split weights: flags[i] != 0 carries conv op i (index into the
@@ -198,6 +202,8 @@ int spk_model_set_zero_sum(spk_model* m, int on);
  * fp16 forward of a representative device batch (as spk_forward_infer takes it) and records the activation
  * ranges; it must be called before the first fp8 forward and again after loading other weights.  3 mantissa
  * bits do not reach the 1e-3 probability tolerance of the reference: the fp16 path stays the parity mode. */
+/* A graph with a Hardswish layer or a ReLU / Hardsigmoid squeeze-excitation gate (MobileNetV3) has no fp8 mode:
+ * spk_model_set_fp8(m, 1) returns SPK_ERR_UNSUPPORTED. */
 int spk_model_set_fp8(spk_model* m, int on);
 int spk_model_calibrate_fp8(spk_model* m, const void* x_dev, int n, int h, int w, int layout, int dtype);
 /* Which MBConv blocks the fp8 mode covers (round 3).  Blocks are counted in graph order over those that qualify
@@ -392,7 +398,7 @@ int spk_op_conv1x1_dual(const void* x, const float* w1, const float* s1, const f
  * neighbour on the other side of w[i]; per row sum_k mu_k (out_k - w_k) is driven to ~0.  Synchronises the stream. */
 int spk_op_zero_sum_round(const float* w_dev, const float* mu_dev, float* out_dev, int64_t rows, int row_len,
                           int mu_period, void* stream);
-/* Depthwise Conv2d(C, C, k, stride, pad (k-1)/2, groups=C) + folded BatchNorm + activation (EfficientNet MBConv):
+/* Depthwise Conv2d(C, C, k, stride, pad (k-1)/2, groups=C) + folded BatchNorm + activation act (SPK_ACT_*; MBConv):
  * x [n,h,w,C] fp16 NHWC, w float32 [C][k*k], y [n,ho,wo,C] fp16; pool (optional) float32 [n][C] = per-image sums of
  * the outputs (squeeze-excitation numerator).  lds != 0: the LDS row-ring kernel, else the gather kernel. */
 int spk_op_dwconv(const void* x_dev, const float* w_dev, const float* bn_scale_dev, const float* bn_bias_dev, void* y_dev,

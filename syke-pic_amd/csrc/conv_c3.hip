@@ -196,10 +196,7 @@ __global__ __launch_bounds__(512, 2) void conv_c3_kernel(C3Args a, int m_tiles, 
       v[2 * i] += lo_f32<DT_F16>(rq[j][i]);
       v[2 * i + 1] += hi_f32<DT_F16>(rq[j][i]);
     }
-    if (a.relu == 2) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[i] = silu_f(v[i]);
-    }
+    act_apply<8, false, false>(v, a.relu);   // (ReLU: the floor of the clamp below)
     u32x4_t ov;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {

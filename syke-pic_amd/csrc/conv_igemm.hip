@@ -645,13 +645,7 @@ __global__ __launch_bounds__(WARPS_M* WARPS_N * 64, DMA == 3 ? 2 : 1) void conv_
             s2[j] += dz * (rw[j] - sc[j]) * bi[j];
           }
         }
-        if (a.relu == 1) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
-        } else if (a.relu == 2) {  // SiLU (EfficientNet)
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = silu_f(v[j]);
-        }
+        act_apply<8>(v, a.relu);
         u32x4_t ov;
 #pragma unroll
         for (int j = 0; j < 4; ++j) ov[j] = pack2<DT>(v[2 * j], v[2 * j + 1]);

@@ -247,10 +247,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void conv_pw_kernel(PwConvArgs a, in
           }
           if (PRE_RES && RESIDENT) rv[m][P] = __builtin_amdgcn_raw_buffer_load_b128(rr, yoff_next[m] + P * 64, 0, 0);
         }
-        if (a.relu == 2) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = silu_f(v[j]);
-        }
+        act_apply<8, false, false>(v, a.relu);   // (ReLU: the floor of the clamp below)
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = __builtin_amdgcn_fmed3f(v[j], relu_floor, out_max);
         u32x4_t ov;
@@ -310,10 +307,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void conv_pw_kernel(PwConvArgs a, in
             v[r] = __builtin_fmaf(az[m][2 * Pz][r], sc0[r], sh0[r]);
             v[4 + r] = __builtin_fmaf(az[m][2 * Pz + 1][r], sc1[r], sh1[r]);
           }
-          if (a.reluz == 2) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = silu_f(v[j]);
-          }
+          act_apply<8, false, false>(v, a.reluz);
 #pragma unroll
           for (int j = 0; j < 8; ++j) v[j] = __builtin_amdgcn_fmed3f(v[j], zfloor, out_max);
           u32x4_t ov;

@@ -243,10 +243,7 @@ __global__ __launch_bounds__(512, 2) void conv_pwr_kernel(PwConvArgs a, int m_ti
           v[2 * i + 1] += hi_f32<DT_F16>(q[i]);
         }
       }
-      if (a.relu == 2) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = silu_f(v[i]);
-      }
+      act_apply<8, false, false>(v, a.relu);   // (ReLU: the floor of the clamp below)
 #pragma unroll
       for (int i = 0; i < 8; ++i) v[i] = __builtin_amdgcn_fmed3f(v[i], relu_floor, 65504.f);
       u32x4_t ov;

@@ -166,13 +166,7 @@ __global__ __launch_bounds__(256) void dwconv_lds_kernel(DwArgs a) {
 #pragma unroll
       for (int u = 0; u < PX; ++u) {
         if (ox0 + u >= a.wo) continue;
-        if (a.act == 2) {   // uniform branch: one activation's instructions, not both + selects
-#pragma unroll
-          for (int j = 0; j < CPT; ++j) acc[u][j] = silu_f(acc[u][j]);
-        } else if (a.act == 1) {
-#pragma unroll
-          for (int j = 0; j < CPT; ++j) acc[u][j] = fmaxf(acc[u][j], 0.f);
-        }
+        act_apply<CPT>(acc[u], a.act);
 #pragma unroll
         for (int j = 0; j < CPT; ++j) pool[j] += acc[u][j];
         *(u32x4_t*)(yi + ((size_t)oy * a.wo + ox0 + u) * a.c_p * ELEM) = pack16B<ET>(acc[u], a.out_inv_scale);

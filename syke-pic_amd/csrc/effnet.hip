@@ -32,11 +32,6 @@ __device__ __forceinline__ u32x4_t pack8f(const float* f) {
   for (int j = 0; j < 4; ++j) o[j] = pack2<DT>(f[2 * j], f[2 * j + 1]);
   return o;
 }
-__device__ __forceinline__ float act_f(float v, int act) {
-  if (act == 1) return fmaxf(v, 0.f);
-  if (act == 2) return silu_f(v);
-  return v;
-}
 
 // [cout][taps][cin] fp32 -> [cout_p][taps][cin_p] 16-bit (hi, then lo halves), zero padded
 template <int DT>
@@ -167,13 +162,7 @@ __global__ __launch_bounds__(256) void stem3x3_kernel(const bf16_t* __restrict__
       for (int j = 0; j < 4; ++j) { acc[2 * j] = acc2[u][j][0]; acc[2 * j + 1] = acc2[u][j][1]; }
 #pragma unroll
       for (int j = 0; j < 4; ++j) { acc[j] = acc[j] * s0[j] + b0[j]; acc[4 + j] = acc[4 + j] * s1[j] + b1[j]; }
-      if (act == 2) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = silu_f(acc[j]);
-      } else if (act == 1) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = fmaxf(acc[j], 0.f);
-      }
+      act_apply<8>(acc, act);
       *(u32x4_t*)(y + (((size_t)img * ho + oy) * wo + ox0 + u) * c + c0) = pack8f<DT>(acc);
     }
   }
@@ -261,13 +250,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const bf16_t* __restrict__ 
 #pragma unroll
         for (int j = 0; j < 8; ++j)
           acc[u][j] = acc[u][j] * wl[((K * K) * 2 + (j >> 2)) * ncg * 4 + (j & 3)] + wl[((K * K + 1) * 2 + (j >> 2)) * ncg * 4 + (j & 3)];
-        if (act == 2) {   // uniform branch: one activation's instructions, not both + selects
-#pragma unroll
-          for (int j = 0; j < 8; ++j) acc[u][j] = silu_f(acc[u][j]);
-        } else if (act == 1) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) acc[u][j] = fmaxf(acc[u][j], 0.f);
-        }
+        act_apply<8>(acc[u], act);
 #pragma unroll
         for (int j = 0; j < 8; ++j) pool[j] += acc[u][j];
         *(u32x4_t*)(yi + ((size_t)oy * wo + ox0 + u) * c_p) = pack8f<DT>(acc[u]);
@@ -288,7 +271,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const bf16_t* __restrict__ 
   }
 }
 
-// excitation, part 1: hid = silu(W1 avg + b1).  Block (IPB images, 4 hidden units): all 256 threads stride the channels
+// excitation, part 1: hid = silu(W1 avg + b1) (GATE 1: relu).  Block (IPB images, 4 hidden units): all 256 threads stride the channels
 // (the pooled mean is summed from the depthwise kernel's chunk partials on the fly); every weight that is loaded serves
 // IPB images - with one image per block the two excitation kernels re-read the fc weights once per image through L2
 // (c 2688: 2 x 300 MB per layer) and ran 30-100 us; fixed-order shuffle + LDS reduction.  hid[img][sq].
@@ -297,7 +280,7 @@ constexpr int SE_IPB = 8;
 // else 0 = run-time count.  With a compile-time count the IPB x CH partial loads of a channel are all in flight
 // together; the run-time loop issued them one after the other, a chain of up to 32 L2 round trips per block (the kernel
 // took ~20 us whatever the layer size: 0.63 ms per EfficientNet-B4 forward).
-template <int CH>
+template <int CH, int GATE>
 __global__ __launch_bounds__(256) void se_fc1_kernel(const float* __restrict__ partial, int chunks_rt, float inv_hw,
                                                      const float* __restrict__ w1, const float* __restrict__ b1,
                                                      float* __restrict__ hid, int n, int c, int c_p, int sq) {
@@ -371,13 +354,14 @@ __global__ __launch_bounds__(256) void se_fc1_kernel(const float* __restrict__ p
     const int im = threadIdx.x >> 2, q = threadIdx.x & 3;
     if (im < nim && j0 + q < sq) {
       const float v = red[0][im][q] + red[1][im][q] + red[2][im][q] + red[3][im][q] + b1[j0 + q];
-      hid[(size_t)(img0 + im) * sq + j0 + q] = silu_f(v);
+      hid[(size_t)(img0 + im) * sq + j0 + q] = GATE ? fmaxf(v, 0.f) : silu_f(v);
     }
   }
 }
 
-// excitation, part 2: s = sigmoid(W2 hid + b2); thread = channel, fc2 weights transposed ([sq][c_p]: coalesced), each
+// excitation, part 2: s = sigmoid(W2 hid + b2) (GATE 1: hardsigmoid); thread = channel, fc2 weights transposed ([sq][c_p]: coalesced), each
 // weight serves the block's IPB images; scale[img][c_p] (0 on padding)
+template <int GATE>
 __global__ __launch_bounds__(256) void se_fc2_kernel(const float* __restrict__ hid, const float* __restrict__ w2t,
                                                      const float* __restrict__ b2, float* __restrict__ scale, int n,
                                                      int c, int c_p, int sq) {
@@ -417,7 +401,7 @@ __global__ __launch_bounds__(256) void se_fc2_kernel(const float* __restrict__ h
   }
 #pragma unroll
   for (int im = 0; im < SE_IPB; ++im)
-    if (im < nim) scale[(size_t)(img0 + im) * c_p + i] = i < c ? sigmoid_f(t[im]) : 0.f;
+    if (im < nim) scale[(size_t)(img0 + im) * c_p + i] = i < c ? (GATE ? hsigmoid_f(t[im]) : sigmoid_f(t[im])) : 0.f;
 }
 
 template <int DT>
@@ -517,24 +501,31 @@ int spk_launch_dwconv(const bf16_t* x, const float* w, const float* scale, const
 // squeeze-excitation gate on a depthwise output whose pool partials [n][chunks][c_p] the depthwise kernel wrote
 int spk_launch_se(const bf16_t* x, bf16_t* y, const float* partial, int chunks, float* scale, const float* w1,
                   const float* b1, const float* w2t, const float* b2, int n, int hw, int c, int c_p, int sq, int dt,
-                  hipStream_t s) {
-  if (dt != DT_F16) return -2;
+                  hipStream_t s, int gate) {
+  if (dt != DT_F16 || (gate != 0 && gate != 1)) return -2;
   float* hid = scale + (size_t)n * c_p;  // scratch behind the scales: [n][sq]
   const int ig = (n + SE_IPB - 1) / SE_IPB;
-#define SPK_FC1(CH) \
-  hipLaunchKernelGGL(se_fc1_kernel<CH>, dim3(ig, (sq + 3) / 4), dim3(256), 0, s, partial, chunks, 1.0f / (float)hw, w1, b1, \
-                     hid, n, c, c_p, sq)
-  switch (chunks) {
-    case 1: SPK_FC1(1); break;
-    case 2: SPK_FC1(2); break;
-    case 3: SPK_FC1(3); break;
-    case 4: SPK_FC1(4); break;
-    case 8: SPK_FC1(8); break;
-    default: SPK_FC1(0);
+#define SPK_FC1(CH, G) \
+  hipLaunchKernelGGL((se_fc1_kernel<CH, G>), dim3(ig, (sq + 3) / 4), dim3(256), 0, s, partial, chunks, 1.0f / (float)hw, w1, \
+                     b1, hid, n, c, c_p, sq)
+#define SPK_FC1_ALL(G)                 \
+  switch (chunks) {                    \
+    case 1: SPK_FC1(1, G); break;      \
+    case 2: SPK_FC1(2, G); break;      \
+    case 3: SPK_FC1(3, G); break;      \
+    case 4: SPK_FC1(4, G); break;      \
+    case 8: SPK_FC1(8, G); break;      \
+    default: SPK_FC1(0, G);            \
   }
+  if (gate) { SPK_FC1_ALL(1); } else { SPK_FC1_ALL(0); }
+#undef SPK_FC1_ALL
 #undef SPK_FC1
-  hipLaunchKernelGGL(se_fc2_kernel, dim3(ig, (c_p + 255) / 256), dim3(256), (size_t)sq * SE_IPB * 4, s, hid, w2t, b2, scale,
-                     n, c, c_p, sq);
+  if (gate)
+    hipLaunchKernelGGL(se_fc2_kernel<1>, dim3(ig, (c_p + 255) / 256), dim3(256), (size_t)sq * SE_IPB * 4, s, hid, w2t, b2,
+                       scale, n, c, c_p, sq);
+  else
+    hipLaunchKernelGGL(se_fc2_kernel<0>, dim3(ig, (c_p + 255) / 256), dim3(256), (size_t)sq * SE_IPB * 4, s, hid, w2t, b2,
+                       scale, n, c, c_p, sq);
   if (!y) return hipGetLastError() == hipSuccess ? 0 : -1;   // gates only
   const size_t per_img = (size_t)hw * (c_p / 8);
   if (per_img >= ((size_t)1 << 31)) return -2;

@@ -113,6 +113,8 @@ struct spk_model {
   std::vector<char> stale;     // per tensor: the last eval forward did not write it (a fused-away shortcut tensor)
   bool effnet = false;         // EfficientNet graph (widths that are not multiples of 64, depthwise / SE / SiLU ops): its
                                // TRAINING plan pads every activation tensor to a multiple of 64 channels (train_effnet.hip)
+  bool mobilenet = false;      // MobileNetV3 arithmetic (a Hardswish layer or a ReLU / Hardsigmoid squeeze-excitation gate):
+                               // an MBConv graph that the fp8 mode (SiLU-only kernels, pw_fp8.hip) does not cover
   bool plan_pad = false;       // the current activation plan is the channel-padded one
   size_t se_off = 0;           // arena offset of the squeeze-excitation scratch (partials + scales)
   bool dirty = true;

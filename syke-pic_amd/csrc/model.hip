@@ -126,12 +126,20 @@ extern "C" int spk_model_create_grouped(const spk_layer_desc* layers, const int3
         (L.d.cout % 8 || (L.d.cin > 4 && L.d.cin % 8))) {
       delete m; return fail(SPK_ERR_UNSUPPORTED, "channel counts must be multiples of 8");
     }
+    if ((L.d.kind == SPK_OP_CONV || L.d.kind == SPK_OP_DWCONV) &&
+        (L.d.relu < SPK_ACT_NONE || L.d.relu > SPK_ACT_HSWISH)) {
+      delete m; return fail(SPK_ERR_UNSUPPORTED, std::string("unknown activation code on ") + L.d.name);
+    }
+    if (L.d.relu == SPK_ACT_HSWISH) m->mobilenet = true;
     if (L.d.kind == SPK_OP_CONV) {
       const bool stem = (L.d.cin <= 4);
       const bool stem7 = stem && L.d.k == 7 && L.d.stride == 2 && L.d.pad == 3 && L.d.cout == 64;
       const bool stem3 = stem && L.d.k == 3 && L.d.stride == 2 && L.d.pad == 1;
       if (stem && !stem7 && !stem3) {
         delete m; return fail(SPK_ERR_UNSUPPORTED, "stems (Cin<=4): 7x7/2 pad 3 -> 64 or 3x3/2 pad 1");
+      }
+      if (stem7 && L.d.relu == SPK_ACT_HSWISH) {   // (conv_stem.hip applies ReLU or nothing)
+        delete m; return fail(SPK_ERR_UNSUPPORTED, "the 7x7/2 stem: ReLU or no activation");
       }
       if (stem) L.cin_p = 4;
       L.mode = stem7 ? CONV_MODE_STEM : (stem3 ? CONV_MODE_STEM3 : CONV_MODE_GENERIC);
@@ -140,7 +148,9 @@ extern "C" int spk_model_create_grouped(const spk_layer_desc* layers, const int3
         L.mode = CONV_MODE_GROUP;
         L.kpad = L.d.k * L.d.k * (L.d.cin / L.groups);
       }
-      if (stem3 || (!stem && L.cin_p != L.d.cin) || L.cout_p != L.d.cout || L.d.relu == SPK_ACT_SILU) m->effnet = true;
+      if (stem3 || (!stem && L.cin_p != L.d.cin) || L.cout_p != L.d.cout || L.d.relu == SPK_ACT_SILU ||
+          L.d.relu == SPK_ACT_HSWISH)
+        m->effnet = true;
     } else if (L.d.kind == SPK_OP_DWCONV) {
       if ((L.d.k != 3 && L.d.k != 5) || L.d.cin != L.d.cout || L.d.pad != (L.d.k - 1) / 2) {
         delete m; return fail(SPK_ERR_UNSUPPORTED, "depthwise conv: k 3 or 5, pad (k-1)/2");
@@ -150,6 +160,11 @@ extern "C" int spk_model_create_grouped(const spk_layer_desc* layers, const int3
       if (L.d.cin != L.d.cout || L.d.k < 1 || L.d.k > 1024) {
         delete m; return fail(SPK_ERR_UNSUPPORTED, "squeeze-excitation: cin == cout, 1 <= squeeze <= 1024");
       }
+      // the gate pair: 0 SiLU -> Sigmoid (EfficientNet), SPK_ACT_RELU: ReLU -> Hardsigmoid (MobileNetV3)
+      if (L.d.relu != SPK_ACT_NONE && L.d.relu != SPK_ACT_RELU) {
+        delete m; return fail(SPK_ERR_UNSUPPORTED, "squeeze-excitation: relu 0 (SiLU / Sigmoid) or 1 (ReLU / Hardsigmoid)");
+      }
+      if (L.d.relu == SPK_ACT_RELU) m->mobilenet = true;
       m->effnet = true;
     }
   }
@@ -294,8 +309,10 @@ extern "C" int spk_model_create_grouped(const spk_layer_desc* layers, const int3
     } else if (L.d.kind == SPK_OP_CONV) {
       L.wpack_off = wpack;
       wpack += (size_t)2 * L.cout_p * L.kpad;  // room for the hi + lo halves
+      // (Hardswish: the implicit GEMM only - the 1x1 / 3x3 kernels of the 64-channel-multiple shapes have no Hardswish
+      // epilogue; no MobileNetV3 conv has such a shape)
       L.pw_ok = L.mode == CONV_MODE_GENERIC && L.d.k == 1 && L.d.pad == 0 && L.cin_p == L.d.cin && L.cout_p == L.d.cout &&
-                L.d.cin % 64 == 0 && L.d.cout % 64 == 0 && L.kpad == L.d.cin;
+                L.d.cin % 64 == 0 && L.d.cout % 64 == 0 && L.kpad == L.d.cin && L.d.relu != SPK_ACT_HSWISH;
       if (L.pw_ok) {
         L.wpw_off = wpack;
         wpack += (size_t)2 * L.d.cout * L.d.cin;
@@ -306,7 +323,7 @@ extern "C" int spk_model_create_grouped(const spk_layer_desc* layers, const int3
       // the batch it was computed in.)
       L.c3_ok = L.mode == CONV_MODE_GENERIC && L.d.k == 3 && L.d.stride == 1 && L.d.pad == 1 && L.cin_p == L.d.cin &&
                 L.cout_p == L.d.cout && L.d.cin % 64 == 0 &&
-                (L.d.cout % 256 == 0 || (L.bn_head >= 0 && L.d.cout % 128 == 0));
+                (L.d.cout % 256 == 0 || (L.bn_head >= 0 && L.d.cout % 128 == 0)) && L.d.relu != SPK_ACT_HSWISH;
       // (the fragment-ordered 3x3 image also feeds the whole-bottleneck kernel: conv2 of such a block keeps one even where
       // conv_c3.hip itself has no configuration for its width)
       if (L.c3_ok || (L.bn_head >= 0 && L.d.k == 3)) {
@@ -535,6 +552,10 @@ extern "C" int spk_model_set_infer_dtype(spk_model* m, int bf16) {
 
 extern "C" int spk_model_set_precision(spk_model* m, int split_weights, int precise_residual) {
   if (!m) return fail(SPK_ERR_ARG, "null model");
+  // MobileNetV3: the single fp16 product of every conv does not hold the 1e-3 probability tolerance on a trained
+  // MobileNetV3-Large (5.3e-4 ... 1.05e-3 worst of 256 images, tests/test_gpu_mobilenet.py), zero-sum rounded or not
+  if (split_weights == 5 && m->mobilenet)
+    return fail(SPK_ERR_UNSUPPORTED, "the calibrated single-pass mode does not hold the tolerance on MobileNetV3 graphs");
   // (4 = mask: spk_model_set_split_ops; 5 = calibrated single pass, needs activation means)
   m->splitw = split_weights < 0 ? 0 : (split_weights == 5 ? 5 : (split_weights > 3 ? 3 : split_weights));
   if ((precise_residual != 0) != m->precise_res) {
@@ -587,7 +608,9 @@ static int layer_split(const spk_model* m, const Layer& L) {
   // SiLU blocks (tests/archive/diagnostics/effnet_prec.py); the weight rounding does not show beside it - goldens 1.2e-4 with
   // hi + lo on every 1x1 conv, 2.4e-4 without, fresh images the same medians and maxima either way
   // (tests/archive/diagnostics/effnet_calibrated.py) - while the lo products cost 7 % of the B4 forward (26.2 -> 28.2 k img/s).
-  if (m->splitw == 3 && m->effnet) return 0;
+  // MobileNetV3 (Hardswish / Hardsigmoid graphs): every conv.  On a trained MobileNetV3-Large the weight rounding does show:
+  // 7.1e-4 ... 1.06e-3 worst of 256 images without the lo products, 3.4e-4 ... 5.8e-4 with them (tests/test_gpu_mobilenet.py).
+  if (m->splitw == 3 && m->effnet && !m->mobilenet) return 0;
   if (m->splitw == 3) return L.trunk_writer || L.d.k != 3 || !L.inner3x3 ? 1 : 0;
   return m->splitw == 1 || L.trunk_writer ? 1 : 0;
 }
@@ -795,6 +818,8 @@ extern "C" int spk_model_set_fp8_blocks(spk_model* m, const unsigned char* flags
 extern "C" int spk_model_set_fp8(spk_model* m, int on) {
   if (!m) return fail(SPK_ERR_ARG, "null model");
   if (on && !m->effnet) return fail(SPK_ERR_UNSUPPORTED, "the fp8 mode covers the EfficientNet MBConv blocks only");
+  if (on && m->mobilenet)
+    return fail(SPK_ERR_UNSUPPORTED, "the fp8 mode covers SiLU MBConv blocks only (this graph has Hardswish / Hardsigmoid)");
   m->fp8 = on ? 1 : 0;
   return SPK_OK;
 }
@@ -1639,7 +1664,7 @@ int spk_run_layer_eval(spk_model* m, Layer& L, int nb) {
       const bool gate_only = m->fuse_se && L.gate_conv >= 0 && m->infer_dt == DT_F16 && !m->force_unfused && !m->precise_res;
       if (spk_launch_se(gate_only ? nullptr : (const bf16_t*)m->TI(L.d.src), gate_only ? nullptr : (bf16_t*)m->TI(L.d.dst),
                         partial, chunks, scale, m->P(L.p_w), m->P(L.p_b), m->dwpack + L.wpack_off, m->P(L.p_b2), nb,
-                        in.h * in.w, L.d.cin, in.c, L.d.k, m->infer_dt, m->stream))
+                        in.h * in.w, L.d.cin, in.c, L.d.k, m->infer_dt, m->stream, L.d.relu == SPK_ACT_RELU ? 1 : 0))
         return fail(SPK_ERR_UNSUPPORTED, std::string("squeeze-excitation launch failed (fp16 eval only) for ") + L.d.name);
       m->gate_h[m->half] = gate_only ? scale : nullptr;
       m->gate_stride_h[m->half] = in.c;

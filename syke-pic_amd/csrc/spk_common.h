@@ -49,6 +49,27 @@ typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
 // x -> -inf: exp overflows to +inf, rcp gives 0, the product is -0 like the division's.
 __device__ __forceinline__ float silu_f(float v) { return v * __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
 __device__ __forceinline__ float sigmoid_f(float v) { return __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
+// Hardsigmoid clamp(x + 3, 0, 6) / 6 and Hardswish x * Hardsigmoid(x) (MobileNetV3): v_add, v_med3, v_mul (, v_mul)
+__device__ __forceinline__ float hsigmoid_f(float v) { return __builtin_amdgcn_fmed3f(v + 3.f, 0.f, 6.f) * (1.f / 6.f); }
+__device__ __forceinline__ float hswish_f(float v) { return v * hsigmoid_f(v); }
+
+// The activation of a BatchNorm epilogue on N values: SPK_ACT_RELU 1, SPK_ACT_SILU 2, SPK_ACT_HSWISH 3, anything else
+// none.  `act` is uniform over the launch: one activation's instructions run, not all of them + selects.  RELU false:
+// the caller applies ReLU itself (a v_med3 with a floor of 0 that also saturates the fp16 store).  HSWISH false: a kernel
+// that no MobileNetV3 layer reaches (the 64-channel-multiple 1x1 / 3x3 kernels) keeps the code it had without Hardswish.
+template <int N, bool RELU = true, bool HSWISH = true>
+__device__ __forceinline__ void act_apply(float* v, int act) {
+  if (act == 2) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = silu_f(v[j]);
+  } else if (HSWISH && act == 3) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = hswish_f(v[j]);
+  } else if (RELU && act == 1) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = fmaxf(v[j], 0.f);
+  }
+}
 
 template <int DT> __device__ __forceinline__ float lo_f32(unsigned int u) {
   if (DT == DT_BF16) return __builtin_bit_cast(float, u << 16);
@@ -301,9 +322,10 @@ int spk_dw_chunks(int n, int hw, int c_p);
 int spk_launch_dwconv(const bf16_t* x, const float* w, const float* scale, const float* bias, bf16_t* y, float* partial,
                       int n, int h, int wid, int c_p, int ho, int wo, int k, int stride, int act, int dt, hipStream_t s);
 // y == nullptr: the gates only (scale[n][c_p]); the caller applies them elsewhere (fp8 mode: in the project conv)
+// gate: 0 fc1 -> SiLU -> fc2 -> Sigmoid (EfficientNet), 1 fc1 -> ReLU -> fc2 -> Hardsigmoid (MobileNetV3)
 int spk_launch_se(const bf16_t* x, bf16_t* y, const float* partial, int chunks, float* scale, const float* w1,
                   const float* b1, const float* w2t, const float* b2, int n, int hw, int c, int c_p, int sq, int dt,
-                  hipStream_t s);
+                  hipStream_t s, int gate = 0);
 int spk_launch_pack_weights(const float* w_krsc, bf16_t* out, int cout, int kh, int kw, int cin,
                             int mode, int dt, int splitw, hipStream_t s, float stem_wscale = 1.0f);
 // fp8 (e4m3) mode of the MBConv interior (pw_fp8.hip)

@@ -617,7 +617,7 @@ extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, in
         break;
       }
       case SPK_OP_SE: {
-        // s = sigmoid(fc2(silu(fc1(mean_hw(a))))), out = a * s; fp32 on the [n][C] vectors
+        // s = sigmoid(fc2(silu(fc1(mean_hw(a))))) (MobileNetV3: hardsigmoid, relu), out = a * s; fp32 on the [n][C] vectors
         const int C = o.c, Cl = L.d.cout, S = L.d.k, HW = o.h * o.w;
         float* pooled = (float*)((char*)t->arena + t->conv[i].se_off);
         float* u1 = pooled + (size_t)n * C;
@@ -628,7 +628,7 @@ extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, in
         if (squeezed != i)
           K_TRY(spk_launch_pool_rows(a, nullptr, scratch, n, HW, C, s), "se pool");
         K_TRY(spk_launch_se_gate_fwd(scratch, spk_se_chunks(HW), 1.f / (float)HW, pooled, m->P(L.p_w), m->P(L.p_b), m->P(L.p_w2), m->P(L.p_b2), u1, h1, gate, n, C, Cl, S,
-                                     s), "se gates");
+                                     s, L.d.relu == SPK_ACT_RELU ? 1 : 0), "se gates");
         K_TRY(spk_launch_se_scale(a, gate, (bf16_t*)m->T(L.d.dst), n, HW, C, s), "se scale");
         mark(m, PH_BN_FWD);
         break;
@@ -997,7 +997,7 @@ extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, in
         K_TRY(spk_launch_pool_rows(g, a, scratch, n, HW, C, s), "se dgate");
         const Param &w1 = m->params[L.p_w], &b1 = m->params[L.p_b], &w2 = m->params[L.p_w2], &b2 = m->params[L.p_b2];
         K_TRY(spk_launch_se_gate_bwd(scratch, spk_se_chunks(HW), dgate, gate, u1, m->P(L.p_w), m->P(L.p_w2), du1, dpool, dpool + (size_t)n * C, n, C, Cl,
-                                     S, s), "se gates bwd");
+                                     S, s, L.d.relu == SPK_ACT_RELU ? 1 : 0), "se gates bwd");
         hipStream_t ws = s;
         if (side_on && (w1.requires_grad || b1.requires_grad || w2.requires_grad || b2.requires_grad)) {
           ws = t->side;   // du2 / du1 are this layer's own: nothing on the main stream waits for the kernel

@@ -1,5 +1,5 @@
 // Training kernels of the EfficientNet graphs (torchvision MBConv: expand 1x1 -> depthwise k3/k5 -> squeeze-excitation
-// -> project 1x1, SiLU, stochastic depth on the residual branch).  The reference trains whatever torchvision model the
+// -> project 1x1, SiLU, stochastic depth on the residual branch; MobileNetV3: ReLU / Hardswish, a ReLU / Hardsigmoid gate).  The reference trains whatever torchvision model the
 // config names (sykepic/train/network.py:48-55, train.py:239-243); these stand in for the autograd pieces that the
 // ResNet kernels of train_kernels.hip do not cover: depthwise Conv2d forward / data gradient / weight gradient, the 3x3
 // RGB stem, BatchNorm with SiLU (and a per-image stochastic-depth factor) forward and backward, squeeze-excitation
@@ -16,7 +16,7 @@
 namespace {
 
 constexpr int DT = DT_BF16;
-constexpr int SPK_ACT_RELU = 1, SPK_ACT_SILU = 2;   // include/sykepic_hip.h
+constexpr int SPK_ACT_RELU = 1, SPK_ACT_SILU = 2, SPK_ACT_HSWISH = 3;   // include/sykepic_hip.h
 
 __device__ __forceinline__ void unpack8(const u32x4_t v, float* f) {
 #pragma unroll
@@ -33,13 +33,17 @@ __device__ __forceinline__ float bf16_round(float f) { return lo_f32<DT>(pack2<D
 // element): the BatchNorm + SiLU passes are as much VALU- as HBM-bound
 __device__ __forceinline__ float sigmoidf_(float z) { return __builtin_amdgcn_rcpf(1.f + __expf(-z)); }
 __device__ __forceinline__ float act_fwd(float z, int act) {
+  if (act == SPK_ACT_HSWISH) return hswish_f(z);
   return act == SPK_ACT_SILU ? z * sigmoidf_(z) : (act == SPK_ACT_RELU ? fmaxf(z, 0.f) : z);
 }
+// Hardswish' as torch takes it: 0 below -3, z / 3 + 1/2 on [-3, 3], 1 above
+__device__ __forceinline__ float hswish_grad(float z) { return z < -3.f ? 0.f : (z <= 3.f ? z * (1.f / 3.f) + 0.5f : 1.f); }
 __device__ __forceinline__ float act_grad(float z, int act) {
   if (act == SPK_ACT_SILU) {
     const float s = sigmoidf_(z);
     return s * (1.f + z * (1.f - s));
   }
+  if (act == SPK_ACT_HSWISH) return hswish_grad(z);
   return act == SPK_ACT_RELU ? (z > 0.f ? 1.f : 0.f) : 1.f;
 }
 
@@ -55,6 +59,7 @@ __device__ __forceinline__ f2_t act_grad2(f2_t z, int act) {
     return s * fma2(z, 1.f - s, (f2_t)1.f);
   }
   if (act == SPK_ACT_RELU) return f2_t{z[0] > 0.f ? 1.f : 0.f, z[1] > 0.f ? 1.f : 0.f};
+  if (act == SPK_ACT_HSWISH) return f2_t{hswish_grad(z[0]), hswish_grad(z[1])};
   return (f2_t)1.f;
 }
 
@@ -910,10 +915,12 @@ __device__ __forceinline__ void se_stage_rows(float* __restrict__ tile, const fl
   }
 }
 
-// Gates of the squeeze-excitation layer, fp32: u1 = W1 pooled + b1, h1 = silu(u1), gate = sigmoid(W2 h1 + b2).
+// Gates of the squeeze-excitation layer, fp32: u1 = W1 pooled + b1, h1 = silu(u1), gate = sigmoid(W2 h1 + b2); GATE 1
+// (MobileNetV3): h1 = relu(u1), gate = hardsigmoid(W2 h1 + b2).
 // Two launches, both (image x tile) grids: with one block per image the block walked both matrices by itself - a chain of
 // dependent L2 round trips, 60-150 us for the 2688-channel layers of B4 however little arithmetic that is.
 // fc1: block = (image, 16 hidden units); W1 [S][Cl] read with the lanes along Cl, 64 loads in flight per thread.
+template <int GATE>
 __global__ __launch_bounds__(256) void se_fc1_train_kernel(const float* __restrict__ part, int chunks, float scale,
                                                            float* __restrict__ pooled, const float* __restrict__ W1,
                                                            const float* __restrict__ b1, float* __restrict__ u1,
@@ -959,12 +966,13 @@ __global__ __launch_bounds__(256) void se_fc1_train_kernel(const float* __restri
     const int sidx = s0 + threadIdx.x;
     const float u = ((red[threadIdx.x] + red[16 + threadIdx.x]) + red[32 + threadIdx.x]) + red[48 + threadIdx.x] + b1[sidx];
     u1[(size_t)img * S + sidx] = u;
-    h1[(size_t)img * S + sidx] = u / (1.f + expf(-u));
+    h1[(size_t)img * S + sidx] = GATE ? fmaxf(u, 0.f) : u / (1.f + expf(-u));
   }
 }
 
 // fc2: block = (image, tile of R channels): the tile's rows of W2 [Cl][S] go through LDS (coalesced loads of whole rows,
 // then one row per thread; a thread walking its own row in global memory touches 64 cache lines per wave and load)
+template <int GATE>
 __global__ __launch_bounds__(256) void se_fc2_train_kernel(const float* __restrict__ h1, const float* __restrict__ W2,
                                                            const float* __restrict__ b2, float* __restrict__ gate, int C,
                                                            int Cl, int S, int R) {
@@ -978,13 +986,16 @@ __global__ __launch_bounds__(256) void se_fc2_train_kernel(const float* __restri
   for (int r = threadIdx.x; r < nrow; r += 256) {
     float acc = b2[c0 + r];
     for (int sidx = 0; sidx < S; ++sidx) acc += tile[r * ld + sidx] * shh[sidx];
-    gate[(size_t)img * C + c0 + r] = 1.f / (1.f + expf(-acc));
+    gate[(size_t)img * C + c0 + r] = GATE ? hsigmoid_f(acc) : 1.f / (1.f + expf(-acc));
   }
 }
 
 // Backward of the gate path.  in: pool_part[img][chunk][c], the per-chunk sums over HW of g*a.
-// bwd1: block = (image, tile of R channels): du2 = (sum of the chunks)*s(1-s) -> dgate, and the tile's share of W2^T du2:
+// bwd1: block = (image, tile of R channels): du2 = (sum of the chunks)*s(1-s) (GATE 1: * 1/6 where 0 < s < 1) -> dgate,
+// and the tile's share of W2^T du2:
 // part[img][tile][s] = sum_{c in tile} du2[c] W2[c][s] (lanes along s, the four waves take rows r, r+4, ...)
+// NQ: hidden units per lane, S <= 64 NQ
+template <int GATE, int NQ>
 __global__ __launch_bounds__(256) void se_bwd1_kernel(const float* __restrict__ pool_part, int chunks,
                                                       float* __restrict__ dgate, const float* __restrict__ gate,
                                                       const float* __restrict__ W2, float* __restrict__ part, int C, int Cl,
@@ -998,22 +1009,24 @@ __global__ __launch_bounds__(256) void se_bwd1_kernel(const float* __restrict__ 
     const float g = gate[(size_t)img * C + c0 + r];
     float dg = 0.f;   // sum over HW of g*a from the per-chunk sums of the pooling pass
     for (int k = 0; k < chunks; ++k) dg += pool_part[((size_t)img * chunks + k) * C + c0 + r];
-    const float v = dg * g * (1.f - g);
+    const float v = GATE ? (g > 0.f && g < 1.f ? dg * (1.f / 6.f) : 0.f) : dg * g * (1.f - g);
     dgate[(size_t)img * C + c0 + r] = v;
     s2[r] = v;
   }
   se_stage_rows(tile, W2 + (size_t)c0 * S, nrow, S, ld);
   __syncthreads();
-  float acc[3] = {0.f, 0.f, 0.f};   // hidden units lane, lane + 64, lane + 128 (S <= 192)
+  float acc[NQ];   // hidden units lane, lane + 64, ... (S <= 64 NQ)
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) acc[q] = 0.f;
   for (int r = wave; r < nrow; r += 4) {
     const float v = s2[r];
 #pragma unroll
-    for (int q = 0; q < 3; ++q)
+    for (int q = 0; q < NQ; ++q)
       if (lane + 64 * q < S) acc[q] += v * tile[r * ld + lane + 64 * q];
   }
   __syncthreads();
 #pragma unroll
-  for (int q = 0; q < 3; ++q)
+  for (int q = 0; q < NQ; ++q)
     if (lane + 64 * q < S) tile[wave * S + lane + 64 * q] = acc[q];
   __syncthreads();
   float* o = part + ((size_t)img * gridDim.y + blockIdx.y) * S;
@@ -1021,8 +1034,9 @@ __global__ __launch_bounds__(256) void se_bwd1_kernel(const float* __restrict__ 
     o[sidx] = ((tile[sidx] + tile[S + sidx]) + tile[2 * S + sidx]) + tile[3 * S + sidx];
 }
 
-// bwd2: block = (image, 1024 channels): du1[s] = silu'(u1[s]) * sum over the tiles of part (every block, block 0 stores
+// bwd2: block = (image, 1024 channels): du1[s] = silu'(u1[s]) (GATE 1: relu'(u1[s])) * sum over the tiles of part (every block, block 0 stores
 // it), dpool[c] = sum_s du1[s] W1[s][c] for the block's channels (lanes along Cl, 16 loads in flight)
+template <int GATE>
 __global__ __launch_bounds__(256) void se_bwd2_kernel(const float* __restrict__ part, int tiles, const float* __restrict__ u1,
                                                       const float* __restrict__ W1, float* __restrict__ du1,
                                                       float* __restrict__ dpool, int C, int Cl, int S) {
@@ -1031,8 +1045,14 @@ __global__ __launch_bounds__(256) void se_bwd2_kernel(const float* __restrict__ 
   for (int sidx = threadIdx.x; sidx < S; sidx += 256) {
     float acc = 0.f;
     for (int t = 0; t < tiles; ++t) acc += part[((size_t)img * tiles + t) * S + sidx];
-    const float z = u1[(size_t)img * S + sidx], sg = 1.f / (1.f + expf(-z));
-    const float v = acc * sg * (1.f + z * (1.f - sg));
+    const float z = u1[(size_t)img * S + sidx];
+    float v;
+    if (GATE) {
+      v = z > 0.f ? acc : 0.f;
+    } else {
+      const float sg = 1.f / (1.f + expf(-z));
+      v = acc * sg * (1.f + z * (1.f - sg));
+    }
     s1[sidx] = v;
     if (blockIdx.y == 0) du1[(size_t)img * S + sidx] = v;
   }
@@ -1059,7 +1079,10 @@ __global__ __launch_bounds__(256) void se_bwd2_kernel(const float* __restrict__ 
 // of A); 1: gW1 [S][Cl] from A = pooled, B = du1 (+ gb1 = column sums of B).  A block owns 64 channels x all S: the batch
 // is staged through LDS 32 images at a time, a thread keeps 4 channels x ceil(S/16) hidden units in registers (one
 // thread per output reading both operands from global memory took 85 us per layer).
-constexpr int SEW_KC = 32, SEW_SJ = 12;   // S <= 192
+// SJ: hidden units per thread, S <= 16 SJ (12: every EfficientNet).  EXACT: ceil(S / 16) == SJ, no per-unit predicate
+// (the gates of 193 ... 256 hidden units, MobileNetV3-Large's 240: one instantiation per SJ 13 ... 16)
+constexpr int SEW_KC = 32;
+template <int SEW_SJ, bool EXACT = false>
 __global__ __launch_bounds__(256) void se_wgrad_kernel(const float* __restrict__ du2, const float* __restrict__ h1,
                                                        const float* __restrict__ du1, const float* __restrict__ pooled,
                                                        float* __restrict__ gW1, float* __restrict__ gb1,
@@ -1076,7 +1099,7 @@ __global__ __launch_bounds__(256) void se_wgrad_kernel(const float* __restrict__
   float* As = sm;
   float* Bs = sm + SEW_KC * 64;
   const int c0 = blockIdx.x * 64, tc = threadIdx.x & 15, ts = threadIdx.x >> 4;
-  const int sj = (S + 15) >> 4;
+  const int sj = EXACT ? SEW_SJ : (S + 15) >> 4;
   float acc[4][SEW_SJ], sa[4] = {0.f, 0.f, 0.f, 0.f}, sb[SEW_SJ];
 #pragma unroll
   for (int j = 0; j < SEW_SJ; ++j) {
@@ -1431,34 +1454,60 @@ int spk_se_gate_tiles(int Cl, int S) {
 // pooled = scale * their sum is stored for the backward pass
 int spk_launch_se_gate_fwd(const float* part, int chunks, float scale, float* pooled, const float* W1, const float* b1,
                            const float* W2, const float* b2, float* u1, float* h1, float* gate, int n, int C, int Cl, int S,
-                           hipStream_t s) {
-  if (S > 192) return -1;
+                           hipStream_t s, int gate_kind) {
+  if (S > 256 || (gate_kind != 0 && gate_kind != 1)) return -1;
   const int R = se_tile_rows(S);
-  hipLaunchKernelGGL(se_fc1_train_kernel, dim3(n, (S + 15) / 16), dim3(256), (size_t)(Cl + 64) * 4, s, part, chunks, scale,
-                     pooled, W1, b1, u1, h1, C, Cl, S);
-  hipLaunchKernelGGL(se_fc2_train_kernel, dim3(n, spk_se_gate_tiles(Cl, S)), dim3(256),
-                     ((size_t)S + (size_t)R * (S | 1)) * 4, s, h1, W2, b2, gate, C, Cl, S, R);
+  const size_t lds1 = (size_t)(Cl + 64) * 4, lds2 = ((size_t)S + (size_t)R * (S | 1)) * 4;
+#define SE_FWD(G)                                                                                                       \
+  hipLaunchKernelGGL(se_fc1_train_kernel<G>, dim3(n, (S + 15) / 16), dim3(256), lds1, s, part, chunks, scale, pooled, W1, \
+                     b1, u1, h1, C, Cl, S);                                                                            \
+  hipLaunchKernelGGL(se_fc2_train_kernel<G>, dim3(n, spk_se_gate_tiles(Cl, S)), dim3(256), lds2, s, h1, W2, b2, gate, C, \
+                     Cl, S, R)
+  if (gate_kind) { SE_FWD(1); } else { SE_FWD(0); }
+#undef SE_FWD
   return LAUNCH_OK();
 }
 
 // part: [n][spk_se_gate_tiles(Cl, S)][S] floats of scratch
 int spk_launch_se_gate_bwd(const float* pool_part, int chunks, float* dgate, const float* gate, const float* u1,
                            const float* W1, const float* W2, float* du1, float* dpool, float* part, int n, int C, int Cl,
-                           int S, hipStream_t s) {
-  if (S > 192) return -1;
+                           int S, hipStream_t s, int gate_kind) {
+  if (S > 256 || (gate_kind != 0 && gate_kind != 1)) return -1;
   const int R = se_tile_rows(S), tiles = spk_se_gate_tiles(Cl, S);
-  hipLaunchKernelGGL(se_bwd1_kernel, dim3(n, tiles), dim3(256), ((size_t)R + (size_t)std::max(R, 4) * (S | 1)) * 4, s,
-                     pool_part, chunks, dgate, gate, W2, part, C, Cl, S, R);
-  hipLaunchKernelGGL(se_bwd2_kernel, dim3(n, (Cl + 1023) / 1024), dim3(256), (size_t)S * 4, s, part, tiles, u1, W1, du1,
-                     dpool, C, Cl, S);
+  const size_t lds1 = ((size_t)R + (size_t)std::max(R, 4) * (S | 1)) * 4;
+#define SE_BWD1(G, Q)                                                                                                  \
+  hipLaunchKernelGGL((se_bwd1_kernel<G, Q>), dim3(n, tiles), dim3(256), lds1, s, pool_part, chunks, dgate, gate, W2, part, \
+                     C, Cl, S, R)
+  if (gate_kind) {
+    if (S > 192) SE_BWD1(1, 4); else SE_BWD1(1, 3);
+    hipLaunchKernelGGL(se_bwd2_kernel<1>, dim3(n, (Cl + 1023) / 1024), dim3(256), (size_t)S * 4, s, part, tiles, u1, W1, du1,
+                       dpool, C, Cl, S);
+  } else {
+    if (S > 192) SE_BWD1(0, 4); else SE_BWD1(0, 3);
+    hipLaunchKernelGGL(se_bwd2_kernel<0>, dim3(n, (Cl + 1023) / 1024), dim3(256), (size_t)S * 4, s, part, tiles, u1, W1, du1,
+                       dpool, C, Cl, S);
+  }
+#undef SE_BWD1
   return LAUNCH_OK();
 }
 
 int spk_launch_se_wgrad(const float* du2, const float* h1, const float* du1, const float* pooled, float* gW1, float* gb1,
                         float* gW2, float* gb2, int n, int C, int Cl, int S, hipStream_t s) {
   if (!gW1 && !gb1 && !gW2 && !gb2) return 0;
-  if (S > 16 * SEW_SJ) return -1;
-  hipLaunchKernelGGL(se_wgrad_kernel, dim3((Cl + 63) / 64, 2), dim3(256), (size_t)SEW_KC * (64 + S) * sizeof(float), s, du2,
-                     h1, du1, pooled, gW1, gb1, gW2, gb2, n, C, Cl, S);
+  if (S > 256) return -1;
+  const size_t lds = (size_t)SEW_KC * (64 + S) * sizeof(float);
+#define SE_WGRAD(SJ, EX)                                                                                           \
+  hipLaunchKernelGGL((se_wgrad_kernel<SJ, EX>), dim3((Cl + 63) / 64, 2), dim3(256), lds, s, du2, h1, du1, pooled, gW1, gb1, \
+                     gW2, gb2, n, C, Cl, S)
+  if (S > 192) {
+    switch ((S + 15) >> 4) {
+      case 13: SE_WGRAD(13, true); break;
+      case 14: SE_WGRAD(14, true); break;
+      case 15: SE_WGRAD(15, true); break;
+      default: SE_WGRAD(16, true);
+    }
+  } else
+    SE_WGRAD(12, false);
+#undef SE_WGRAD
   return LAUNCH_OK();
 }

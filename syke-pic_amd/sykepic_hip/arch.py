@@ -15,7 +15,9 @@ avgpool,fc``).  The graph is consumed by the C-ABI library
 from dataclasses import dataclass, field
 
 OP_CONV, OP_MAXPOOL, OP_GAVGPOOL, OP_LINEAR, OP_DROPOUT, OP_DWCONV, OP_SE = 1, 2, 3, 4, 5, 6, 7
-ACT_NONE, ACT_RELU, ACT_SILU = 0, 1, 2   # Op.relu (bool for the ResNets: True == ACT_RELU)
+ACT_NONE, ACT_RELU, ACT_SILU, ACT_HSWISH = 0, 1, 2, 3   # Op.relu (bool for the ResNets: True == ACT_RELU)
+# On an OP_SE op, Op.relu names the gate pair: ACT_NONE = SiLU, Sigmoid (EfficientNet); ACT_RELU = ReLU, Hardsigmoid
+# (MobileNetV3)
 
 _RESNETS = {
     "resnet18": ("basic", (2, 2, 2, 2)),
@@ -57,14 +59,46 @@ _MBCONV = ((1, 3, 1, 32, 16, 1), (6, 3, 2, 16, 24, 2), (6, 5, 2, 24, 40, 2), (6,
            (6, 5, 1, 80, 112, 3), (6, 5, 2, 112, 192, 4), (6, 3, 1, 192, 320, 1))
 
 
-# BatchNorm2d(eps, momentum) of the backbone: torch's defaults, except torchvision's efficientnet_b5..b7
+# torchvision mobilenet_v3_large / _small (width_mult 1.0, no dilation, full tail; Howard et al. 2019, tables 1-2):
+# one row per InvertedResidual (input channels, kernel, expanded channels, output channels, SE, Hardswish, stride)
+# and the width of the last 1x1 conv (6 x the last block's output)
+_MOBILENETS = {
+    "mobilenet_v3_large": ((
+        (16, 3, 16, 16, False, False, 1), (16, 3, 64, 24, False, False, 2), (24, 3, 72, 24, False, False, 1),
+        (24, 5, 72, 40, True, False, 2), (40, 5, 120, 40, True, False, 1), (40, 5, 120, 40, True, False, 1),
+        (40, 3, 240, 80, False, True, 2), (80, 3, 200, 80, False, True, 1), (80, 3, 184, 80, False, True, 1),
+        (80, 3, 184, 80, False, True, 1), (80, 3, 480, 112, True, True, 1), (112, 3, 672, 112, True, True, 1),
+        (112, 5, 672, 160, True, True, 2), (160, 5, 960, 160, True, True, 1), (160, 5, 960, 160, True, True, 1)), 960),
+    "mobilenet_v3_small": ((
+        (16, 3, 16, 16, True, False, 2), (16, 3, 72, 24, False, False, 2), (24, 3, 88, 24, False, False, 1),
+        (24, 5, 96, 40, True, True, 2), (40, 5, 240, 40, True, True, 1), (40, 5, 240, 40, True, True, 1),
+        (40, 5, 120, 48, True, True, 1), (48, 5, 144, 48, True, True, 1), (48, 5, 288, 96, True, True, 2),
+        (96, 5, 576, 96, True, True, 1), (96, 5, 576, 96, True, True, 1)), 576),
+}
+
+
+# BatchNorm2d(eps, momentum) of the backbone: torch's defaults, except torchvision's efficientnet_b5..b7 and MobileNetV3
 # (norm_layer = partial(nn.BatchNorm2d, eps=0.001, momentum=0.01))
 def bn_params(network):
-    return (1e-3, 0.01) if network in ("efficientnet_b5", "efficientnet_b6", "efficientnet_b7") else (1e-5, 0.1)
+    if network in ("efficientnet_b5", "efficientnet_b6", "efficientnet_b7") or network in _MOBILENETS:
+        return (1e-3, 0.01)
+    return (1e-5, 0.1)
 
 
 def supported_networks():
-    return sorted(_RESNETS) + sorted(_EFFNETS)
+    return sorted(_RESNETS) + sorted(_EFFNETS) + sorted(_MOBILENETS)
+
+
+def calibrated_mode_ok(g):
+    """Whether the library runs the calibrated single-pass mode (split_weights 5) on graph `g`: not on MobileNetV3
+    graphs (a Hardswish layer or a ReLU / Hardsigmoid squeeze-excitation gate), where one fp16 product per conv does not
+    hold the 1e-3 probability tolerance (spk_model_set_precision returns SPK_ERR_UNSUPPORTED)."""
+    for op in g.ops:
+        if op.kind in (OP_CONV, OP_DWCONV) and int(op.relu) == ACT_HSWISH:
+            return False
+        if op.kind == OP_SE and int(op.relu) == ACT_RELU:
+            return False
+    return True
 
 
 def _make_divisible(v, divisor=8):
@@ -182,11 +216,58 @@ def _build_efficientnet(network, num_classes, head, dropout, in_chans, stochasti
     return g
 
 
+def _build_mobilenet_v3(network, num_classes, head, dropout, in_chans):
+    """torchvision MobileNetV3: children [features, avgpool, classifier]; the reference keeps [features, avgpool] as
+    ``base`` and reads ``in_features`` (960 / 576) off ``classifier[0]`` (network.py:50-55).  An InvertedResidual is an
+    MBConv block with ReLU or Hardswish, an optional SE gate (ReLU / Hardsigmoid) and no stochastic depth.  state_dict
+    keys: base.0.<i>... for features[i]."""
+    rows, last = _MOBILENETS[network]
+    g = Graph(network, in_chans, num_classes, last, n_base_children=2)
+    ops = g.ops
+    t = [0]
+
+    def new_t():
+        t[0] += 1
+        return t[0]
+
+    cur = new_t()
+    ops.append(Op(OP_CONV, "base.0.0.0", "base.0.0.1", in_chans, 16, 3, 2, 1, ACT_HSWISH, 0, cur, -1, 0))
+    for i, (cin, k, exp, cout, se, hs, stride) in enumerate(rows):
+        pre = f"base.0.{i + 1}.block"
+        act = ACT_HSWISH if hs else ACT_RELU
+        x_in, j = cur, 0
+        if exp != cin:
+            d = new_t()
+            ops.append(Op(OP_CONV, f"{pre}.{j}.0", f"{pre}.{j}.1", cin, exp, 1, 1, 0, act, cur, d, -1, 0))
+            cur, j = d, j + 1
+        d = new_t()
+        ops.append(Op(OP_DWCONV, f"{pre}.{j}.0", f"{pre}.{j}.1", exp, exp, k, stride, (k - 1) // 2, act, cur, d, -1, 0))
+        cur, j = d, j + 1
+        if se:
+            d = new_t()
+            ops.append(Op(OP_SE, f"{pre}.{j}", "", exp, exp, _make_divisible(exp // 4), 1, 0, ACT_RELU, cur, d, -1, 0))
+            cur, j = d, j + 1
+        d = new_t()
+        res = x_in if (stride == 1 and cin == cout) else -1
+        ops.append(Op(OP_CONV, f"{pre}.{j}.0", f"{pre}.{j}.1", exp, cout, 1, 1, 0, ACT_NONE, cur, d, res, 0, res >= 0))
+        cur = d
+    n = len(rows) + 1
+    d = new_t()
+    ops.append(Op(OP_CONV, f"base.0.{n}.0", f"base.0.{n}.1", rows[-1][3], last, 1, 1, 0, ACT_HSWISH, cur, d, -1, 0))
+    cur = d
+    d = new_t()
+    ops.append(Op(OP_GAVGPOOL, "", "", last, last, 0, 1, 0, False, cur, d, -1, 1))
+    _add_head(g, ops, new_t, d, last, num_classes, head, dropout)
+    return g
+
+
 def build_graph(network, num_classes, head=(256, 128), dropout=(), in_chans=3, stochastic_depth=0.2):
-    """Mirror of ``TorchVisionNet.__init__`` (ResNet and EfficientNet-B0..B4 families).  ``stochastic_depth`` is
+    """Mirror of ``TorchVisionNet.__init__`` (ResNet, EfficientNet and MobileNetV3 families).  ``stochastic_depth`` is
     torchvision's ``stochastic_depth_prob`` (0.2 for every EfficientNet variant; 0 turns the train-mode row dropping off)."""
     if network in _EFFNETS:
         return _build_efficientnet(network, num_classes, list(head), list(dropout), in_chans, stochastic_depth)
+    if network in _MOBILENETS:
+        return _build_mobilenet_v3(network, num_classes, list(head), list(dropout), in_chans)
     if network not in _RESNETS:
         raise ValueError(
             f"network {network!r} has no MI355X path yet; supported: {supported_networks()}"
@@ -295,7 +376,7 @@ def param_specs(g):
             return 0
         return 1 if ".downsample." in op.name else 0
 
-    if g.network in _EFFNETS:   # graph order == module order == state_dict order
+    if g.network in _EFFNETS or g.network in _MOBILENETS:   # graph order == module order == state_dict order
         for op in g.ops:
             if op.kind in (OP_CONV, OP_DWCONV):
                 cin1 = 1 if op.kind == OP_DWCONV else op.cin
@@ -365,10 +446,10 @@ _RESNET_CHILDREN = {"conv1": 0, "bn1": 1, "layer1": 4, "layer2": 5, "layer3": 6,
 def backbone_key(network, key):
     """state_dict key of a torchvision backbone checkpoint (``resnet50-*.pth``: ``conv1.weight``,
     ``layer1.0.conv1.weight``, ``fc.weight`` ...; EfficientNet: ``features.1.0.block...``,
-    ``classifier.1.weight``; ResNeXt / Wide ResNet: the ResNet layout) -> key of the same tensor under ``TorchVisionNet.base`` (``base.<child>...``),
+    ``classifier.1.weight``; MobileNetV3: ``features.*``, ``classifier.0/3.*``; ResNeXt / Wide ResNet: the ResNet layout) -> key of the same tensor under ``TorchVisionNet.base`` (``base.<child>...``),
     or None for the classifier the reference drops (network.py:49-55)."""
     first, _, rest = key.partition(".")
-    if network in _EFFNETS:
+    if network in _EFFNETS or network in _MOBILENETS:
         return f"base.0.{rest}" if first == "features" else None
     if first in _RESNET_CHILDREN:
         return f"base.{_RESNET_CHILDREN[first]}.{rest}"

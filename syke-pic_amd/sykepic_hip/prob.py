@@ -584,6 +584,11 @@ def calibrate_call(args):
     classify (raw samples or PNG images, chosen as for `prob`) and store them as `act_means.pth` beside
     `best_state.pth`.  From then on `sykepic prob -m <dir>` runs the calibrated single-pass mode."""
     from . import files, ifcb, pngio
+    cfg = ConfigParser()
+    cfg.read(Path(args.model) / "config.ini")
+    network = cfg.get("model", "network", fallback="")
+    if network and not arch.calibrated_mode_ok(arch.build_graph(network, 2)):
+        raise ValueError(f"{network} has no calibrated single-pass mode: there are no activation means to measure")
     keep = os.environ.get("SYKEPIC_CALIBRATED")
     os.environ["SYKEPIC_CALIBRATED"] = "0"      # measure with the weights alone, whatever file is already there
     try:

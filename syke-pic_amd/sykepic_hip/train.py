@@ -23,7 +23,7 @@ from pathlib import Path
 
 import torch
 
-from . import data, schedule
+from . import arch, data, schedule
 from .config import Settings, get_network, get_transforms
 from . import dp
 from .dp import GradSync
@@ -150,6 +150,8 @@ def main(args):
         # best_state.pth: `sykepic prob` then runs the calibrated single-pass mode (prob.use_act_means)
         from . import prob
         try:
+            if not arch.calibrated_mode_ok(net.graph):   # (MobileNetV3: `prob` runs the default mode, nothing to store)
+                raise RuntimeError(f"{mo.network} has no calibrated single-pass mode")
             n_cal = prob.calibrate_model(net, model_data.val_loader, 2048)
             if n_cal:
                 prob.save_act_means(net, model_dir, n_cal)
