@@ -390,10 +390,13 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_bneck_kernel(BneckArgs a) {
 
   // =====================================================================================================================
   // phase 3: out = ReLU(BN3(W3 . y2) + x) in 8 half passes: in half pass hp a wave computes the 32 couts
-  // (hp / 2) 64 WN + 64 wn + 32 (hp % 2) .. + 31 of its position tiles.  Everything a half pass reads from memory is
-  // requested one half pass earlier, BEFORE the previous epilogue's stores (vmcnt retires in issue order: a load waited for
-  // behind stores sits through their write latency): its weight fragments when the previous K loop has consumed the
-  // register set, its shortcut values into the second of two register sets.
+  // (hp / 2) 64 WN + 64 wn + 32 (hp % 2) .. + 31 of its position tiles - the two halves of a position's 128-byte line of
+  // 64 couts.  The even half pass keeps its packed outputs in registers and the odd one stores both, back to back, so
+  // that every line leaves the wave whole (stored half by half, a pass apart, the lines reached HBM as partial writes:
+  // 1.33 x the output bytes).  Everything a half pass reads from memory is requested one half pass earlier, BEFORE any
+  // store that follows (vmcnt retires in issue order: a load waited for behind stores sits through their write
+  // latency): its weight fragments when the previous K loop has consumed the register set, its shortcut values when
+  // the previous epilogue has consumed theirs (one register set: the even half pass has no stores to wait behind).
   // =====================================================================================================================
   {
     constexpr int KS3 = CM / 32;
@@ -413,7 +416,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_bneck_kernel(BneckArgs a) {
     // out of phase (MI355X_MICROARCH.md, "Two waves per SIMD", items 4 and 9).
     if (NW == 8 && wave >= 4 && !(a.flags & 1)) __builtin_amdgcn_s_setprio(1);
     u32x4_t wq[KS3][2];      // the half pass's weight fragments: K step x tile of the pair
-    u32x4_t rq[2][MTW];      // shortcut values: this half pass's and the next one's
+    u32x4_t rq[MTW];         // the half pass's shortcut values
+    u32x4_t ovk[MTW];        // the even half pass's packed outputs, stored with the odd one's
     auto col = [&](int hp) { return (hp >> 1) * 64 * WN + 32 * (hp & 1); };   // first cout of the half pass (this wave: + 64 wn)
     auto load_w = [&](int hp) {
 #pragma unroll
@@ -422,15 +426,16 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_bneck_kernel(BneckArgs a) {
         for (int t = 0; t < 2; ++t)
           wq[ks][t] = __builtin_amdgcn_raw_buffer_load_b128(rw3, w_lane + t * 1024, (ks * (C4 / 32) + (hp >> 1) * 2 * WN + (hp & 1)) * 2048, 0);
     };
-    auto load_r = [&](u32x4_t (&d)[MTW], int hp) {
+    auto load_r = [&](int hp) {
 #pragma unroll
-      for (int j = 0; j < MTW; ++j) d[j] = __builtin_amdgcn_raw_buffer_load_b128(rxr, yoff[j], col(hp) * 2, 0);
+      for (int j = 0; j < MTW; ++j) rq[j] = __builtin_amdgcn_raw_buffer_load_b128(rxr, yoff[j], col(hp) * 2, 0);
     };
     load_w(0);
-    load_r(rq[0], 0);
+    load_r(0);
     lds_u8_t sb0 = (lds_u8_t)win + plane_lane, sb1 = sb0 + (KS3 > 4 ? 16 * PLANE : 0);
     asm volatile("" : "+v"(sb0), "+v"(sb1));
-    auto half_pass = [&](int hp, const u32x4_t (&rcur)[MTW], u32x4_t (&rnext)[MTW]) {
+    // K loop + epilogue of half pass hp into ov; the next half pass's weight fragments are requested between the two
+    auto half_pass = [&](int hp, u32x4_t (&ov)[MTW]) {
       f32x4_t acc[MTW][2];
 #pragma unroll
       for (int j = 0; j < MTW; ++j) acc[j][0] = acc[j][1] = f32x4_t{0.f, 0.f, 0.f, 0.f};
@@ -455,11 +460,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_bneck_kernel(BneckArgs a) {
         acc[j][1] = mfma16<DT_F16>(wq[ks][1], fr[u % D3], acc[j][1]);
         __builtin_amdgcn_sched_barrier(0);
       }
-      // the next half pass's operands, in front of this one's stores
-      if (hp + 1 < 8) {
-        load_w(hp + 1);
-        load_r(rnext, hp + 1);
-      }
+      if (hp + 1 < 8) load_w(hp + 1);   // (the register set the K loop above has consumed)
       if (hp == 0) stamp(7);
       __builtin_amdgcn_sched_barrier(0);
       const int co = col(hp);
@@ -479,24 +480,35 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_bneck_kernel(BneckArgs a) {
                                           __builtin_shufflevector(sh1, sh1, 0, 1));
         v2[3] = __builtin_elementwise_fma(__builtin_shufflevector(acc[j][1], acc[j][1], 2, 3), __builtin_shufflevector(sc1, sc1, 2, 3),
                                           __builtin_shufflevector(sh1, sh1, 2, 3));
-        const u32x4_t q = rcur[j];
+        const u32x4_t q = rq[j];
         const unsigned q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
         v2[0] += __builtin_convertvector(__builtin_bit_cast(f16x2_t, q0), f32x2_t);
         v2[1] += __builtin_convertvector(__builtin_bit_cast(f16x2_t, q1), f32x2_t);
         v2[2] += __builtin_convertvector(__builtin_bit_cast(f16x2_t, q2), f32x2_t);
         v2[3] += __builtin_convertvector(__builtin_bit_cast(f16x2_t, q3), f32x2_t);
-        u32x4_t ov;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-          ov[i] = pack2h(__builtin_amdgcn_fmed3f(v2[i][0], 0.f, 65504.f), __builtin_amdgcn_fmed3f(v2[i][1], 0.f, 65504.f));
-        // (the column offset in the VECTOR operand, never an SGPR soffset on a store: conv_pw.hip's store-data hazard note)
-        __builtin_amdgcn_raw_buffer_store_b128(ov, ry, yoff[j] + (unsigned)(co * 2), 0, 0);
+          ov[j][i] = pack2h(__builtin_amdgcn_fmed3f(v2[i][0], 0.f, 65504.f), __builtin_amdgcn_fmed3f(v2[i][1], 0.f, 65504.f));
       }
+      // the next half pass's shortcut values, into the registers just consumed - in front of any store
+      if (hp + 1 < 8) load_r(hp + 1);
       if (hp == 0) stamp(6);
+      __builtin_amdgcn_sched_barrier(0);
     };
+    // (unrolled: as a loop, hipcc keeps more than the 256 registers live across its back edge and spills)
+#pragma unroll
     for (int hp = 0; hp < 8; hp += 2) {
-      half_pass(hp, rq[0], rq[1]);
-      half_pass(hp + 1, rq[1], rq[0]);
+      half_pass(hp, ovk);
+      u32x4_t ov[MTW];
+      half_pass(hp + 1, ov);
+      const int co = col(hp);
+      // both halves of each line, back to back (the column offset in the VECTOR operand, never an SGPR soffset on a
+      // store: conv_pw.hip's store-data hazard note)
+#pragma unroll
+      for (int j = 0; j < MTW; ++j) {
+        __builtin_amdgcn_raw_buffer_store_b128(ovk[j], ry, yoff[j] + (unsigned)(co * 2), 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(ov[j], ry, yoff[j] + (unsigned)((co + 32) * 2), 0, 0);
+      }
     }
     stamp(5);
   }
