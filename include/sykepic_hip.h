@@ -404,6 +404,69 @@ int spk_op_zero_sum_round(const float* w_dev, const float* mu_dev, float* out_de
 int spk_op_dwconv(const void* x_dev, const float* w_dev, const float* bn_scale_dev, const float* bn_bias_dev, void* y_dev,
                   float* pool_dev, int n, int h, int w, int channels, int k, int stride, int act, int lds, void* hip_stream);
 
+/* --- Test hooks: single operators of the MBConv training step (csrc/train_effnet.hip) ---
+ * What `out = net(x)` (train mode) and `loss.backward()` run for ONE layer of an EfficientNet-B0...B7 / MobileNetV3
+ * (sykepic/train/train.py:240,242): the launches spk_train_forward_backward makes for it, chosen by the functions the
+ * step itself calls.  Layout as in the step: activations and gradients bf16 NHWC device buffers of C channels, C the
+ * padded channel count (a multiple of 64); c_log <= C the layer's own count, pad channels hold zeros; parameters and
+ * their gradients float32, c_log entries.  A NULL output pointer skips that part.  Synchronous.
+ *
+ * Depthwise Conv2d(c_log, c_log, k, stride, pad, groups = c_log), k 3 or 5, stride 1 or 2: x [n,h,w,C], dy [n,ho,wo,C],
+ * w float32 [c_log][k*k] (packed inside the call to the tap-major window and its flipped copy, bf16-rounded, as the step
+ * packs it).  y: the raw output [n,ho,wo,C]; dx [n,h,w,C] (= or, accumulate != 0, +=) the data gradient; dw float32
+ * [c_log][k*k].  The kernels are the step's: pad (k-1)/2 runs the eval path's kernel in bf16 (forward; stride-1 dx that is
+ * not accumulated, on the flipped window) and dw_dgrad_px_kernel, any other pad dw_fwd_kernel / dw_dgrad_kernel. */
+int spk_op_dw_train(const void* x_dev, const void* dy_dev, const float* w_dev, void* y_dev, void* dx_dev, float* dw_dev,
+                    int accumulate, int n, int h, int w, int channels, int c_log, int k, int stride, int pad,
+                    void* hip_stream);
+/* BatchNorm2d (train mode) + activation (SPK_ACT_*) forward on raw [n*hw][C]: column sums -> finalize -> apply.
+ * out = act(raw * scale + shift) * rowscale[image] + res; res (bf16 [n*hw][C]) and rowscale (float32 [n], the stochastic
+ * depth factor) are optional.  pool_part != NULL (float32 [n][chunks][C], chunks = 1 / 4 / 16 for hw < 196 / < 3136 /
+ * more; res and rowscale must be NULL): the form that also leaves the per-chunk channel sums of `out` for the
+ * squeeze-excitation layer behind.  st: float32 [4][C] = batch mean, invstd, scale, shift (zeros in the pad channels);
+ * running_mean / running_var [c_log] are updated in place (unbiased variance). */
+int spk_op_bna_forward(const void* raw_dev, const float* gamma_dev, const float* beta_dev, float* running_mean_dev,
+                       float* running_var_dev, const void* res_dev, const float* rowscale_dev, void* out_dev,
+                       float* pool_part_dev, float* st_dev, int n, int hw, int channels, int c_log, int act, float eps,
+                       float momentum, void* hip_stream);
+/* Its backward: g = gradient of `out`, st as spk_op_bna_forward left it.  dy [n*hw][C] = gradient of raw, dgamma /
+ * dbeta [c_log] (either may be NULL), g_res (optional) receives (or, res_accumulate != 0, adds) the shortcut's gradient. */
+int spk_op_bna_backward(const void* g_dev, const void* raw_dev, const float* st_dev, const float* gamma_dev,
+                        const float* rowscale_dev, void* dy_dev, float* dgamma_dev, float* dbeta_dev, void* g_res_dev,
+                        int res_accumulate, int n, int hw, int channels, int c_log, int act, void* hip_stream);
+/* Squeeze-excitation forward: out = a * gate, gate = sigmoid(W2 silu(W1 mean_hw(a) + b1) + b2) (gate_kind 1: Hardsigmoid /
+ * ReLU).  a, out [n][hw][C]; W1 [S][c_log], b1 [S], W2 [c_log][S], b2 [c_log], S <= 256 (else SPK_ERR_UNSUPPORTED).
+ * Saved for the backward pass, float32: pooled [n][C], u1 [n][S] (W1 pooled + b1), h1 [n][S], gate [n][C].
+ * pool_part (optional): the channel sums spk_op_bna_forward left, used instead of pooling `a`; out == NULL: gates only. */
+int spk_op_se_train_forward(const void* a_dev, const float* pool_part_dev, const float* w1_dev, const float* b1_dev,
+                            const float* w2_dev, const float* b2_dev, float* pooled_dev, float* u1_dev, float* h1_dev,
+                            float* gate_dev, void* out_dev, int n, int hw, int channels, int c_log, int s_hidden,
+                            int gate_kind, void* hip_stream);
+/* Its backward: da [n][hw][C] from g (gradient of out), a and the saved vectors; gW1 [S][c_log], gb1 [S], gW2 [c_log][S],
+ * gb2 [c_log] (each optional).  du2 [n][C] / du1 [n][S] receive the gradients of the two pre-activations; pool_part
+ * (optional) the per-chunk sums over hw of g * a.  g == NULL: only the parameter-gradient kernel, on the caller's du2 /
+ * du1 / h1 / pooled. */
+int spk_op_se_train_backward(const void* g_dev, const void* a_dev, const float* gate_dev, const float* u1_dev,
+                             const float* h1_dev, const float* pooled_dev, const float* w1_dev, const float* w2_dev,
+                             float* du2_dev, float* du1_dev, float* pool_part_dev, void* da_dev, float* gw1_dev,
+                             float* gb1_dev, float* gw2_dev, float* gb2_dev, int n, int hw, int channels, int c_log,
+                             int s_hidden, int gate_kind, void* hip_stream);
+/* The 3x3 stride-2 pad-1 stem: x [n][h][w rounded up to even][4] bf16 holding pixel values x 255 (zeros in the unused
+ * channels and the pad column), w float32 [cout][9][cin], cin <= 4, cout <= 85.  y: raw output [n,ho,wo,C] (NULL: skipped);
+ * dw float32 [cout][9][cin] from dy [n,ho,wo,C] (NULL: skipped), scaled by 1 / 255 as in the step. */
+int spk_op_stem3_train(const void* x_dev, const float* w_dev, const void* dy_dev, void* y_dev, float* dw_dev, int n, int h,
+                       int w, int cin, int cout, int channels, void* hip_stream);
+/* Launch geometry those kernels would get (host arithmetic only, no GPU needed; the launchers' own helpers):
+ *   kind 0 (col_stats / bna_*: m rows, C) and kind 1 (depthwise weight gradient: m = n * ho * ceil(wo / 4) items, C):
+ *     out = rows per block, blocks, channel tiles, channels per tile, rows in flight, idle threads of 256,
+ *           8-channel groups of the last tile
+ *   kind 2 (pool_partial / bna_apply_pool: hw, C): the same with rows per block = rows of a chunk, blocks = chunks
+ *   kind 3 (squeeze-excitation gates: m = c_log, s hidden units): out = rows of W2 per tile, gate tiles, hidden units per
+ *     lane of se_bwd1 (NQ), hidden units per thread of se_wgrad (SJ), blocks of se_wgrad; s > 256: SPK_ERR_UNSUPPORTED
+ *   kind 4 (depthwise: m = k, C = stride, hw = pad, s = accumulate): out = forward form, data-gradient form;
+ *     0 the eval path's LDS-window kernel, 1 dw_dgrad_px_kernel, 2 the gather kernels, -1 none */
+int spk_op_mbconv_geometry(int kind, int m, int channels, int hw, int s_hidden, int out[8]);
+
 /* --- ROI preprocessing straight from the .roi blob ---
  * One ROI of an IFCB sample: byte offset into the .roi blob, width, height
  * (columns 17/15/16 of the .adc line, sykepic/utils/ifcb.py:100-110). */

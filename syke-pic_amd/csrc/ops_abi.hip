@@ -6,7 +6,9 @@
 //   BatchNorm / conv backward             what loss.backward() runs for that layer,  sykepic/train/train.py:242
 // Scratch is allocated and freed inside the call (these are not on any hot path).
 #include "model.h"
+#include "train_effnet.h"
 
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -569,4 +571,229 @@ extern "C" int spk_op_conv_group_wgrad(const void* x, const void* dy, float* dw,
   O_TRY(spk_launch_slab_reduce(slabs, dw, (size_t)c * 9 * (c / groups), chunks, s), "grouped conv wgrad reduce");
   if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_conv_group_wgrad: kernel failed");
   return SPK_OK;
+}
+
+// ---- the MBConv training kernels (train_effnet.hip), one layer at a time: the launches spk_train_forward_backward makes
+// for a depthwise conv, a BatchNorm + activation, a squeeze-excitation layer and the 3x3 stem of an EfficientNet /
+// MobileNetV3 step, on caller-provided buffers.  [M][C] tensors are bf16 with C the padded channel count (a multiple of
+// 64), parameters exist for c < c_log. ----
+namespace {
+bool padded_ok(int C, int c_log) { return C >= 64 && C % 64 == 0 && c_log >= 1 && c_log <= C; }
+}  // namespace
+
+extern "C" int spk_op_dw_train(const void* x, const void* dy, const float* w, void* y, void* dx, float* dw, int accumulate,
+                               int n, int h, int wd, int C, int c_log, int k, int stride, int pad, void* stream) {
+  if (!x || !w || n < 1 || h < 1 || wd < 1 || pad < 0 || ((dx || dw) && !dy) || (!y && !dx && !dw))
+    return ofail(SPK_ERR_ARG, "op_dw_train: bad arguments");
+  if (!padded_ok(C, c_log) || spk_dw_fwd_form(k, stride, pad) == SPK_DW_FORM_NONE ||
+      spk_dw_dgrad_form(k, stride, pad, accumulate) == SPK_DW_FORM_NONE)
+    return ofail(SPK_ERR_UNSUPPORTED, "op_dw_train: C a multiple of 64, k 3 or 5, stride 1 or 2");
+  const int ho = (h + 2 * pad - k) / stride + 1, wo = (wd + 2 * pad - k) / stride + 1;
+  if (h + 2 * pad < k || wd + 2 * pad < k || ho < 1 || wo < 1) return ofail(SPK_ERR_ARG, "op_dw_train: empty output");
+  if ((size_t)n * h * wd * C >= ((size_t)1 << 31) || (size_t)n * ho * wo * C >= ((size_t)1 << 31))
+    return ofail(SPK_ERR_UNSUPPORTED, "op_dw_train: a tensor of 2^31 elements or more");
+  hipStream_t s = (hipStream_t)stream;
+  const int taps = k * k, M = n * ho * wo;
+  Scratch sc;
+  float* wt = sc.get<float>((size_t)2 * taps * C);   // the window and its flipped copy, as the step packs them
+  float* unit = sc.get<float>((size_t)2 * C);
+  const int cap = dw ? spk_dw_wgrad_rows(M, C) : 0;
+  float* slabs = sc.get<float>((size_t)cap * c_log * taps);
+  if (!wt || !unit || !slabs) return ofail(SPK_ERR_HIP, "hipMalloc failed");
+  std::vector<float> hu((size_t)2 * C, 0.f);
+  std::fill(hu.begin(), hu.begin() + C, 1.f);
+  if (hipMemcpyAsync(unit, hu.data(), hu.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return ofail(SPK_ERR_HIP, "op_dw_train: staging failed");
+  PadPackTable tab;
+  memset(&tab, 0, sizeof tab);
+  tab.e[0].src = 0; tab.e[0].dst = 0;
+  tab.e[0].cout = (unsigned)c_log; tab.e[0].taps = (unsigned)taps; tab.e[0].cout_p = (unsigned)C; tab.e[0].kind = 2;
+  tab.count = 1;
+  O_TRY(spk_launch_pack_padded_multi(w, nullptr, wt, tab, s), "dw_pack");
+  if (y)
+    O_TRY(spk_dw_train_forward((const bf16_t*)x, wt, unit, (size_t)C, (bf16_t*)y, n, h, wd, C, k, stride, pad, ho, wo, s),
+          "depthwise fwd");
+  if (dx)
+    O_TRY(spk_dw_train_dgrad((const bf16_t*)dy, wt, unit, (size_t)C, (bf16_t*)dx, accumulate != 0, n, h, wd, C, k, stride,
+                             pad, ho, wo, s), "depthwise dgrad");
+  if (dw) {
+    int rows = 0;
+    const WalkGeometry g = spk_dw_wgrad_geometry(n * ho * ((wo + 3) / 4), C);
+    if (g.blocks > cap) return ofail(SPK_ERR_STATE, "op_dw_train: spk_dw_wgrad_rows is smaller than the launch's partial rows");
+    O_TRY(spk_launch_dw_wgrad((const bf16_t*)x, (const bf16_t*)dy, slabs, n, h, wd, C, c_log, k, stride, pad, ho, wo, &rows,
+                              s), "depthwise wgrad");
+    O_TRY(spk_launch_slab_reduce(slabs, dw, (size_t)c_log * taps, rows, s), "depthwise wgrad reduce");
+  }
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_dw_train: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_bna_forward(const void* raw, const float* gamma, const float* beta, float* running_mean,
+                                  float* running_var, const void* res, const float* rowscale, void* out, float* pool_part,
+                                  float* st, int n, int HW, int C, int c_log, int act, float eps, float momentum,
+                                  void* stream) {
+  if (!raw || !gamma || !beta || !running_mean || !running_var || !out || !st || n < 1 || HW < 1 || act < 0 || act > 3 ||
+      (pool_part && (res || rowscale)))
+    return ofail(SPK_ERR_ARG, "op_bna_forward: bad arguments (the pooling form has no shortcut and no row factor)");
+  if (!padded_ok(C, c_log) || (size_t)n * HW * C >= ((size_t)1 << 31))
+    return ofail(SPK_ERR_UNSUPPORTED, "op_bna_forward: C a multiple of 64, fewer than 2^31 elements");
+  hipStream_t s = (hipStream_t)stream;
+  const int M = n * HW;
+  Scratch sc;
+  float* part = sc.get<float>((size_t)spk_walk_geometry(M, C).blocks * 2 * C);
+  float* tmp = sc.get<float>((size_t)C * 2 * 64);
+  if (!part || !tmp) return ofail(SPK_ERR_HIP, "hipMalloc failed");
+  int nbk = 0;
+  O_TRY(spk_launch_col_stats((const bf16_t*)raw, part, M, C, &nbk, s), "col_stats");
+  O_TRY(spk_launch_bna_finalize(part, nbk, C, c_log, (double)M, gamma, beta, running_mean, running_var, st, eps, momentum,
+                                tmp, s), "bn_finalize");
+  if (pool_part)
+    O_TRY(spk_launch_bna_apply_pool((const bf16_t*)raw, st + 2 * C, st + 3 * C, (bf16_t*)out, pool_part, n, HW, C, act, s),
+          "bn_apply + squeeze");
+  else
+    O_TRY(spk_launch_bna_apply((const bf16_t*)raw, st + 2 * C, st + 3 * C, (const bf16_t*)res, rowscale, (bf16_t*)out, M, C,
+                               HW, act, s), "bn_apply");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_bna_forward: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_bna_backward(const void* g, const void* raw, const float* st, const float* gamma,
+                                   const float* rowscale, void* dy, float* dgamma, float* dbeta, void* g_res,
+                                   int res_accumulate, int n, int HW, int C, int c_log, int act, void* stream) {
+  if (!g || !raw || !st || !gamma || !dy || n < 1 || HW < 1 || act < 0 || act > 3)
+    return ofail(SPK_ERR_ARG, "op_bna_backward: bad arguments");
+  if (!padded_ok(C, c_log) || (size_t)n * HW * C >= ((size_t)1 << 31))
+    return ofail(SPK_ERR_UNSUPPORTED, "op_bna_backward: C a multiple of 64, fewer than 2^31 elements");
+  hipStream_t s = (hipStream_t)stream;
+  const int M = n * HW;
+  Scratch sc;
+  float* part = sc.get<float>((size_t)spk_walk_geometry(M, C).blocks * 2 * C);
+  float* coef = sc.get<float>((size_t)3 * C);
+  float* tmp = sc.get<float>((size_t)C * 2 * 64);
+  if (!part || !coef || !tmp) return ofail(SPK_ERR_HIP, "hipMalloc failed");
+  int nbk = 0;
+  O_TRY(spk_launch_bna_bwd_reduce((const bf16_t*)g, (const bf16_t*)raw, st + 2 * C, st + 3 * C, st, st + C, rowscale, part,
+                                  M, C, HW, act, &nbk, s), "bn bwd reduce");
+  O_TRY(spk_launch_bna_bwd_finalize(part, nbk, C, c_log, (double)M, gamma, st + C, dgamma, dbeta, coef, tmp, s),
+        "bn bwd finalize");
+  O_TRY(spk_launch_bna_bwd_apply((const bf16_t*)g, (const bf16_t*)raw, st + 2 * C, st + 3 * C, st, st + C, coef, rowscale,
+                                 (bf16_t*)dy, (bf16_t*)g_res, g_res ? res_accumulate != 0 : 0, M, C, HW, act, s),
+        "bn bwd apply");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_bna_backward: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_se_train_forward(const void* a, const float* pool_part, const float* W1, const float* b1,
+                                       const float* W2, const float* b2, float* pooled, float* u1, float* h1, float* gate,
+                                       void* out, int n, int HW, int C, int Cl, int S, int gate_kind, void* stream) {
+  if ((!a && !pool_part) || (out && !a) || !W1 || !b1 || !W2 || !b2 || !pooled || !u1 || !h1 || !gate || n < 1 || HW < 1 ||
+      S < 1)
+    return ofail(SPK_ERR_ARG, "op_se_train_forward: bad arguments");
+  if (!padded_ok(C, Cl) || S > 256 || (gate_kind != 0 && gate_kind != 1) || (size_t)n * HW * C >= ((size_t)1 << 31))
+    return ofail(SPK_ERR_UNSUPPORTED, "op_se_train_forward: C a multiple of 64, 256 hidden units at most, gate kind 0 or 1");
+  hipStream_t s = (hipStream_t)stream;
+  const int chunks = spk_se_chunks(HW);
+  Scratch sc;
+  float* part = sc.get<float>(pool_part ? 1 : (size_t)n * chunks * C);
+  if (!part) return ofail(SPK_ERR_HIP, "hipMalloc failed");
+  // pad columns of the saved vectors: zeroed once by the step's plan, never written by the kernels
+  if (hipMemsetAsync(pooled, 0, (size_t)n * C * 4, s) != hipSuccess || hipMemsetAsync(gate, 0, (size_t)n * C * 4, s) != hipSuccess)
+    return ofail(SPK_ERR_HIP, "op_se_train_forward: memset failed");
+  if (!pool_part) O_TRY(spk_launch_pool_rows((const bf16_t*)a, nullptr, part, n, HW, C, s), "se pool");
+  O_TRY(spk_launch_se_gate_fwd(pool_part ? pool_part : part, chunks, 1.f / (float)HW, pooled, W1, b1, W2, b2, u1, h1, gate, n,
+                               C, Cl, S, s, gate_kind), "se gates");
+  if (out) O_TRY(spk_launch_se_scale((const bf16_t*)a, gate, (bf16_t*)out, n, HW, C, s), "se scale");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_se_train_forward: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_se_train_backward(const void* g, const void* a, const float* gate, const float* u1, const float* h1,
+                                        const float* pooled, const float* W1, const float* W2, float* du2, float* du1,
+                                        float* pool_part, void* da, float* gW1, float* gb1, float* gW2, float* gb2, int n,
+                                        int HW, int C, int Cl, int S, int gate_kind, void* stream) {
+  if (!h1 || !pooled || !du2 || !du1 || n < 1 || HW < 1 || S < 1 || (g && (!a || !gate || !u1 || !W1 || !W2 || !da)) ||
+      (!g && (da || pool_part)))
+    return ofail(SPK_ERR_ARG, "op_se_train_backward: bad arguments");
+  if (!padded_ok(C, Cl) || S > 256 || (gate_kind != 0 && gate_kind != 1) || (size_t)n * HW * C >= ((size_t)1 << 31))
+    return ofail(SPK_ERR_UNSUPPORTED, "op_se_train_backward: C a multiple of 64, 256 hidden units at most, gate kind 0 or 1");
+  hipStream_t s = (hipStream_t)stream;
+  const int chunks = spk_se_chunks(HW), tiles = spk_se_gate_tiles(Cl, S);
+  Scratch sc;
+  float* part = sc.get<float>(pool_part || !g ? 1 : (size_t)n * chunks * C);
+  float* dpool = sc.get<float>((size_t)n * C);
+  float* tpart = sc.get<float>((size_t)n * tiles * S);
+  if (!part || !dpool || !tpart) return ofail(SPK_ERR_HIP, "hipMalloc failed");
+  if (pool_part) part = pool_part;
+  if (g) {   // g == NULL: the parameter gradients alone, from the caller's du2 / du1
+    if (hipMemsetAsync(du2, 0, (size_t)n * C * 4, s) != hipSuccess || hipMemsetAsync(dpool, 0, (size_t)n * C * 4, s) != hipSuccess)
+      return ofail(SPK_ERR_HIP, "op_se_train_backward: memset failed");
+    O_TRY(spk_launch_pool_rows((const bf16_t*)g, (const bf16_t*)a, part, n, HW, C, s), "se dgate");
+    O_TRY(spk_launch_se_gate_bwd(part, chunks, du2, gate, u1, W1, W2, du1, dpool, tpart, n, C, Cl, S, s, gate_kind),
+          "se gates bwd");
+  }
+  if (spk_launch_se_wgrad(du2, h1, du1, pooled, gW1, gb1, gW2, gb2, n, C, Cl, S, s) != 0)
+    return ofail(SPK_ERR_HIP, "se wgrad failed");
+  if (g) O_TRY(spk_launch_se_bwd_apply((const bf16_t*)g, gate, dpool, (bf16_t*)da, n, HW, C, s), "se bwd apply");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_se_train_backward: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_stem3_train(const void* x, const float* w, const void* dy, void* y, float* dw, int n, int h, int wd,
+                                  int cin, int cout, int C, void* stream) {
+  if (!x || (!y && !dw) || (y && !w) || (dw && !dy) || n < 1 || h < 1 || wd < 1 || cin < 1 || cin > 4)
+    return ofail(SPK_ERR_ARG, "op_stem3_train: bad arguments");
+  if (!padded_ok(C, cout) || cout * 9 > 768 || (size_t)n * h * wd * C >= ((size_t)1 << 31))
+    return ofail(SPK_ERR_UNSUPPORTED, "op_stem3_train: C a multiple of 64, 85 output channels at most");
+  hipStream_t s = (hipStream_t)stream;
+  const int wstride = (wd + 1) & ~1, ho = (h - 1) / 2 + 1, wo = (wd - 1) / 2 + 1, M = n * ho * wo;
+  if (y)
+    O_TRY(spk_launch_stem3_train_fwd((const bf16_t*)x, w, (bf16_t*)y, n, h, wd, wstride, cin, cout, C, ho, wo, s,
+                                     1.0f / SPK_INPUT_SCALE), "stem3 fwd");
+  if (dw) {
+    int ppb, nbk = 0;
+    Scratch sc;
+    float* slabs = sc.get<float>((size_t)spk_stem3_wgrad_blocks(M, &ppb) * cout * 9 * cin);
+    if (!slabs) return ofail(SPK_ERR_HIP, "hipMalloc failed");
+    O_TRY(spk_launch_stem3_wgrad((const bf16_t*)x, (const bf16_t*)dy, slabs, n, h, wd, wstride, cin, cout, C, ho, wo, &nbk, s),
+          "stem3 wgrad");
+    O_TRY(spk_launch_slab_reduce(slabs, dw, (size_t)cout * 9 * cin, nbk, s, 1.0f / SPK_INPUT_SCALE), "stem3 wgrad reduce");
+    if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_stem3_train: kernel failed");   // (slabs die here)
+    return SPK_OK;
+  }
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_stem3_train: kernel failed");
+  return SPK_OK;
+}
+
+// What the launchers of train_effnet.hip would choose for a problem (host only, no GPU): see include/sykepic_hip.h
+extern "C" int spk_op_mbconv_geometry(int kind, int M, int C, int HW, int S, int out[8]) {
+  if (!out) return ofail(SPK_ERR_ARG, "op_mbconv_geometry: bad arguments");
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  auto put = [&](const WalkGeometry& g) {
+    out[0] = g.rows_per_block; out[1] = g.blocks; out[2] = g.ctiles; out[3] = g.tile_channels; out[4] = g.rows_in_flight;
+    out[5] = g.idle_threads;
+    out[6] = C / 8 - (g.ctiles - 1) * (g.tile_channels / 8);   // 8-channel groups of the last tile
+  };
+  switch (kind) {
+    case 0:
+    case 1:
+      if (M < 1 || C < 64 || C % 64) return ofail(SPK_ERR_ARG, "op_mbconv_geometry: bad arguments");
+      put(kind == 0 ? spk_walk_geometry(M, C) : spk_dw_wgrad_geometry(M, C));
+      return SPK_OK;
+    case 2:
+      if (HW < 1 || C < 64 || C % 64) return ofail(SPK_ERR_ARG, "op_mbconv_geometry: bad arguments");
+      put(spk_pool_geometry(HW, C));
+      return SPK_OK;
+    case 3:
+      if (M < 1 || S < 1) return ofail(SPK_ERR_ARG, "op_mbconv_geometry: bad arguments");
+      if (S > 256) return ofail(SPK_ERR_UNSUPPORTED, "op_mbconv_geometry: 256 hidden units at most");
+      out[0] = spk_se_tile_rows(S); out[1] = spk_se_gate_tiles(M, S); out[2] = spk_se_bwd1_nq(S); out[3] = spk_se_wgrad_sj(S);
+      out[4] = (M + 63) / 64;   // blocks of se_wgrad per job
+      return SPK_OK;
+    case 4:
+      out[0] = spk_dw_fwd_form(M, C, HW);
+      out[1] = spk_dw_dgrad_form(M, C, HW, S);
+      return SPK_OK;
+  }
+  return ofail(SPK_ERR_ARG, "op_mbconv_geometry: kind 0 ... 4");
 }

@@ -586,17 +586,9 @@ extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, in
         const int C = o.c, M = n * o.h * o.w;
         float* st = t->stats + t->conv[i].stat_off;
         int nbk = 0;
-        // the eval path's kernel (window weights in LDS, four adjacent outputs per thread) with a = 1, b = 0, no
-        // activation; -2: a window it does not have
-        int r = L.d.pad == (L.d.k - 1) / 2
-                    ? spk_launch_dwconv((const bf16_t*)m->T(L.d.src), t->dwt + t->conv[i].dwt_off, t->unit,
-                                        t->unit + t->unit_c, t->RAW(i), nullptr, n, in.h, in.w, C, o.h, o.w, L.d.k,
-                                        L.d.stride, 0, DT_BF16, s)
-                    : -2;
-        if (r == -2)
-          r = spk_launch_dw_train_fwd((const bf16_t*)m->T(L.d.src), t->dwt + t->conv[i].dwt_off, t->RAW(i), n, in.h, in.w,
-                                      C, L.d.k, L.d.stride, L.d.pad, o.h, o.w, s);
-        K_TRY(r, "depthwise fwd");
+        // the eval path's kernel in bf16 or dw_fwd_kernel: spk_dw_fwd_form (train_effnet.hip)
+        K_TRY(spk_dw_train_forward((const bf16_t*)m->T(L.d.src), t->dwt + t->conv[i].dwt_off, t->unit, t->unit_c, t->RAW(i),
+                                   n, in.h, in.w, C, L.d.k, L.d.stride, L.d.pad, o.h, o.w, s), "depthwise fwd");
         K_TRY(spk_launch_col_stats(t->RAW(i), part, M, C, &nbk, s), "col_stats");
         mark(m, PH_CONV_FWD);
         L.nbt += 1;
@@ -844,16 +836,10 @@ extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, in
         if (L.d.kind == SPK_OP_DWCONV) {
           const float* wt = t->dwt + t->conv[i].dwt_off;
           if (needs[L.d.src]) {
-            // stride 1: dx = depthwise conv of dy with the flipped window (the forward kernel); else the gather kernel
-            int r = L.d.stride == 1 && !has_grad[L.d.src] && L.d.pad == (L.d.k - 1) / 2
-                        ? spk_launch_dwconv(dy, wt + (size_t)L.d.k * L.d.k * C, t->unit, t->unit + t->unit_c,
-                                            (bf16_t*)t->G(L.d.src), nullptr, n, o.h, o.w, C, in.h, in.w, L.d.k, 1, 0,
-                                            DT_BF16, s)
-                        : -2;
-            if (r == -2)
-              r = spk_launch_dw_dgrad(dy, wt, (bf16_t*)t->G(L.d.src), has_grad[L.d.src] != 0, n, in.h, in.w, C, L.d.k,
-                                      L.d.stride, L.d.pad, o.h, o.w, s);
-            K_TRY(r, "depthwise dgrad");
+            // stride 1: dx = depthwise conv of dy with the flipped window (the forward kernel); else the px / gather
+            // kernels: spk_dw_dgrad_form (train_effnet.hip)
+            K_TRY(spk_dw_train_dgrad(dy, wt, t->unit, t->unit_c, (bf16_t*)t->G(L.d.src), has_grad[L.d.src] != 0, n, in.h,
+                                     in.w, C, L.d.k, L.d.stride, L.d.pad, o.h, o.w, s), "depthwise dgrad");
             mark(m, PH_CONV_DGRAD);
             has_grad[L.d.src] = 1;
           }

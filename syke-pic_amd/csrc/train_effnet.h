@@ -29,6 +29,30 @@ int spk_launch_dw_train_fwd(const bf16_t* x, const float* wt, bf16_t* y, int n, 
 int spk_launch_dw_dgrad(const bf16_t* dy, const float* wt, bf16_t* dx, int accumulate, int n, int h, int wd, int C, int k,
                         int stride, int pad, int ho, int wo, hipStream_t s);
 int spk_dw_wgrad_rows(int M, int C);
+// The two launcher choices of a depthwise layer in a training step, made in one place for the step (train.hip) and the
+// single-operator hook (ops_abi.hip).  wt: the packed windows [2][k*k][C] (forward, then flipped: pack_padded_multi
+// kind 2); unit: [unit_c] ones, [unit_c] zeros (the eval kernel applies a per-channel a * x + b).
+enum { SPK_DW_FORM_NONE = -1, SPK_DW_FORM_LDS = 0, SPK_DW_FORM_PX = 1, SPK_DW_FORM_GATHER = 2 };
+// forward: SPK_DW_FORM_LDS the eval path's kernel in bf16 (pad (k-1)/2), SPK_DW_FORM_GATHER dw_fwd_kernel (any pad)
+int spk_dw_fwd_form(int k, int stride, int pad);
+// data gradient: SPK_DW_FORM_LDS the eval path's kernel on dy with the flipped window (stride 1, pad (k-1)/2, dx not
+// accumulated), SPK_DW_FORM_PX dw_dgrad_px_kernel (pad (k-1)/2), SPK_DW_FORM_GATHER dw_dgrad_kernel (any pad)
+int spk_dw_dgrad_form(int k, int stride, int pad, int accumulate);
+int spk_dw_train_forward(const bf16_t* x, const float* wt, const float* unit, size_t unit_c, bf16_t* y, int n, int h,
+                         int wd, int C, int k, int stride, int pad, int ho, int wo, hipStream_t s);
+int spk_dw_train_dgrad(const bf16_t* dy, const float* wt, const float* unit, size_t unit_c, bf16_t* dx, int accumulate,
+                       int n, int h, int wd, int C, int k, int stride, int pad, int ho, int wo, hipStream_t s);
+// Launch geometry as the launchers choose it (spk_op_mbconv_geometry reports these)
+struct WalkGeometry {
+  int rows_per_block, blocks, ctiles, tile_channels, rows_in_flight, idle_threads;
+};
+WalkGeometry spk_walk_geometry(int M, int C);          // col_stats, bna_apply, bna_bwd_reduce, bna_bwd_apply
+WalkGeometry spk_dw_wgrad_geometry(int items, int C);  // dw_wgrad_kernel; items = n * ho * ceil(wo / 4)
+WalkGeometry spk_pool_geometry(int HW, int C);         // pool_partial, bna_apply_pool: rows_per_block = rows of a chunk,
+                                                       // blocks = chunks
+int spk_se_tile_rows(int S);      // rows of W2 staged per block of se_fc2_train / se_bwd1
+int spk_se_bwd1_nq(int S);        // hidden units per lane of se_bwd1_kernel
+int spk_se_wgrad_sj(int S);       // hidden units per thread of se_wgrad_kernel (12: predicated, 13 ... 16: exact)
 int spk_launch_dw_wgrad(const bf16_t* x, const bf16_t* dy, float* partials, int n, int h, int wd, int C, int c_log,
                         int k, int stride, int pad, int ho, int wo, int* rows, hipStream_t s);
 int spk_launch_bna_apply_pool(const bf16_t* raw, const float* scale, const float* shift, bf16_t* out, float* part, int n,

@@ -36,8 +36,9 @@ __device__ __forceinline__ float act_fwd(float z, int act) {
   if (act == SPK_ACT_HSWISH) return hswish_f(z);
   return act == SPK_ACT_SILU ? z * sigmoidf_(z) : (act == SPK_ACT_RELU ? fmaxf(z, 0.f) : z);
 }
-// Hardswish' as torch takes it: 0 below -3, z / 3 + 1/2 on [-3, 3], 1 above
-__device__ __forceinline__ float hswish_grad(float z) { return z < -3.f ? 0.f : (z <= 3.f ? z * (1.f / 3.f) + 0.5f : 1.f); }
+// Hardswish' as torch autograd takes it: z / 3 + 1/2 on the OPEN interval (-3, 3), 0 at and below -3, 1 at and above 3
+// (torch's hardswish_backward; the closed interval gave -1/2 at -3 and 3/2 at 3: tests/test_gpu_mbconv_train_ops.py)
+__device__ __forceinline__ float hswish_grad(float z) { return z <= -3.f ? 0.f : (z < 3.f ? z * (1.f / 3.f) + 0.5f : 1.f); }
 __device__ __forceinline__ float act_grad(float z, int act) {
   if (act == SPK_ACT_SILU) {
     const float s = sigmoidf_(z);
@@ -1228,9 +1229,15 @@ inline int walk_rows(int M, int* rows_per_block) {
 }
 // channel tiles of about 256 channels once a tensor is wider than that
 inline int walk_ctiles(int C) { return (C / 8 + 31) / 32; }
-inline size_t walk_lds(int C) {
+// the channel tile of a block as RowWalk lays it out: 8-channel groups per tile, threads per row, rows in flight
+struct WalkTile { int tile, tpr, rif; };
+inline WalkTile walk_tile(int C) {
   const int c8 = C / 8, cts = walk_ctiles(C), tile = (c8 + cts - 1) / cts, tpr = tile < 256 ? tile : 256;
-  return (size_t)(256 / tpr) * 2 * tile * 8 * sizeof(float);
+  return {tile, tpr, 256 / tpr};
+}
+inline size_t walk_lds(int C) {
+  const WalkTile t = walk_tile(C);
+  return (size_t)t.rif * 2 * t.tile * 8 * sizeof(float);
 }
 inline size_t pool_lds(int C) { return walk_lds(C) / 2; }   // [rif][TW] floats
 #define LAUNCH_OK() (hipGetLastError() == hipSuccess ? 0 : -1)
@@ -1329,13 +1336,17 @@ int spk_launch_dw_train_fwd(const bf16_t* x, const float* wt, bf16_t* y, int n, 
   return LAUNCH_OK();
 }
 
+static bool dw_dgrad_px_ok(int k, int stride, int pad) {
+  return (stride == 1 || stride == 2) && pad == (k - 1) / 2 && (k == 3 || k == 5);
+}
+
 int spk_launch_dw_dgrad(const bf16_t* dy, const float* wt, bf16_t* dx, int accumulate, int n, int h, int wd, int C, int k,
                         int stride, int pad, int ho, int wo, hipStream_t s) {
   const size_t total = (size_t)n * h * wd * (C / 8);
 #define DW_DGRAD(K_, S_)                                                                                              \
   hipLaunchKernelGGL((dw_dgrad_kernel<K_, S_>), dim3(grid_of(total, 256)), dim3(256), 0, s, dy, wt, dx, accumulate, n, h, \
                      wd, C, pad, ho, wo)
-  if ((stride == 1 || stride == 2) && pad == (k - 1) / 2 && (k == 3 || k == 5)) {
+  if (dw_dgrad_px_ok(k, stride, pad)) {
     const dim3 grid(grid_of((size_t)n * h * ((wd + 3) / 4) * (C / 8), 256));
 #define DW_DGRAD_PX(K_, S_)                                                                                             \
   hipLaunchKernelGGL((dw_dgrad_px_kernel<K_, S_>), grid, dim3(256), 0, s, dy, wt, dx, accumulate, n, h, wd, C, ho, wo)
@@ -1373,8 +1384,9 @@ int spk_launch_dw_wgrad(const bf16_t* x, const bf16_t* dy, float* partials, int 
   const int M = n * ho * ((wo + DW_PX - 1) / DW_PX);
   const int nb = dw_wgrad_blocks(M, &rpb);
   *rows = nb;
-  const int c8 = C / 8, cts = walk_ctiles(C), tile = (c8 + cts - 1) / cts, tpr = tile < 256 ? tile : 256;
-  const size_t lds = (size_t)(256 / tpr) * tpr * k * 8 * sizeof(float);
+  const int cts = walk_ctiles(C);
+  const WalkTile wt_ = walk_tile(C);
+  const size_t lds = (size_t)wt_.rif * wt_.tpr * k * 8 * sizeof(float);
 #define DW_WGRAD(K_, S_)                                                                                          \
   hipLaunchKernelGGL((dw_wgrad_kernel<K_, S_>), dim3(nb, K_, cts), dim3(256), lds, s, x, dy, partials, n, h, wd, C, \
                      c_log, pad, ho, wo, rpb)
@@ -1387,7 +1399,63 @@ int spk_launch_dw_wgrad(const bf16_t* x, const bf16_t* dy, float* partials, int 
   return LAUNCH_OK();
 }
 
+// eval-path kernel (effnet.hip, spk_launch_dwconv) windows: k 3 / 5, stride 1 / 2, pad (k-1)/2
+static bool dw_lds_ok(int k, int stride, int pad) {
+  return pad == (k - 1) / 2 && (k == 3 || k == 5) && (stride == 1 || stride == 2);
+}
+int spk_dw_fwd_form(int k, int stride, int pad) {
+  if (dw_lds_ok(k, stride, pad)) return SPK_DW_FORM_LDS;
+  return k == 3 || k == 5 ? SPK_DW_FORM_GATHER : SPK_DW_FORM_NONE;
+}
+int spk_dw_dgrad_form(int k, int stride, int pad, int accumulate) {
+  // stride 1: dx = depthwise conv of dy with the flipped window (the forward kernel); else the px / gather kernels
+  if (stride == 1 && !accumulate && dw_lds_ok(k, stride, pad)) return SPK_DW_FORM_LDS;
+  if (dw_dgrad_px_ok(k, stride, pad)) return SPK_DW_FORM_PX;
+  return (k == 3 || k == 5) && (stride == 1 || stride == 2) ? SPK_DW_FORM_GATHER : SPK_DW_FORM_NONE;
+}
+
+int spk_dw_train_forward(const bf16_t* x, const float* wt, const float* unit, size_t unit_c, bf16_t* y, int n, int h,
+                         int wd, int C, int k, int stride, int pad, int ho, int wo, hipStream_t s) {
+  // the eval path's kernel (window weights in LDS, four adjacent outputs per thread) with a = 1, b = 0, no
+  // activation; -2: a window it does not have
+  int r = spk_dw_fwd_form(k, stride, pad) == SPK_DW_FORM_LDS
+              ? spk_launch_dwconv(x, wt, unit, unit + unit_c, y, nullptr, n, h, wd, C, ho, wo, k, stride, 0, DT_BF16, s)
+              : -2;
+  if (r == -2) r = spk_launch_dw_train_fwd(x, wt, y, n, h, wd, C, k, stride, pad, ho, wo, s);
+  return r;
+}
+
+int spk_dw_train_dgrad(const bf16_t* dy, const float* wt, const float* unit, size_t unit_c, bf16_t* dx, int accumulate,
+                       int n, int h, int wd, int C, int k, int stride, int pad, int ho, int wo, hipStream_t s) {
+  int r = spk_dw_dgrad_form(k, stride, pad, accumulate) == SPK_DW_FORM_LDS
+              ? spk_launch_dwconv(dy, wt + (size_t)k * k * C, unit, unit + unit_c, dx, nullptr, n, ho, wo, C, h, wd, k, 1, 0,
+                                  DT_BF16, s)
+              : -2;
+  if (r == -2) r = spk_launch_dw_dgrad(dy, wt, dx, accumulate, n, h, wd, C, k, stride, pad, ho, wo, s);
+  return r;
+}
+
+static WalkGeometry walk_geometry(int rpb, int nb, int C) {
+  const WalkTile t = walk_tile(C);
+  return {rpb, nb, walk_ctiles(C), t.tile * 8, t.rif, 256 - t.rif * t.tpr};
+}
+WalkGeometry spk_walk_geometry(int M, int C) {
+  int rpb;
+  const int nb = walk_rows(M, &rpb);
+  return walk_geometry(rpb, nb, C);
+}
+WalkGeometry spk_dw_wgrad_geometry(int items, int C) {
+  int rpb;
+  const int nb = dw_wgrad_blocks(items, &rpb);
+  return walk_geometry(rpb, nb, C);
+}
+
 int spk_se_chunks(int HW) { return HW >= 3136 ? 16 : (HW >= 196 ? 4 : 1); }
+
+WalkGeometry spk_pool_geometry(int HW, int C) {
+  const int chunks = spk_se_chunks(HW);
+  return walk_geometry((HW + chunks - 1) / chunks, chunks, C);
+}
 
 // part[n][chunks][C] = per-chunk sums over HW of x (* y); the squeeze-excitation gate kernels sum the chunks themselves
 int spk_launch_pool_rows(const bf16_t* x, const bf16_t* y, float* part, int n, int HW, int C, hipStream_t s) {
@@ -1445,6 +1513,14 @@ int spk_launch_pack_padded_multi(const float* pbuf, bf16_t* wpack, float* dwt, c
   return LAUNCH_OK();
 }
 
+int spk_se_tile_rows(int S) { return se_tile_rows(S); }
+int spk_se_bwd1_nq(int S) { return S > 192 ? 4 : 3; }
+int spk_se_wgrad_sj(int S) {
+  if (S <= 192) return 12;
+  const int sj = (S + 15) >> 4;
+  return sj < 16 ? sj : 16;
+}
+
 int spk_se_gate_tiles(int Cl, int S) {
   const int R = se_tile_rows(S);
   return (Cl + R - 1) / R;
@@ -1479,11 +1555,11 @@ int spk_launch_se_gate_bwd(const float* pool_part, int chunks, float* dgate, con
   hipLaunchKernelGGL((se_bwd1_kernel<G, Q>), dim3(n, tiles), dim3(256), lds1, s, pool_part, chunks, dgate, gate, W2, part, \
                      C, Cl, S, R)
   if (gate_kind) {
-    if (S > 192) SE_BWD1(1, 4); else SE_BWD1(1, 3);
+    if (spk_se_bwd1_nq(S) == 4) SE_BWD1(1, 4); else SE_BWD1(1, 3);
     hipLaunchKernelGGL(se_bwd2_kernel<1>, dim3(n, (Cl + 1023) / 1024), dim3(256), (size_t)S * 4, s, part, tiles, u1, W1, du1,
                        dpool, C, Cl, S);
   } else {
-    if (S > 192) SE_BWD1(0, 4); else SE_BWD1(0, 3);
+    if (spk_se_bwd1_nq(S) == 4) SE_BWD1(0, 4); else SE_BWD1(0, 3);
     hipLaunchKernelGGL(se_bwd2_kernel<0>, dim3(n, (Cl + 1023) / 1024), dim3(256), (size_t)S * 4, s, part, tiles, u1, W1, du1,
                        dpool, C, Cl, S);
   }
@@ -1499,15 +1575,13 @@ int spk_launch_se_wgrad(const float* du2, const float* h1, const float* du1, con
 #define SE_WGRAD(SJ, EX)                                                                                           \
   hipLaunchKernelGGL((se_wgrad_kernel<SJ, EX>), dim3((Cl + 63) / 64, 2), dim3(256), lds, s, du2, h1, du1, pooled, gW1, gb1, \
                      gW2, gb2, n, C, Cl, S)
-  if (S > 192) {
-    switch ((S + 15) >> 4) {
-      case 13: SE_WGRAD(13, true); break;
-      case 14: SE_WGRAD(14, true); break;
-      case 15: SE_WGRAD(15, true); break;
-      default: SE_WGRAD(16, true);
-    }
-  } else
-    SE_WGRAD(12, false);
+  switch (spk_se_wgrad_sj(S)) {
+    case 12: SE_WGRAD(12, false); break;
+    case 13: SE_WGRAD(13, true); break;
+    case 14: SE_WGRAD(14, true); break;
+    case 15: SE_WGRAD(15, true); break;
+    default: SE_WGRAD(16, true);
+  }
 #undef SE_WGRAD
   return LAUNCH_OK();
 }

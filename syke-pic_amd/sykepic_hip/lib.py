@@ -109,6 +109,13 @@ SYMBOLS = {
     "spk_op_pw_fp8": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_float, C.c_float, _P]),
     "spk_op_dwconv": (C.c_int, [_P, _P, _P, _P, _P, _P] + [C.c_int] * 8 + [_P]),
+    "spk_op_dw_train": (C.c_int, [_P] * 6 + [C.c_int] * 9 + [_P]),
+    "spk_op_bna_forward": (C.c_int, [_P] * 10 + [C.c_int] * 5 + [C.c_float, C.c_float, _P]),
+    "spk_op_bna_backward": (C.c_int, [_P] * 9 + [C.c_int] * 6 + [_P]),
+    "spk_op_se_train_forward": (C.c_int, [_P] * 11 + [C.c_int] * 6 + [_P]),
+    "spk_op_se_train_backward": (C.c_int, [_P] * 16 + [C.c_int] * 6 + [_P]),
+    "spk_op_stem3_train": (C.c_int, [_P] * 5 + [C.c_int] * 6 + [_P]),
+    "spk_op_mbconv_geometry": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)]),
     "spk_op_conv1x1": (C.c_int, [_P, _P, _P, _P, _P, _P] + [C.c_int] * 9 + [_P]),
     "spk_op_conv1x1_num_configs": (C.c_int, []),
     "spk_op_conv3x3": (C.c_int, [_P, _P, _P, _P, _P, _P] + [C.c_int] * 8 + [_P]),

@@ -342,3 +342,179 @@ def zero_sum_round(w, mu=None, period=None):
     with torch.cuda.device(w.device):
         lib.check(so.spk_op_zero_sum_round(_p(w), _p(mu), _p(out), rows, row_len, int(period or row_len), _stream(w.device)))
     return out
+
+
+# ---- the MBConv training kernels (csrc/train_effnet.hip), one layer at a time.  Unlike the hooks above these take the
+# step's own layout: bf16 NHWC device tensors whose last dimension is the PADDED channel count C (a multiple of 64, zeros
+# in the pad channels); parameters float32 with c_log <= C entries.
+
+def _bf16c(t):
+    assert t.dtype == torch.bfloat16 and t.is_contiguous() and t.is_cuda, "bf16 contiguous device tensor expected"
+    return t
+
+
+def _f32c(t):
+    if t is None:
+        return None
+    assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda, "float32 contiguous device tensor expected"
+    return t
+
+
+def mbconv_geometry(kind, m=0, c=0, hw=0, s=0):
+    """spk_op_mbconv_geometry: the launch geometry the kernels of csrc/train_effnet.hip would get (no GPU needed).
+    Returns the 8 integers (see include/sykepic_hip.h); raises RuntimeError when the launchers refuse the problem."""
+    so = lib.load()
+    out = (C.c_int * 8)()
+    lib.check(so.spk_op_mbconv_geometry(int(kind), int(m), int(c), int(hw), int(s), out))
+    return list(out)
+
+
+def dw_train(x, weight, c_log, k, stride=1, pad=None, dy=None, want_y=True, want_dx=False, want_dw=False,
+             accumulate_into=None):
+    """Depthwise layer of a training step (spk_op_dw_train).  x [N,H,W,C] bf16, weight [c_log, k*k] float32, dy
+    [N,Ho,Wo,C] bf16.  Returns dict(y, dx, dw): the raw forward output, the data gradient (added to `accumulate_into`
+    [N,H,W,C] when given) and the weight gradient [c_log, k*k]; entries not asked for are None."""
+    so = lib.load()
+    dev = x.device
+    n, h, w, c = x.shape
+    pad = (k - 1) // 2 if pad is None else pad
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    wk = _f32c(weight.reshape(c_log, k * k))
+    nan = float("nan")   # poison: every element must be written by the launches
+    y = torch.full((n, ho, wo, c), nan, dtype=torch.bfloat16, device=dev) if want_y else None
+    dx = None
+    if accumulate_into is not None:
+        dx = accumulate_into.clone()
+    elif want_dx:
+        dx = torch.full((n, h, w, c), nan, dtype=torch.bfloat16, device=dev)
+    dw = torch.full((c_log, k * k), nan, dtype=torch.float32, device=dev) if want_dw else None
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_dw_train(_p(_bf16c(x)), _p(_bf16c(dy)) if dy is not None else None, _p(wk), _p(y), _p(dx),
+                                     _p(dw), int(accumulate_into is not None), n, h, w, c, int(c_log), int(k),
+                                     int(stride), int(pad), _stream(dev)))
+    return {"y": y, "dx": dx, "dw": dw}
+
+
+def bna_forward(raw, gamma, beta, running_mean, running_var, act=0, res=None, rowscale=None, pool=False, eps=1e-5,
+                momentum=0.1):
+    """BatchNorm (train mode) + activation forward (spk_op_bna_forward).  raw [N,HW,C] bf16; gamma / beta /
+    running_* float32 [c_log] (the running statistics are updated in place); res [N,HW,C] bf16, rowscale [N] float32.
+    pool: the form that also returns the per-chunk channel sums of the output, pool_part [N,chunks,C].
+    Returns dict(out, st [4,C] = mean, invstd, scale, shift, pool_part)."""
+    so = lib.load()
+    dev = raw.device
+    n, hw, c = raw.shape
+    c_log = gamma.numel()
+    out = torch.full((n, hw, c), float("nan"), dtype=torch.bfloat16, device=dev)
+    st = torch.full((4, c), float("nan"), dtype=torch.float32, device=dev)
+    part = None
+    if pool:
+        chunks = mbconv_geometry(2, c=c, hw=hw)[1]
+        part = torch.full((n, chunks, c), float("nan"), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_bna_forward(_p(_bf16c(raw)), _p(_f32c(gamma)), _p(_f32c(beta)), _p(_f32c(running_mean)),
+                                        _p(_f32c(running_var)), _p(_bf16c(res)) if res is not None else None,
+                                        _p(_f32c(rowscale)), _p(out), _p(part), _p(st), n, hw, c, c_log, int(act),
+                                        float(eps), float(momentum), _stream(dev)))
+    return {"out": out, "st": st, "pool_part": part}
+
+
+def bna_backward(g, raw, st, gamma, act=0, rowscale=None, g_res=None, want_res=False):
+    """Its backward (spk_op_bna_backward).  g, raw [N,HW,C] bf16, st [4,C] as bna_forward returned it, gamma [c_log].
+    g_res: the shortcut gradient accumulates into a copy of it; want_res: it is returned on its own.
+    Returns dict(dy, dgamma, dbeta, g_res)."""
+    so = lib.load()
+    dev = g.device
+    n, hw, c = g.shape
+    c_log = gamma.numel()
+    dy = torch.full((n, hw, c), float("nan"), dtype=torch.bfloat16, device=dev)
+    dgamma = torch.full((c_log,), float("nan"), dtype=torch.float32, device=dev)
+    dbeta = torch.full((c_log,), float("nan"), dtype=torch.float32, device=dev)
+    gres = None
+    if g_res is not None:
+        gres = g_res.clone()
+    elif want_res:
+        gres = torch.full((n, hw, c), float("nan"), dtype=torch.bfloat16, device=dev)
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_bna_backward(_p(_bf16c(g)), _p(_bf16c(raw)), _p(_f32c(st)), _p(_f32c(gamma)),
+                                         _p(_f32c(rowscale)), _p(dy), _p(dgamma), _p(dbeta), _p(gres),
+                                         int(g_res is not None), n, hw, c, c_log, int(act), _stream(dev)))
+    return {"dy": dy, "dgamma": dgamma, "dbeta": dbeta, "g_res": gres}
+
+
+def se_train_forward(a, w1, b1, w2, b2, gate_kind=0, pool_part=None, want_out=True):
+    """Squeeze-excitation forward (spk_op_se_train_forward).  a [N,HW,C] bf16; w1 [S,Cl], b1 [S], w2 [Cl,S], b2 [Cl]
+    float32; pool_part [N,chunks,C]: the sums bna_forward(pool=True) left, instead of pooling `a`.
+    Returns dict(pooled [N,C], u1 [N,S], h1 [N,S], gate [N,C], out [N,HW,C])."""
+    so = lib.load()
+    dev = a.device
+    n, hw, c = a.shape
+    s_hid, cl = w1.shape
+    nan = float("nan")
+    pooled = torch.full((n, c), nan, dtype=torch.float32, device=dev)
+    gate = torch.full((n, c), nan, dtype=torch.float32, device=dev)
+    u1 = torch.full((n, s_hid), nan, dtype=torch.float32, device=dev)
+    h1 = torch.full((n, s_hid), nan, dtype=torch.float32, device=dev)
+    out = torch.full((n, hw, c), nan, dtype=torch.bfloat16, device=dev) if want_out else None
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_se_train_forward(_p(_bf16c(a)), _p(_f32c(pool_part)), _p(_f32c(w1)), _p(_f32c(b1)),
+                                             _p(_f32c(w2)), _p(_f32c(b2)), _p(pooled), _p(u1), _p(h1), _p(gate), _p(out),
+                                             n, hw, c, cl, s_hid, int(gate_kind), _stream(dev)))
+    return {"pooled": pooled, "u1": u1, "h1": h1, "gate": gate, "out": out}
+
+
+def se_train_backward(g, a, saved, w1, w2, gate_kind=0):
+    """Its backward (spk_op_se_train_backward).  g, a [N,HW,C] bf16, saved: what se_train_forward returned.
+    Returns dict(da, gw1, gb1, gw2, gb2, du2 [N,C], du1 [N,S], pool_part [N,chunks,C] = per-chunk sums of g * a)."""
+    so = lib.load()
+    dev = g.device
+    n, hw, c = g.shape
+    s_hid, cl = w1.shape
+    nan = float("nan")
+    f = lambda *shape: torch.full(shape, nan, dtype=torch.float32, device=dev)   # noqa: E731
+    du2, du1 = f(n, c), f(n, s_hid)
+    part = f(n, mbconv_geometry(2, c=c, hw=hw)[1], c)
+    gw1, gb1, gw2, gb2 = f(s_hid, cl), f(s_hid), f(cl, s_hid), f(cl)
+    da = torch.full((n, hw, c), nan, dtype=torch.bfloat16, device=dev)
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_se_train_backward(
+            _p(_bf16c(g)), _p(_bf16c(a)), _p(_f32c(saved["gate"])), _p(_f32c(saved["u1"])), _p(_f32c(saved["h1"])),
+            _p(_f32c(saved["pooled"])), _p(_f32c(w1)), _p(_f32c(w2)), _p(du2), _p(du1), _p(part), _p(da), _p(gw1), _p(gb1),
+            _p(gw2), _p(gb2), n, hw, c, cl, s_hid, int(gate_kind), _stream(dev)))
+    return {"da": da, "gw1": gw1, "gb1": gb1, "gw2": gw2, "gb2": gb2, "du2": du2, "du1": du1, "pool_part": part}
+
+
+def se_wgrad(du2, h1, du1, pooled, cl):
+    """The parameter-gradient kernel of the squeeze-excitation layer alone, on the caller's vectors
+    (spk_op_se_train_backward with g == NULL): du2, pooled [N,C], h1, du1 [N,S] float32.
+    Returns dict(gw1 [S,cl], gb1 [S], gw2 [cl,S], gb2 [cl])."""
+    so = lib.load()
+    dev = du2.device
+    n, c = du2.shape
+    s_hid = h1.shape[1]
+    f = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)   # noqa: E731
+    gw1, gb1, gw2, gb2 = f(s_hid, cl), f(s_hid), f(cl, s_hid), f(cl)
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_se_train_backward(None, None, None, None, _p(_f32c(h1)), _p(_f32c(pooled)), None, None,
+                                              _p(_f32c(du2)), _p(_f32c(du1)), None, None, _p(gw1), _p(gb1), _p(gw2),
+                                              _p(gb2), n, 1, c, int(cl), s_hid, 0, _stream(dev)))
+    return {"gw1": gw1, "gb1": gb1, "gw2": gw2, "gb2": gb2}
+
+
+def stem3_train(x4, weight, c, dy=None, w_in=None):
+    """The 3x3 stride-2 stem of a training step (spk_op_stem3_train).  x4 [N,H,Wp,4] bf16: pixel values x 255 in the
+    first cin channels, Wp = the width rounded up to even (`w_in`: the logical width, default Wp); weight [cout,9,cin]
+    float32; dy [N,Ho,Wo,C] bf16.  Returns dict(y [N,Ho,Wo,C] raw output, dw [cout,9,cin] or None)."""
+    so = lib.load()
+    dev = x4.device
+    n, h, wp, _ = x4.shape
+    w = wp if w_in is None else w_in
+    assert wp == (w + 1) & ~1
+    cout, _, cin = weight.shape
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    y = torch.full((n, ho, wo, c), float("nan"), dtype=torch.bfloat16, device=dev)
+    dw = torch.full((cout, 9, cin), float("nan"), dtype=torch.float32, device=dev) if dy is not None else None
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_stem3_train(_p(_bf16c(x4)), _p(_f32c(weight)), _p(_bf16c(dy)) if dy is not None else None,
+                                        _p(y), _p(dw), n, h, w, cin, cout, int(c), _stream(dev)))
+    return {"y": y, "dw": dw}
