@@ -1,13 +1,18 @@
 // Host-side sanitizer driver (the reference has no native code, so no sanitizer story; this
 // library has ~9 k lines of it).  Built by `build.sh asan` with -fsanitize=address,undefined on the HOST pass of every
 // translation unit and run on the CPU (tests/test_abi.py): it walks the host logic that does not need a GPU - handle
-// creation and its error paths, the parameter table, spk_last_error, and the three tuner-cache parsers - so that
-// heap overflows, use-after-free and undefined behaviour there abort the run.  With no GPU every HIP call fails and
-// the error paths are what runs; on a GPU box the same binary works on real (small) buffers.
+// creation and its error paths, the parameter table, spk_last_error, and the tuner table (tune_table.h: one parser for
+// the seven tags of the tune-cache file, the nearest-batch rule, the appended lines) - so that heap overflows,
+// use-after-free and undefined behaviour there abort the run.  With no GPU every HIP call fails and the error paths
+// are what runs; on a GPU box the same binary works on real (small) buffers.  argv[1]: the shipped tuning seed
+// (default: the source tree's).
 #include "model.h"
+#include "tune_table.h"
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -25,7 +30,131 @@ static spk_layer_desc conv(const char* name, const char* bn, int cin, int cout, 
   return d;
 }
 
-int main() {
+// ---- the tuner table ----
+// every non-comment line of a tune-cache file: its tag and its ints
+struct TuneLine { std::string text; int tag; std::vector<int> v; };
+static std::vector<TuneLine> read_tune_lines(const std::string& path) {
+  std::vector<TuneLine> out;
+  FILE* f = fopen(path.c_str(), "r");
+  char buf[1024];
+  while (f && fgets(buf, sizeof buf, f)) {
+    if (buf[0] == '#' || buf[0] == '\n') continue;
+    TuneLine l;
+    l.text = buf;
+    l.tag = -1;
+    std::istringstream in(l.text);
+    std::string tag;
+    in >> tag;
+    for (int t = 0; t < TUNE_NTAGS; ++t)
+      if (kTuneSchemas[t].tag && tag == kTuneSchemas[t].tag) l.tag = t;
+    for (int x; in >> x;) l.v.push_back(x);
+    out.push_back(l);
+  }
+  if (f) fclose(f);
+  return out;
+}
+// -1000: absent, else the (first) stored value
+static int look(TuneTag t, std::vector<int> key, int* second = nullptr) {
+  int v[2] = {0, 0};
+  if (!spk_tune_find(t, key.data(), v)) return -1000;
+  if (second) *second = v[1];
+  return v[0];
+}
+static void use_cache(const char* path) {   // what a fresh process with this SPK_TUNE_CACHE would see
+  if (path) setenv("SPK_TUNE_CACHE", path, 1);
+  else unsetenv("SPK_TUNE_CACHE");
+  spk_tune_reset_for_test();
+}
+
+static void tuner_table_checks(const std::string& tmp, const std::string& seed_path) {
+  const char* seed = seed_path.c_str();
+  // the path rule
+  unsetenv("SPK_TUNE_CACHE");
+  EXPECT(spk_tune_cache_path() == nullptr);
+  setenv("SPK_TUNE_CACHE", "", 1);
+  EXPECT(spk_tune_cache_path() == nullptr);
+  setenv("SPK_TUNE_CACHE", "off", 1);
+  EXPECT(spk_tune_cache_path() == nullptr);
+  setenv("SPK_TUNE_CACHE", "offline.txt", 1);
+  EXPECT(spk_tune_cache_path() && !strcmp(spk_tune_cache_path(), "offline.txt"));
+
+  // the nearest-batch rule, on entries that stay in the process (no file)
+  use_cache(nullptr);
+  const int a = 3, b = 7;
+  const int k64[] = {1, 14, 14, 256, 256, 64}, k256[] = {1, 14, 14, 256, 256, 256}, other[] = {1, 14, 14, 256, 512, 90};
+  spk_tune_store(TUNE_C3, k64, &a, true);
+  spk_tune_store(TUNE_C3, k256, &b, true);
+  spk_tune_store(TUNE_C3, other, &b, true);   // another problem between the two batches: never a match
+  EXPECT(look(TUNE_C3, {1, 14, 14, 256, 256, 64}) == a);
+  EXPECT(look(TUNE_C3, {1, 14, 14, 256, 256, 100}) == a);
+  EXPECT(look(TUNE_C3, {1, 14, 14, 256, 256, 128}) == b);    // a tie goes to the larger batch
+  EXPECT(look(TUNE_C3, {1, 14, 14, 256, 256, 512}) == b);
+  EXPECT(look(TUNE_C3, {1, 14, 14, 256, 256, 600}) == -1000);
+  EXPECT(look(TUNE_C3, {1, 14, 14, 256, 256, 31}) == -1000);
+  EXPECT(look(TUNE_C3, {1, 14, 14, 256, 128, 64}) == -1000);
+  const int cv[] = {4, 3}, ck[] = {0, 1, 1, 64, 14, 14, 256, 256, 3, 1, 16, 0, 0};   // conv: N is the 4th field
+  spk_tune_store(TUNE_CONV, ck, cv, true);
+  int dma = -1;
+  EXPECT(look(TUNE_CONV, {0, 1, 1, 100, 14, 14, 256, 256, 3, 1, 16, 0, 0}, &dma) == 4 && dma == 3);
+  EXPECT(look(TUNE_CONV, {0, 1, 1, 64, 14, 14, 256, 256, 3, 1, 16, 0, 1}) == -1000);
+  EXPECT(look(TUNE_CONV, {0, 1, 1, 64, 28, 14, 256, 256, 3, 1, 16, 0, 0}) == -1000);
+  const int one = 1, wk[] = {6272, 256, 256, 3, 1, 0, 13, 128128}, dk[] = {0, 64, 28, 28, 240, 5, 1};
+  spk_tune_store(TUNE_WGRAD, wk, &one, true);                  // no batch field: exact matches only
+  spk_tune_store(TUNE_DW, dk, &one, true);                     // (asked to persist: still never written)
+  EXPECT(look(TUNE_WGRAD, {6272, 256, 256, 3, 1, 0, 13, 128128}) == 1);
+  EXPECT(look(TUNE_WGRAD, {6273, 256, 256, 3, 1, 0, 13, 128128}) == -1000);
+  EXPECT(look(TUNE_WGRAD, {6272, 256, 256, 3, 1, 0, 13, 128129}) == -1000);
+  EXPECT(look(TUNE_DW, {0, 64, 28, 28, 240, 5, 1}) == 1);
+  EXPECT(look(TUNE_DW, {0, 65, 28, 28, 240, 5, 1}) == -1000);
+  EXPECT(look(TUNE_DW, {0, 64, 28, 28, 240, 5, 2}) == -1000);
+
+  // the shipped seed: loads whole, and writing every entry back through spk_tune_store gives the seed's own lines
+  std::vector<TuneLine> lines = read_tune_lines(seed);
+  EXPECT(lines.size() == 282);
+  use_cache(seed);
+  (void)look(TUNE_BNECK, {0, 0, 0});
+  EXPECT(spk_tune_detail::table().map.size() == lines.size());   // every line an entry, no key twice
+  remove(tmp.c_str());
+  setenv("SPK_TUNE_CACHE", tmp.c_str(), 1);                      // (the path is looked up when a line is appended)
+  bool tags[TUNE_NTAGS] = {};
+  for (const TuneLine& l : lines) {
+    EXPECT(l.tag >= 0);
+    if (l.tag < 0) continue;
+    tags[l.tag] = true;
+    const TuneSchema& sc = kTuneSchemas[l.tag];
+    EXPECT((int)l.v.size() == sc.n_key + sc.n_val);
+    int v[2] = {-1000, -1000};
+    EXPECT(spk_tune_find((TuneTag)l.tag, l.v.data(), v));
+    for (int i = 0; i < sc.n_val; ++i) EXPECT(v[i] == l.v[sc.n_key + i]);
+    spk_tune_store((TuneTag)l.tag, l.v.data(), v, true);
+  }
+  EXPECT(std::count(tags, tags + TUNE_NTAGS, true) == 6);
+  std::vector<TuneLine> back = read_tune_lines(tmp);
+  auto by_text = [](const TuneLine& x, const TuneLine& y) { return x.text < y.text; };
+  std::sort(lines.begin(), lines.end(), by_text);
+  std::sort(back.begin(), back.end(), by_text);
+  EXPECT(back.size() == lines.size());
+  for (size_t i = 0; i < lines.size() && i < back.size(); ++i) EXPECT(back[i].text == lines[i].text);
+
+  // one new entry per tag appended to that file, then a fresh table: each is found (and so is the seed's first line)
+  const std::vector<std::vector<int>> fresh = {
+      {2, 1, 0, 5, 9, 9, 64, 64, 3, 1, 16, 1, 0, 6, 5}, {1, 9, 9, 64, 64, 1, 0, 1, 5, -1}, {1, 9, 9, 64, 18, 18, 64, 128, 1, 2, 5, 17},
+      {2, 9, 9, 64, 64, 5, 13}, {9, 9, 64, 0, 64, 5, 0}, {9, 64, 5, 2}, {81, 64, 64, 3, 1, 0, 1, 64064, 1}};
+  for (int t = 0; t < (int)fresh.size(); ++t) spk_tune_store((TuneTag)t, fresh[t].data(), fresh[t].data() + kTuneSchemas[t].n_key, true);
+  spk_tune_store(TUNE_DW, dk, &one, true);
+  EXPECT(read_tune_lines(tmp).size() == lines.size() + fresh.size());   // (nothing for the depthwise choice)
+  use_cache(tmp.c_str());
+  for (int t = 0; t < (int)fresh.size(); ++t) {
+    int v[2] = {-1000, -1000};
+    EXPECT(spk_tune_find((TuneTag)t, fresh[t].data(), v));
+    for (int i = 0; i < kTuneSchemas[t].n_val; ++i) EXPECT(v[i] == fresh[t][kTuneSchemas[t].n_key + i]);
+  }
+  EXPECT(look(TUNE_DW, {0, 64, 28, 28, 240, 5, 1}) == -1000);
+  EXPECT(spk_tune_detail::table().map.size() == lines.size() + fresh.size());
+  remove(tmp.c_str());
+}
+
+int main(int argc, char** argv) {
   int ndev = 0;
   const bool gpu = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
   printf("asan_driver: %d GPU(s)\n", gpu ? ndev : 0);
@@ -77,20 +206,62 @@ int main() {
     spk_model_destroy(m);
   }
 
-  // ---- tuner-cache parsers: valid lines of all three kinds, garbage, over-long and truncated lines ----
+  // ---- the tuner table: the nearest-batch rule, the shipped seed and the appended lines, then a file with one valid
+  // line per tag, a value out of range per range-checked tag, truncated lines, garbage, a comment, over-long lines ----
   const std::string path = std::string(getenv("TMPDIR") ? getenv("TMPDIR") : "/tmp") + "/spk_asan_tune_cache.txt";
+  // the shipped seed: argv[1], else where it lies in the source tree as seen from this program (csrc/build/asan/)
+  std::string seed = argc > 1 ? argv[1] : std::string(argv[0]);
+  if (argc <= 1) seed = seed.substr(0, seed.find_last_of('/') + 1) + "../../../sykepic_hip/tune_seed_gfx950.txt";
+  tuner_table_checks(path + ".rt", seed);
+  std::string fixture;
   if (FILE* f = fopen(path.c_str(), "w")) {
     fprintf(f, "conv 0 1 1 256 14 14 256 256 3 1 16 0 0 4 3\n");
     fprintf(f, "pw1x1 2 14 14 256 1024 1 1 1 256 7\n");
+    fprintf(f, "pw2 1 14 14 256 28 28 512 1024 1 2 256 5\n");
     fprintf(f, "c3 1 14 14 256 256 256 2\n");
-    fprintf(f, "pw1x1 2 14 14 256 1024 1 1 1 256 99999\n");       // configuration id out of range: ignored
+    fprintf(f, "chain 14 14 256 0 256 64 0\n");
+    fprintf(f, "bneck 14 256 8 1\n");
+    fprintf(f, "wgrad 6272 256 256 3 1 0 13 128128 1\n");
+    fprintf(f, "pw1x1 2 14 14 256 2048 1 1 1 256 99999\n");       // values out of range: ignored
+    fprintf(f, "pw1x1 2 14 14 256 2048 1 1 1 256 -2\n");
+    fprintf(f, "pw2 1 14 14 256 28 28 512 2048 1 2 256 %d\n", kPwNumCfgs);
+    fprintf(f, "pw2 1 14 14 256 28 28 512 2048 1 2 256 -1\n");
+    fprintf(f, "c3 1 14 14 256 512 256 %d\n", kC3NumCfgs);
+    fprintf(f, "chain 14 14 256 0 512 64 2\n");
+    fprintf(f, "bneck 28 128 8 3\n");
     fprintf(f, "c3 1 14 14\n");                                    // truncated
-    fprintf(f, "conv x y z\n\n,,,,\n");
-    for (int i = 0; i < 3000; ++i) fputc('9', f);                  // longer than the parsers' line buffers
-    fprintf(f, "\nwgrad 1 2 3\n");
+    fprintf(f, "bneck 28 128 8\n");
+    fprintf(f, "bneck 28 128 8 1 1\n");                            // one field too many
+    fprintf(f, "chain 14 14 256 0 512 64 1x\n");                   // not an integer
+    fprintf(f, "wgrad 6272 256 512 3 1 0 13 128128 99999999999\n");
+    fprintf(f, "# bneck 28 128 8 2\n#bneck 28 128 8 2\n");         // comments
+    fprintf(f, "conv x y z\n\n,,,,\nbneck\nbneckx 28 128 8 2\n");
+    for (int i = 0; i < 3000; ++i) fputc('9', f);                  // longer than the parser's line buffer: dropped whole,
+    fprintf(f, "\n");
+    for (int i = 0; i < spk_tune_detail::kLineBuf - 1; ++i) fputc('9', f);
+    fprintf(f, "bneck 28 128 8 2\n");                              // even where its tail would read as an entry
+    fprintf(f, "wgrad 1 2 3\n");
+    fprintf(f, "c3 2 7 7 512 512 128 13");                         // the entry after it; no newline at the end of the file
     fclose(f);
+    for (const TuneLine& l : read_tune_lines(path)) fixture += l.text;
   }
-  setenv("SPK_TUNE_CACHE", path.c_str(), 1);
+  use_cache(path.c_str());
+  int dma = -1;
+  EXPECT(look(TUNE_CONV, {0, 1, 1, 256, 14, 14, 256, 256, 3, 1, 16, 0, 0}, &dma) == 4 && dma == 3);
+  EXPECT(look(TUNE_PW1, {2, 14, 14, 256, 1024, 1, 1, 1, 256}) == 7);
+  EXPECT(look(TUNE_PW2, {1, 14, 14, 256, 28, 28, 512, 1024, 1, 2, 256}) == 5);
+  EXPECT(look(TUNE_C3, {1, 14, 14, 256, 256, 256}) == 2);
+  EXPECT(look(TUNE_CHAIN, {14, 14, 256, 0, 256, 64}) == 0);
+  EXPECT(look(TUNE_BNECK, {14, 256, 8}) == 1);
+  EXPECT(look(TUNE_WGRAD, {6272, 256, 256, 3, 1, 0, 13, 128128}) == 1);
+  EXPECT(look(TUNE_C3, {2, 7, 7, 512, 512, 128}) == 13);
+  EXPECT(look(TUNE_PW1, {2, 14, 14, 256, 2048, 1, 1, 1, 256}) == -1000);
+  EXPECT(look(TUNE_PW2, {1, 14, 14, 256, 28, 28, 512, 2048, 1, 2, 256}) == -1000);
+  EXPECT(look(TUNE_C3, {1, 14, 14, 256, 512, 256}) == -1000);
+  EXPECT(look(TUNE_CHAIN, {14, 14, 256, 0, 512, 64}) == -1000);
+  EXPECT(look(TUNE_BNECK, {28, 128, 8}) == -1000);
+  EXPECT(look(TUNE_WGRAD, {6272, 256, 512, 3, 1, 0, 13, 128128}) == -1000);
+  EXPECT(spk_tune_detail::table().map.size() == 8);
   setenv("SPK_AUTOTUNE", "0", 1);
   // a problem that is NOT in the file (channels 128), on real buffers when there is a GPU
   const int n = 1, h = 8, wd = 8, cin = 128, cout = 128, M = n * h * wd;
@@ -115,19 +286,22 @@ int main() {
   q.x = x; q.wp = wp; q.y = y; q.scale = sb; q.shift = sb ? sb + cout : nullptr;
   q.N = n; q.H = h; q.W = wd; q.Ho = h; q.Wo = wd; q.stride = 1; q.Cin = cin; q.Cout = cout; q.M = M; q.relu = 1;
   q.dt = DT_F16; q.nb = 2; q.x_bytes = a.x_bytes; q.y_bytes = (unsigned)((size_t)M * cout * 2);
-  const int r1 = spk_conv1x1_launch(a, q, nullptr);               // loads the "pw1x1" lines, then the "conv" lines
+  const int r1 = spk_conv1x1_launch(a, q, nullptr);               // not tuned, no tuning: the implicit GEMM, nothing stored
   EXPECT(gpu ? r1 == 0 : r1 != 0);
   C3Args c;
   memset(&c, 0, sizeof c);
   c.x = x; c.wp = wp; c.y = y; c.scale = sb; c.shift = sb ? sb + 256 : nullptr;
   c.N = n; c.H = h; c.W = wd; c.Cin = cin; c.Cout = 256; c.M = M; c.relu = 1; c.dt = DT_F16; c.nb = 1;
   c.x_bytes = a.x_bytes; c.y_bytes = (unsigned)((size_t)M * 256 * 2); c.wp_bytes = (unsigned)((size_t)256 * 9 * cin * 2);
-  const int r3 = spk_conv3x3_launch(c, nullptr);                  // loads the "c3" lines
+  const int r3 = spk_conv3x3_launch(c, nullptr);                  // not tuned, no tuning: the first configuration that launches
   EXPECT(gpu ? r3 == 0 : r3 != 0);
   if (gpu) {
     (void)hipDeviceSynchronize();
     (void)hipFree(x); (void)hipFree(y); (void)hipFree(wp); (void)hipFree(sb);
   }
+  std::string after;                                              // without tuning nothing is appended
+  for (const TuneLine& l : read_tune_lines(path)) after += l.text;
+  EXPECT(!fixture.empty() && after == fixture);
   remove(path.c_str());
   printf("asan_driver: %s\n", g_fail ? "FAILED" : "ok");
   return g_fail ? 1 : 0;

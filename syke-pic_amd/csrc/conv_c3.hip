@@ -16,6 +16,7 @@
 // couts of one pixel).  MTW (7, 8 or 10 pixel tiles per wave) is tuned per problem: the tile count decides how evenly
 // the 256 CUs are filled (14x14 x batch 256: 448 tiles of 112 pixels = 1.75 rounds).
 #include "spk_common.h"
+#include "tune_table.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -269,7 +270,7 @@ int launch_c3(const C3Args& a, hipStream_t s) {
 }  // namespace
 
 // cfg: pixel tiles per wave x waves per pair
-int spk_c3_num_configs() { return 14; }
+int spk_c3_num_configs() { return kC3NumCfgs; }
 int spk_c3_launch(const C3Args& a, int cfg, hipStream_t s) {
   if (a.Cin % 64 || a.Cout % 64 || a.M <= 0 || a.dt != DT_F16) return -2;
   if ((size_t)a.M * a.Cout * 2 >= 0x80000000ull || (size_t)a.x_bytes >= 0x80000000ull) return -2;
@@ -303,85 +304,29 @@ int spk_launch_pack_c3(const float* w, bf16_t* out, int cout, int cin, int nb, h
 }
 
 // ---------------------------------------------------------------------------
-// Eval-path entry: tile configuration tuned once per problem and process (cached in SPK_TUNE_CACHE, "c3 ..." lines).
-// Every configuration sums in the same order (chunk -> tap -> half), so the choice never shows in the output; which
-// layers run here at all is a static rule of the caller (the sums differ from the implicit GEMM's tap-major order in
-// the last bits, so that choice must not depend on the batch).
+// Eval-path entry: tile configuration tuned once per problem ("c3" entries of the tuner table).  Every configuration
+// sums in the same order (chunk -> tap -> half), so the choice never shows in the output; which layers run here at all
+// is a static rule of the caller (the sums differ from the implicit GEMM's tap-major order in the last bits, so that
+// choice must not depend on the batch).
 // ---------------------------------------------------------------------------
-#include <map>
-#include <mutex>
-#include <tuple>
-namespace {
-typedef std::tuple<int, int, int, int, int, int> C3Key;   // nb H W Cin Cout N
-std::map<C3Key, int> g_c3_choice;
-std::mutex g_c3_mu;
-bool g_c3_loaded = false;
-const char* c3_cache_path() {
-  const char* e = getenv("SPK_TUNE_CACHE");
-  return e && *e && strcmp(e, "off") ? e : nullptr;
-}
-}  // namespace
-
 int spk_conv3x3_launch(const C3Args& a, hipStream_t s) {
-  const C3Key key(a.nb, a.H, a.W, a.Cin, a.Cout, a.N);
-  int choice = -2;
-  {
-    std::lock_guard<std::mutex> lk(g_c3_mu);
-    if (!g_c3_loaded) {
-      g_c3_loaded = true;
-      if (const char* path = c3_cache_path())
-        if (FILE* f = fopen(path, "r")) {
-          char line[256];
-          int v[7];
-          while (fgets(line, sizeof line, f))
-            if (sscanf(line, "c3 %d %d %d %d %d %d %d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6]) == 7 && v[6] >= -1 &&
-                v[6] < spk_c3_num_configs())
-              g_c3_choice[C3Key(v[0], v[1], v[2], v[3], v[4], v[5])] = v[6];
-          fclose(f);
-        }
-    }
-    auto it = g_c3_choice.find(key);
-    if (it != g_c3_choice.end()) choice = it->second;
-    else {
-      double best_ratio = 2.0 + 1e-9;   // nearest tuned batch within a factor of two
-      for (const auto& kv : g_c3_choice) {
-        C3Key k2 = kv.first;
-        const int n2 = std::get<5>(k2);
-        std::get<5>(k2) = a.N;
-        if (k2 != key) continue;
-        const double r = n2 > a.N ? (double)n2 / a.N : (double)a.N / n2;
-        if (r <= best_ratio) { best_ratio = r; choice = kv.second; }
-      }
-    }
-  }
-  const bool tune = !getenv("SPK_AUTOTUNE") || atoi(getenv("SPK_AUTOTUNE")) != 0;
-  if (choice == -2) {
+  const int key[] = {a.nb, a.H, a.W, a.Cin, a.Cout, a.N};
+  int choice;
+  if (!spk_tune_find(TUNE_C3, key, &choice)) {
+    const bool tune = spk_autotune_on();
     float best = 1e30f;
     choice = -1;
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1;
+    SpkLaunchTimer timer;
+    if (!timer.ok) return -1;
     for (int cfg = 0; cfg < spk_c3_num_configs(); ++cfg) {
       if (spk_c3_launch(a, cfg, s)) continue;
-      if (!tune) { choice = cfg; break; }
-      (void)hipEventRecord(e0, s);
-      for (int r = 0; r < 3; ++r) spk_c3_launch(a, cfg, s);
-      (void)hipEventRecord(e1, s);
-      if (hipEventSynchronize(e1) != hipSuccess) continue;
+      if (!tune) { choice = cfg; break; }   // no tuning: the first configuration that launches, for this process only
       float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, e0, e1);
+      if (!timer.time(s, 3, [&] { return spk_c3_launch(a, cfg, s); }, &ms)) continue;
       if (ms < best) { best = ms; choice = cfg; }
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    std::lock_guard<std::mutex> lk(g_c3_mu);
-    g_c3_choice[key] = choice;
-    if (tune)
-      if (const char* path = c3_cache_path())
-        if (FILE* f = fopen(path, "a")) {
-          fprintf(f, "c3 %d %d %d %d %d %d %d\n", a.nb, a.H, a.W, a.Cin, a.Cout, a.N, choice);
-          fclose(f);
-        }
-    if (getenv("SPK_TUNE_LOG"))
+    spk_tune_store(TUNE_C3, key, &choice, tune);
+    if (spk_tune_log())
       fprintf(stderr, "[spk tune 3x3] N%d %dx%d C%d->%d nb%d: cfg %d (%.1f us)\n", a.N, a.H, a.W, a.Cin, a.Cout, a.nb, choice,
               best * 1000.f / 3.f);
   }

@@ -19,6 +19,7 @@
 // of tiles, N-tiles of one M-tile adjacent, so the activation tile a block
 // streams is an L2 hit for its neighbour.
 #include "spk_common.h"
+#include "tune_table.h"
 
 namespace {
 
@@ -848,90 +849,12 @@ static int launch_with(const ConvArgs& a, int mode, int cfg, hipStream_t s, int*
 }
 
 // ---------------------------------------------------------------------------
-// Per-problem autotuning (tile config x main-loop flavour), cached per process.
-// The winner differs by layer (measured on ResNet-50, batch 256: 128x128
-// register-staged for the HBM-bound stage-1 layers, 256x256 / 256x128 LDS-DMA
-// for the deep 3x3 and 1x1 layers), so each distinct problem is timed once on
-// first use.  SPK_AUTOTUNE=0 pins the static heuristic.  Every candidate
-// accumulates each output element in the same K order, so results do not
+// Per-problem autotuning (tile config x main-loop flavour), "conv" entries of the tuner table.  The winner differs by
+// layer (measured on ResNet-50, batch 256: 128x128 register-staged for the HBM-bound stage-1 layers, 256x256 / 256x128
+// LDS-DMA for the deep 3x3 and 1x1 layers), so each distinct problem is timed once on first use.  SPK_AUTOTUNE=0 pins
+// the static heuristic.  Every candidate accumulates each output element in the same K order, so results do not
 // depend on the choice (only the grouping of the BN partial sums does).
 // ---------------------------------------------------------------------------
-#include <map>
-#include <mutex>
-#include <tuple>
-namespace {
-// problem without the batch size N; winners are kept per N underneath it
-typedef std::tuple<int, int, int, int, int, int, int, int, int, int, int, int> TuneKey;
-typedef std::map<int, std::pair<int, int>> ByBatch;   // N -> (tile config, main-loop flavour)
-std::map<TuneKey, ByBatch> g_tuned;
-std::mutex g_tune_mu;   // the maps are process-wide; handles may be driven from several host threads
-bool g_cache_loaded = false;
-
-bool autotune_on() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("SPK_AUTOTUNE");
-    v = e ? atoi(e) != 0 : 1;
-  }
-  return v != 0;
-}
-
-// SPK_TUNE_CACHE=<file>: winners persist across processes (one text line per problem, appended when a problem
-// is tuned).  Ranks of a data-parallel job and re-runs then pick the same configurations, the first call of a
-// process does not pay the tuning, and a rocprofv3 kernel trace of a warm run holds steady-state launches only.
-const char* cache_path() {
-  const char* e = getenv("SPK_TUNE_CACHE");
-  return e && *e ? e : nullptr;
-}
-
-void cache_load_locked() {
-  if (g_cache_loaded) return;
-  g_cache_loaded = true;
-  const char* path = cache_path();
-  if (!path) return;
-  FILE* f = fopen(path, "r");
-  if (!f) return;
-  char line[512];
-  while (fgets(line, sizeof line, f)) {
-    int v[15];
-    if (sscanf(line, "conv %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6],
-               &v[7], &v[8], &v[9], &v[10], &v[11], &v[12], &v[13], &v[14]) == 15) {
-      const TuneKey key(v[0], v[1], v[2], v[4], v[5], v[6], v[7], v[8], v[9], v[10], v[11], v[12]);
-      g_tuned[key][v[3]] = {v[13], v[14]};
-    }
-  }
-  fclose(f);
-}
-
-void cache_append(const TuneKey& k, int n, const std::pair<int, int>& win) {
-  const char* path = cache_path();
-  if (!path) return;
-  FILE* f = fopen(path, "a");
-  if (!f) return;
-  fprintf(f, "conv %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d\n", std::get<0>(k), std::get<1>(k), std::get<2>(k), n,
-          std::get<3>(k), std::get<4>(k), std::get<5>(k), std::get<6>(k), std::get<7>(k), std::get<8>(k), std::get<9>(k),
-          std::get<10>(k), std::get<11>(k), win.first, win.second);
-  fclose(f);
-}
-
-// The winner for batch size n: the exact entry, else the entry of the nearest tuned batch size within a factor of
-// two (a ragged tail batch of `sykepic prob` re-uses the full batch's choice instead of re-timing ~40 candidates
-// for each of the 53 convolutions; every candidate is correct for every M, the choice only affects speed).
-const std::pair<int, int>* find_tuned_locked(const TuneKey& key, int n) {
-  auto it = g_tuned.find(key);
-  if (it == g_tuned.end() || it->second.empty()) return nullptr;
-  const ByBatch& by = it->second;
-  auto ex = by.find(n);
-  if (ex != by.end()) return &ex->second;
-  const std::pair<int, int>* best = nullptr;
-  double best_ratio = 2.0 + 1e-9;
-  for (const auto& kv : by) {
-    const double r = kv.first > n ? (double)kv.first / n : (double)n / kv.first;
-    if (r <= best_ratio) { best_ratio = r; best = &kv.second; }
-  }
-  return best;
-}
-}  // namespace
 
 // Test-hook pin (spk_op_conv_pin): one (tile config, main-loop flavour) for every implicit-GEMM launch of the process
 // and one pipeline depth for the weight gradient; -1 = not pinned.  Process-wide, like the tuner's tables.
@@ -965,7 +888,7 @@ int spk_conv_launch(const ConvArgs& a_in, int mode, hipStream_t s, int* m_tiles_
     a.dma = g_pin_dma.load();
     return launch_with(a, mode, pin_cfg, s, m_tiles_out);
   }
-  if (env_cfg() >= 0 || !autotune_on() || a.cfg >= 0) {
+  if (env_cfg() >= 0 || !spk_autotune_on() || a.cfg >= 0) {
     const int cfg = a.cfg >= 0 ? a.cfg : (env_cfg() >= 0 ? env_cfg() : pick_cfg(a.M, a.Cout));
     if (a.dma < 0 && getenv("SPK_CONV_DMA")) a.dma = atoi(getenv("SPK_CONV_DMA"));  // flavour 0..4
     if (mode == CONV_MODE_GENERIC && a.pool_y) a.dma = 0;   // gated operand: one flavour
@@ -975,16 +898,10 @@ int spk_conv_launch(const ConvArgs& a_in, int mode, hipStream_t s, int* m_tiles_
     return launch_with(a, mode, cfg, s, m_tiles_out);
   }
   const int pad_cls = a.pad * 16 + (a.cls_ph >= 0 ? 1 + a.cls_ph * 2 + a.cls_pw : 0);
-  const TuneKey key(mode, a.dt, a.splitw, a.H, a.W, a.Cin, a.Cout, a.kh, a.stride, pad_cls,
-                    a.stats != nullptr, (a.res != nullptr && (const void*)a.res != (const void*)a.y) + 2 * (a.cin_s > 0) + 4 * (a.cout_s > 0) + 8 * (mode == CONV_MODE_GENERIC && a.pool_y != nullptr));
-  std::pair<int, int> chosen;
-  bool have = false;
-  {
-    std::lock_guard<std::mutex> lk(g_tune_mu);
-    cache_load_locked();
-    if (const std::pair<int, int>* w = find_tuned_locked(key, a.N)) { chosen = *w; have = true; }
-  }
-  if (!have) {
+  const int key[] = {mode, a.dt, a.splitw, a.N, a.H, a.W, a.Cin, a.Cout, a.kh, a.stride, pad_cls, a.stats != nullptr,
+                     (a.res != nullptr && (const void*)a.res != (const void*)a.y) + 2 * (a.cin_s > 0) + 4 * (a.cout_s > 0) + 8 * (mode == CONV_MODE_GENERIC && a.pool_y != nullptr)};
+  int win[2];   // tile config, main-loop flavour
+  if (!spk_tune_find(TUNE_CONV, key, win)) {
     // in-place accumulation (dgrad into an existing gradient): re-running it would add twice, so the candidates
     // write to a scratch tensor and read the real one as their shortcut operand - same traffic, nothing clobbered
     bf16_t* scratch = nullptr;
@@ -995,13 +912,14 @@ int spk_conv_launch(const ConvArgs& a_in, int mode, hipStream_t s, int* m_tiles_
         return launch_with(a, mode, pick_cfg(a.M, a.Cout), s, m_tiles_out);
       a.y = scratch;
     }
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+    SpkLaunchTimer timer;
+    if (!timer.ok) {
       if (scratch) (void)hipFree(scratch);
       return -1;
     }
     float best = 1e30f;
-    std::pair<int, int> win(pick_cfg(a.M, a.Cout), 0);
+    win[0] = pick_cfg(a.M, a.Cout);
+    win[1] = 0;
     const int cands[] = {0, 1, 2, 3, 4, 5, 6};
     for (int cfg : cands) {
       const int bn = cfg == 5 ? 256 : ((cfg == 0 || cfg == 4) ? 128 : 64);
@@ -1017,36 +935,24 @@ int spk_conv_launch(const ConvArgs& a_in, int mode, hipStream_t s, int* m_tiles_
         if (dma == 2) continue;  // 5: LDS-DMA 2-stage, 32-deep K steps; 6: LDS-DMA 1 stage
         a.dma = dma;
         if (launch_with(a, mode, cfg, s, nullptr)) continue;  // warm-up
-        (void)hipEventRecord(e0, s);
-        for (int r = 0; r < 3; ++r) launch_with(a, mode, cfg, s, nullptr);
-        (void)hipEventRecord(e1, s);
-        if (hipEventSynchronize(e1) != hipSuccess) continue;
         float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        if (getenv("SPK_TUNE_LOG") && atoi(getenv("SPK_TUNE_LOG")) > 1)
+        if (!timer.time(s, 3, [&] { return launch_with(a, mode, cfg, s, nullptr); }, &ms)) continue;
+        if (spk_tune_log() > 1)
           fprintf(stderr, "[spk cand] %dx%d C%d->%d k%d s%d sw%d: cfg %d dma %d %.1f us\n", a.H, a.W, a.Cin, a.Cout,
                   a.kh, a.stride, a.splitw, cfg, dma, ms * 1000.f / 3.f);
-        if (ms < best) { best = ms; win = {cfg, dma}; }
+        if (ms < best) { best = ms; win[0] = cfg; win[1] = dma; }
       }
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     if (scratch) {
       (void)hipStreamSynchronize(s);
       (void)hipFree(scratch);
       a.y = real_y;
     }
-    {
-      std::lock_guard<std::mutex> lk(g_tune_mu);
-      g_tuned[key][a.N] = win;
-      cache_append(key, a.N, win);
-    }
-    chosen = win;
-    if (getenv("SPK_TUNE_LOG"))
+    spk_tune_store(TUNE_CONV, key, win, true);
+    if (spk_tune_log())
       fprintf(stderr, "[spk tune] mode %d dt %d sw %d N%d %dx%d C%d->%d k%d s%d: cfg %d dma %d (%.1f us)\n", mode,
-              a.dt, a.splitw, a.N, a.H, a.W, a.Cin, a.Cout, a.kh, a.stride, win.first, win.second,
-              best * 1000.f / 3.f);
+              a.dt, a.splitw, a.N, a.H, a.W, a.Cin, a.Cout, a.kh, a.stride, win[0], win[1], best * 1000.f / 3.f);
   }
-  a.dma = chosen.second;
-  return launch_with(a, mode, chosen.first, s, m_tiles_out);
+  a.dma = win[1];
+  return launch_with(a, mode, win[0], s, m_tiles_out);
 }

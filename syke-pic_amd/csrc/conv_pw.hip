@@ -24,6 +24,7 @@
 //    MFMAs of the others.  RING flavour (deep K): classic K-outer loop, weights register-staged through a 2-stage LDS
 //    ring, one barrier per 32-deep K step.
 #include "spk_common.h"
+#include "tune_table.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -569,7 +570,7 @@ int launch_res(const PwConvArgs& a, hipStream_t s) {
 }
 
 // candidate table (index = cfg id).  BN = 32*NPAIR couts, BM = WAVES*MT*16 pixels.
-constexpr int kNumCfgs = 18;   // 12-17: the LDS-ring kernel of the deep layers (conv_pwr.hip)
+constexpr int kNumCfgs = kPwNumCfgs;   // 12-17: the LDS-ring kernel of the deep layers (conv_pwr.hip)
 template <int DT, int NB>
 int launch_cfg(const PwConvArgs& a, int cfg, hipStream_t s) {
   switch (cfg) {
@@ -640,42 +641,13 @@ int spk_launch_pack_pw(const float* w, const float* scale, bf16_t* out, int cout
 
 // ---------------------------------------------------------------------------
 // Eval-path entry: one 1x1 convolution, by whichever kernel is faster for this problem on this machine - the
-// implicit-GEMM kernel (its own best tile x flavour) or one of the configurations above.  Timed once per process
-// and problem like the conv tuner, winners persisted in the same SPK_TUNE_CACHE file ("pw1x1 ..." lines).  The two
-// kernels give bit-identical outputs (same accumulation order, same fp32 epilogue).  The candidates are timed
-// back to back on one problem, i.e. with a warmer cache than inside a forward pass, and the kernel here is the more
-// latency-sensitive of the two (measured per layer inside the network it ran 15-25 % over its isolated time on the
-// 14x14 / 7x7 layers, the implicit GEMM did not): it has to win by 8 % to be chosen.
+// implicit-GEMM kernel (its own best tile x flavour) or one of the configurations above ("pw1x1" entries of the tuner
+// table).  The two kernels give bit-identical outputs (same accumulation order, same fp32 epilogue).  The candidates
+// are timed back to back on one problem, i.e. with a warmer cache than inside a forward pass, and the kernel here is
+// the more latency-sensitive of the two (measured per layer inside the network it ran 15-25 % over its isolated time
+// on the 14x14 / 7x7 layers, the implicit GEMM did not): it has to win by 8 % to be chosen.
 // ---------------------------------------------------------------------------
-#include <map>
-#include <mutex>
-#include <tuple>
 namespace {
-typedef std::tuple<int, int, int, int, int, int, int, int, int> Pw1Key;   // nb H W Cin Cout stride res relu N
-std::map<Pw1Key, int> g_pw_choice;   // -1: implicit GEMM, else configuration id
-std::mutex g_pw_mu;
-bool g_pw_loaded = false;
-
-const char* pw_cache_path() {
-  const char* e = getenv("SPK_TUNE_CACHE");
-  return e && *e && strcmp(e, "off") ? e : nullptr;
-}
-void pw_cache_load_locked() {
-  if (g_pw_loaded) return;
-  g_pw_loaded = true;
-  const char* path = pw_cache_path();
-  if (!path) return;
-  FILE* f = fopen(path, "r");
-  if (!f) return;
-  char line[512];
-  while (fgets(line, sizeof line, f)) {
-    int v[10];
-    if (sscanf(line, "pw1x1 %d %d %d %d %d %d %d %d %d %d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8],
-               &v[9]) == 10 && v[9] >= -1 && v[9] < kNumCfgs)
-      g_pw_choice[Pw1Key(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8])] = v[9];
-  }
-  fclose(f);
-}
 // SPK_PW: 1 (default) each problem runs on the faster of the two kernels; 2: always conv_pw (its best tile
 // configuration); 0: never.  The choice never shows in the output: every configuration of this kernel and the
 // implicit GEMM accumulate in the same order and share the fp32 epilogue - bit-identical results, asserted by
@@ -691,45 +663,20 @@ int pw_mode() {
 }  // namespace
 
 int spk_conv1x1_launch(const ConvArgs& a, const PwConvArgs& q, hipStream_t s) {
-  const bool tune = !getenv("SPK_AUTOTUNE") || atoi(getenv("SPK_AUTOTUNE")) != 0;
   if (pw_mode() == 0 || a.Cin % 64 || a.Cout % 64 || q.dt != DT_F16) return spk_conv_launch(a, CONV_MODE_GENERIC, s, nullptr);
-  const Pw1Key key(q.nb, q.H, q.W, q.Cin, q.Cout, q.stride, q.res != nullptr, q.relu, q.N);
-  int choice = -2;
-  {
-    std::lock_guard<std::mutex> lk(g_pw_mu);
-    pw_cache_load_locked();
-    auto it = g_pw_choice.find(key);
-    if (it != g_pw_choice.end()) choice = it->second;
-    else {
-      // a ragged tail batch re-uses the choice of the nearest tuned batch within a factor of two
-      double best_ratio = 2.0 + 1e-9;
-      for (const auto& kv : g_pw_choice) {
-        Pw1Key k2 = kv.first;
-        const int n2 = std::get<8>(k2);
-        std::get<8>(k2) = q.N;
-        if (k2 != key) continue;
-        const double r = n2 > q.N ? (double)n2 / q.N : (double)q.N / n2;
-        if (r <= best_ratio) { best_ratio = r; choice = kv.second; }
-      }
-    }
-  }
-  if (choice == -2 && !tune) choice = -1;
-  if (choice == -2) {
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1;
+  const int key[] = {q.nb, q.H, q.W, q.Cin, q.Cout, q.stride, q.res != nullptr, q.relu, q.N};
+  int choice = -1;   // -1: implicit GEMM (also what an untuned problem runs on without tuning), else configuration id
+  if (!spk_tune_find(TUNE_PW1, key, &choice) && spk_autotune_on()) {
+    SpkLaunchTimer timer;
+    if (!timer.ok) return -1;
     float best = 1e30f, t_igemm = 1e30f, t_pw = 1e30f;
     int best_pw = -1;
-    choice = -1;
     for (int cfg = (pw_mode() == 2 ? 0 : -1); cfg < kNumCfgs; ++cfg) {
       auto run = [&]() { return cfg < 0 ? spk_conv_launch(a, CONV_MODE_GENERIC, s, nullptr) : spk_pw_launch(q, cfg, s); };
       if (run()) continue;  // warm-up (and the implicit GEMM's own tuning); -3: configuration does not fit
-      (void)hipEventRecord(e0, s);
-      for (int r = 0; r < 3; ++r) run();
-      (void)hipEventRecord(e1, s);
-      if (hipEventSynchronize(e1) != hipSuccess) continue;
       float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, e0, e1);
-      if (getenv("SPK_TUNE_LOG") && atoi(getenv("SPK_TUNE_LOG")) > 1)
+      if (!timer.time(s, 3, run, &ms)) continue;
+      if (spk_tune_log() > 1)
         fprintf(stderr, "[spk pw cand] %dx%d C%d->%d s%d nb%d res%d: %s %d %.1f us\n", q.H, q.W, q.Cin, q.Cout, q.stride,
                 q.nb, q.res != nullptr, cfg < 0 ? "igemm" : "pw", cfg, ms * 1000.f / 3.f);
       if (cfg < 0) t_igemm = ms;
@@ -737,20 +684,8 @@ int spk_conv1x1_launch(const ConvArgs& a, const PwConvArgs& q, hipStream_t s) {
     }
     if (best_pw >= 0 && t_pw < 0.92f * t_igemm) { choice = best_pw; best = t_pw; }
     else { choice = -1; best = t_igemm; }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    {
-      std::lock_guard<std::mutex> lk(g_pw_mu);
-      g_pw_choice[key] = choice;
-      if (const char* path = pw_cache_path()) {
-        if (FILE* f = fopen(path, "a")) {
-          fprintf(f, "pw1x1 %d %d %d %d %d %d %d %d %d %d\n", q.nb, q.H, q.W, q.Cin, q.Cout, q.stride, q.res != nullptr,
-                  q.relu, q.N, choice);
-          fclose(f);
-        }
-      }
-    }
-    if (getenv("SPK_TUNE_LOG"))
+    spk_tune_store(TUNE_PW1, key, &choice, true);
+    if (spk_tune_log())
       fprintf(stderr, "[spk tune 1x1] N%d %dx%d C%d->%d s%d nb%d res%d: %s %d (%.1f us)\n", q.N, q.H, q.W, q.Cin, q.Cout,
               q.stride, q.nb, q.res != nullptr, choice < 0 ? "igemm" : "pw", choice, best * 1000.f / 3.f);
   }
@@ -764,87 +699,34 @@ int spk_conv1x1_launch(const ConvArgs& a, const PwConvArgs& q, hipStream_t s) {
 }
 
 // The dual-source conv (block-closing 1x1 conv + 1x1 shortcut conv as one K-concatenated GEMM): conv_pw configurations
-// only (the implicit GEMM has no second source); the fastest is timed once per problem and persisted.
-namespace {
-typedef std::tuple<int, int, int, int, int, int, int, int, int, int, int> Pw2Key;  // nb H W Cin H2 W2 Cin2 Cout s s2 N
-std::map<Pw2Key, int> g_pw2_choice;
-bool g_pw2_loaded = false;
-}  // namespace
-
+// only (the implicit GEMM has no second source); the fastest is timed once per problem ("pw2" entries).
 int spk_conv1x1_dual_launch(const PwConvArgs& q, hipStream_t s) {
   if (!q.x2 || q.dt != DT_F16) return -3;
-  const bool tune = !getenv("SPK_AUTOTUNE") || atoi(getenv("SPK_AUTOTUNE")) != 0;
-  const Pw2Key key(q.nb, q.H, q.W, q.Cin, q.H2, q.W2, q.Cin2, q.Cout, q.stride, q.stride2, q.N);
-  int choice = -2;
-  {
-    std::lock_guard<std::mutex> lk(g_pw_mu);
-    if (!g_pw2_loaded) {
-      g_pw2_loaded = true;
-      if (const char* path = pw_cache_path())
-        if (FILE* f = fopen(path, "r")) {
-          char line[512];
-          while (fgets(line, sizeof line, f)) {
-            int v[12];
-            if (sscanf(line, "pw2 %d %d %d %d %d %d %d %d %d %d %d %d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7],
-                       &v[8], &v[9], &v[10], &v[11]) == 12 && v[11] >= 0 && v[11] < kNumCfgs)
-              g_pw2_choice[Pw2Key(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9], v[10])] = v[11];
-          }
-          fclose(f);
-        }
-    }
-    auto it = g_pw2_choice.find(key);
-    if (it != g_pw2_choice.end()) choice = it->second;
-    else {
-      double best_ratio = 2.0 + 1e-9;   // a ragged tail batch re-uses the nearest tuned batch within a factor of two
-      for (const auto& kv : g_pw2_choice) {
-        Pw2Key k2 = kv.first;
-        const int n2 = std::get<10>(k2);
-        std::get<10>(k2) = q.N;
-        if (k2 != key) continue;
-        const double r = n2 > q.N ? (double)n2 / q.N : (double)q.N / n2;
-        if (r <= best_ratio) { best_ratio = r; choice = kv.second; }
-      }
-    }
-  }
-  if (choice == -2 && !tune) {
+  const int key[] = {q.nb, q.H, q.W, q.Cin, q.H2, q.W2, q.Cin2, q.Cout, q.stride, q.stride2, q.N};
+  int choice;
+  if (spk_tune_find(TUNE_PW2, key, &choice)) return spk_pw_launch(q, choice, s);
+  if (!spk_autotune_on()) {
     for (int cfg : {5, 1, 0, 3, 4})   // no tuning: the first ring configuration that fits
       if (spk_pw_launch(q, cfg, s) == 0) return 0;
     return -3;
   }
-  if (choice == -2) {
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1;
-    float best = 1e30f;
-    choice = -1;
-    for (int cfg = 0; cfg < kNumCfgs; ++cfg) {
-      if (spk_pw_launch(q, cfg, s)) continue;
-      (void)hipEventRecord(e0, s);
-      for (int r = 0; r < 3; ++r) spk_pw_launch(q, cfg, s);
-      (void)hipEventRecord(e1, s);
-      if (hipEventSynchronize(e1) != hipSuccess) continue;
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, e0, e1);
-      if (getenv("SPK_TUNE_LOG") && atoi(getenv("SPK_TUNE_LOG")) > 1)
-        fprintf(stderr, "[spk pw2 cand] %dx%d C%d+%d->%d nb%d: pw %d %.1f us\n", q.Ho, q.Wo, q.Cin, q.Cin2, q.Cout, q.nb, cfg,
-                ms * 1000.f / 3.f);
-      if (ms < best) { best = ms; choice = cfg; }
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (choice < 0) return -3;
-    {
-      std::lock_guard<std::mutex> lk(g_pw_mu);
-      g_pw2_choice[key] = choice;
-      if (const char* path = pw_cache_path())
-        if (FILE* f = fopen(path, "a")) {
-          fprintf(f, "pw2 %d %d %d %d %d %d %d %d %d %d %d %d\n", q.nb, q.H, q.W, q.Cin, q.H2, q.W2, q.Cin2, q.Cout, q.stride,
-                  q.stride2, q.N, choice);
-          fclose(f);
-        }
-    }
-    if (getenv("SPK_TUNE_LOG"))
-      fprintf(stderr, "[spk tune 1x1 dual] N%d %dx%d C%d+%d->%d nb%d: pw %d (%.1f us)\n", q.N, q.Ho, q.Wo, q.Cin, q.Cin2,
-              q.Cout, q.nb, choice, best * 1000.f / 3.f);
+  SpkLaunchTimer timer;
+  if (!timer.ok) return -1;
+  float best = 1e30f;
+  choice = -1;
+  for (int cfg = 0; cfg < kNumCfgs; ++cfg) {
+    if (spk_pw_launch(q, cfg, s)) continue;
+    float ms = 0.f;
+    if (!timer.time(s, 3, [&] { return spk_pw_launch(q, cfg, s); }, &ms)) continue;
+    if (spk_tune_log() > 1)
+      fprintf(stderr, "[spk pw2 cand] %dx%d C%d+%d->%d nb%d: pw %d %.1f us\n", q.Ho, q.Wo, q.Cin, q.Cin2, q.Cout, q.nb, cfg,
+              ms * 1000.f / 3.f);
+    if (ms < best) { best = ms; choice = cfg; }
   }
+  if (choice < 0) return -3;   // nothing fits: nothing remembered
+  spk_tune_store(TUNE_PW2, key, &choice, true);
+  if (spk_tune_log())
+    fprintf(stderr, "[spk tune 1x1 dual] N%d %dx%d C%d+%d->%d nb%d: pw %d (%.1f us)\n", q.N, q.Ho, q.Wo, q.Cin, q.Cin2,
+            q.Cout, q.nb, choice, best * 1000.f / 3.f);
   return spk_pw_launch(q, choice, s);
 }

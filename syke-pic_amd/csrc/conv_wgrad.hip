@@ -17,12 +17,10 @@
 // slab and a second kernel adds the slabs in a fixed order (reproducible, no
 // atomics).
 #include "spk_common.h"
+#include "tune_table.h"
 
 #include <cstdio>
 #include <cstdlib>
-#include <map>
-#include <mutex>
-#include <tuple>
 
 struct WgradArgs {
   const bf16_t* x;
@@ -248,77 +246,33 @@ int launch_nb(const WgradArgs& a, int splits, hipStream_t s) {
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// one- vs two-stage: timed once per problem (both give bit-identical slabs); process-wide table behind a mutex,
-// persisted in SPK_TUNE_CACHE like the conv tile choices (conv_igemm.hip)
-typedef std::tuple<int, int, int, int, int, int, int, int> WgKey;
-std::map<WgKey, int> g_wg_tuned;
-std::mutex g_wg_mu;
-bool g_wg_loaded = false;
-
-void wg_cache_load_locked() {
-  if (g_wg_loaded) return;
-  g_wg_loaded = true;
-  const char* path = getenv("SPK_TUNE_CACHE");
-  if (!path || !*path) return;
-  FILE* f = fopen(path, "r");
-  if (!f) return;
-  char line[512];
-  while (fgets(line, sizeof line, f)) {
-    int v[9];
-    if (sscanf(line, "wgrad %d %d %d %d %d %d %d %d %d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8]) == 9)
-      g_wg_tuned[WgKey(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7])] = v[8];
-  }
-  fclose(f);
-}
-
+// one- vs two-stage: timed once per problem (both give bit-identical slabs), "wgrad" entries of the tuner table.  Two
+// timed repetitions, the two-stage pipeline first; remembered (as two stages) even if nothing could be timed, and
+// not subject to SPK_AUTOTUNE.
 template <int BCO, int BCI, bool STEM>
 int launch(const WgradArgs& a, int splits, hipStream_t s) {
   static const int forced = getenv("SPK_WGRAD_NBUF") ? atoi(getenv("SPK_WGRAD_NBUF")) : 0;
-  const int pinned = spk_conv_pinned_wgrad_nbuf();   // test hook: no tuner, no tune cache
+  const int pinned = spk_conv_pinned_wgrad_nbuf();   // test hook: no tuner, no tuner table
   int nbuf = pinned == 1 || pinned == 2 ? pinned : forced;
   if (nbuf != 1 && nbuf != 2) {
-    const WgKey key(a.M, a.Cin, a.Cout, a.kh, a.stride, (int)STEM, splits, BCO * 1000 + BCI);
-    bool have = false;
-    {
-      std::lock_guard<std::mutex> lk(g_wg_mu);
-      wg_cache_load_locked();
-      auto it = g_wg_tuned.find(key);
-      if (it != g_wg_tuned.end()) { nbuf = it->second; have = true; }
-    }
-    if (!have) {
-      hipEvent_t e0, e1;
-      int best = 2;
-      if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
+    const int key[] = {a.M, a.Cin, a.Cout, a.kh, a.stride, (int)STEM, splits, BCO * 1000 + BCI};
+    if (!spk_tune_find(TUNE_WGRAD, key, &nbuf)) {
+      nbuf = 2;
+      auto run = [&](int nb) { return nb == 2 ? launch_nb<BCO, BCI, STEM, 2>(a, splits, s) : launch_nb<BCO, BCI, STEM, 1>(a, splits, s); };
+      SpkLaunchTimer timer;
+      if (timer.ok) {
         float tbest = 1e30f;
         for (int nb = 2; nb >= 1; --nb) {
-          if (nb == 2 ? launch_nb<BCO, BCI, STEM, 2>(a, splits, s) : launch_nb<BCO, BCI, STEM, 1>(a, splits, s)) continue;
-          (void)hipEventRecord(e0, s);
-          for (int r = 0; r < 2; ++r)
-            nb == 2 ? launch_nb<BCO, BCI, STEM, 2>(a, splits, s) : launch_nb<BCO, BCI, STEM, 1>(a, splits, s);
-          (void)hipEventRecord(e1, s);
+          if (run(nb)) continue;
           float ms = 1e30f;
-          if (hipEventSynchronize(e1) == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
-          if (ms < tbest) { tbest = ms; best = nb; }
+          if (!timer.time(s, 2, [&] { return run(nb); }, &ms)) ms = 1e30f;
+          if (ms < tbest) { tbest = ms; nbuf = nb; }
         }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        if (getenv("SPK_TUNE_LOG"))
+        if (spk_tune_log())
           fprintf(stderr, "[spk tune] wgrad M%d C%d->%d k%d s%d: %d stage(s) (%.1f us)\n", a.M, a.Cin, a.Cout, a.kh,
-                  a.stride, best, tbest * 500.f);
+                  a.stride, nbuf, tbest * 500.f);
       }
-      {
-        std::lock_guard<std::mutex> lk(g_wg_mu);
-        g_wg_tuned[key] = best;
-        const char* path = getenv("SPK_TUNE_CACHE");
-        if (path && *path) {
-          if (FILE* f = fopen(path, "a")) {
-            fprintf(f, "wgrad %d %d %d %d %d %d %d %d %d\n", a.M, a.Cin, a.Cout, a.kh, a.stride, (int)STEM, splits,
-                    BCO * 1000 + BCI, best);
-            fclose(f);
-          }
-        }
-      }
-      nbuf = best;
+      spk_tune_store(TUNE_WGRAD, key, &nbuf, true);
     }
   }
   return nbuf == 1 ? launch_nb<BCO, BCI, STEM, 1>(a, splits, s) : launch_nb<BCO, BCI, STEM, 2>(a, splits, s);

@@ -4,6 +4,7 @@
 #include "../../include/sykepic_hip.h"
 #include "spk_common.h"
 #include "model.h"
+#include "tune_table.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1061,85 +1062,34 @@ static bool chain_possible(const spk_model* m, const Layer& L) {
   return true;
 }
 
-// chained kernel or two kernels?  Timed once per problem (both give the same bits), "chain ..." lines of SPK_TUNE_CACHE
-#include <map>
-#include <mutex>
-#include <tuple>
-typedef std::tuple<int, int, int, int, int, int> ChainKey;   // H W Cin Cin2 Coutz N
-static std::map<ChainKey, int> g_chain_choice;
-static std::mutex g_chain_mu;
-static bool g_chain_loaded = false;
-
 static int run_conv_eval(spk_model* m, Layer& L, int nb);
 
+// chained kernel (1) or two kernels (0)?  Timed once per problem (both give the same bits), "chain" entries of the tuner
+// table; without tuning the chained kernel, not remembered
 static int chain_choice(spk_model* m, Layer& L, const PwConvArgs& q, int nb) {
   if (m->chain >= 2) return 1;
-  const ChainKey key(q.H, q.W, q.Cin, q.x2 ? q.Cin2 : 0, q.Coutz, q.N);
-  const char* path = getenv("SPK_TUNE_CACHE");
-  if (path && (!*path || !strcmp(path, "off"))) path = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(g_chain_mu);
-    if (!g_chain_loaded) {
-      g_chain_loaded = true;
-      if (path)
-        if (FILE* f = fopen(path, "r")) {
-          char line[256];
-          int v[7];
-          while (fgets(line, sizeof line, f))
-            if (sscanf(line, "chain %d %d %d %d %d %d %d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6]) == 7 && (v[6] == 0 || v[6] == 1))
-              g_chain_choice[ChainKey(v[0], v[1], v[2], v[3], v[4], v[5])] = v[6];
-          fclose(f);
-        }
-    }
-    auto it = g_chain_choice.find(key);
-    if (it != g_chain_choice.end()) return it->second;
-    for (const auto& kv : g_chain_choice) {   // a ragged tail batch: the choice of a tuned batch within a factor of two
-      ChainKey k2 = kv.first;
-      const int n2 = std::get<5>(k2);
-      std::get<5>(k2) = q.N;
-      if (k2 == key && n2 <= 2 * q.N && q.N <= 2 * n2) return kv.second;
-    }
-  }
-  const bool tune = !getenv("SPK_AUTOTUNE") || atoi(getenv("SPK_AUTOTUNE")) != 0;
+  const int key[] = {q.H, q.W, q.Cin, q.x2 ? q.Cin2 : 0, q.Coutz, q.N};
   int choice = 1;
+  if (spk_tune_find(TUNE_CHAIN, key, &choice) || !spk_autotune_on()) return choice;
+  SpkLaunchTimer timer;
+  if (!timer.ok) return choice;
+  Layer& Q = m->layers[L.chain_next];
+  auto two = [&]() {
+    m->no_chain_now = true;
+    int r = run_conv_eval(m, L, nb);
+    if (r == SPK_OK) r = run_conv_eval(m, Q, nb);
+    m->no_chain_now = false;
+    return r;
+  };
+  auto one = [&]() { return spk_pw_chain_launch(q, m->stream); };
   float t_two = 0.f, t_one = 0.f;
-  hipEvent_t e0, e1;
-  if (tune && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
-    Layer& Q = m->layers[L.chain_next];
-    auto two = [&]() {
-      m->no_chain_now = true;
-      int r = run_conv_eval(m, L, nb);
-      if (r == SPK_OK) r = run_conv_eval(m, Q, nb);
-      m->no_chain_now = false;
-      return r;
-    };
-    bool ok = two() == SPK_OK && spk_pw_chain_launch(q, m->stream) == 0;   // warm-up (and the other kernels' own tuning)
-    if (ok) {
-      (void)hipEventRecord(e0, m->stream);
-      for (int r = 0; r < 3; ++r) (void)two();
-      (void)hipEventRecord(e1, m->stream);
-      ok = hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&t_two, e0, e1) == hipSuccess;
-    }
-    if (ok) {
-      (void)hipEventRecord(e0, m->stream);
-      for (int r = 0; r < 3; ++r) (void)spk_pw_chain_launch(q, m->stream);
-      (void)hipEventRecord(e1, m->stream);
-      ok = hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&t_one, e0, e1) == hipSuccess;
-    }
-    choice = ok && t_one < t_two ? 1 : 0;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (getenv("SPK_TUNE_LOG"))
-      fprintf(stderr, "[spk tune chain] N%d %dx%d C%d+%d->256->%d: two kernels %.1f us, chained %.1f us\n", q.N, q.H, q.W, q.Cin,
-              q.x2 ? q.Cin2 : 0, q.Coutz, t_two * 1000.f / 3.f, t_one * 1000.f / 3.f);
-    std::lock_guard<std::mutex> lk(g_chain_mu);
-    g_chain_choice[key] = choice;
-    if (path)
-      if (FILE* f = fopen(path, "a")) {
-        fprintf(f, "chain %d %d %d %d %d %d %d\n", q.H, q.W, q.Cin, q.x2 ? q.Cin2 : 0, q.Coutz, q.N, choice);
-        fclose(f);
-      }
-  }
+  const bool ok = two() == SPK_OK && one() == 0 &&   // warm-up (and the other kernels' own tuning)
+                  timer.time(m->stream, 3, two, &t_two) && timer.time(m->stream, 3, one, &t_one);
+  choice = ok && t_one < t_two ? 1 : 0;
+  if (spk_tune_log())
+    fprintf(stderr, "[spk tune chain] N%d %dx%d C%d+%d->256->%d: two kernels %.1f us, chained %.1f us\n", q.N, q.H, q.W, q.Cin,
+            q.x2 ? q.Cin2 : 0, q.Coutz, t_two * 1000.f / 3.f, t_one * 1000.f / 3.f);
+  spk_tune_store(TUNE_CHAIN, key, &choice, true);
   return choice;
 }
 
@@ -1159,13 +1109,6 @@ static bool chain_args(spk_model* m, const Layer& L, PwConvArgs& q, int nb) {
   return true;
 }
 
-// whole-bottleneck kernel or three launches?  Timed once per problem (the same bits either way), "bneck ..." lines of
-// SPK_TUNE_CACHE
-typedef std::tuple<int, int, int> BneckKey;   // H CM N
-static std::map<BneckKey, int> g_bneck_choice;
-static std::mutex g_bneck_mu;
-static bool g_bneck_loaded = false;
-
 static void bneck_args(spk_model* m, const Layer& L, BneckArgs& a, int nb) {
   const Layer& L2 = m->layers[L.bn_c2];
   const Layer& L3 = m->layers[L.bn_c3];
@@ -1181,7 +1124,9 @@ static void bneck_args(spk_model* m, const Layer& L, BneckArgs& a, int nb) {
   a.x_bytes = (unsigned)((size_t)nb * in.h * in.w * in.c * 2);
 }
 
-// 0: three launches, 1: blocks of 14 rows x 8 waves (one per CU), 2: blocks of 7 rows x 4 waves (two per CU)
+// whole-bottleneck kernel or three launches?  0: three launches, 1: blocks of 14 rows x 8 waves (one per CU), 2: blocks of
+// 7 rows x 4 waves (two per CU).  Below a quarter of the chip 0 and 2 are timed once per problem (the same bits either
+// way), "bneck" entries of the tuner table; without tuning 2, not remembered
 static int bneck_choice(spk_model* m, Layer& L, const BneckArgs& a, int nb) {
   if (m->bneck >= 2) return m->bneck == 3 ? 2 : 1;
   const int big_blocks = a.N * (a.H / 14);
@@ -1193,72 +1138,30 @@ static int bneck_choice(spk_model* m, Layer& L, const BneckArgs& a, int nb) {
   // (isolated, 14 x 14: 256 images 123 -> 114 us, 128 images 96 -> 67 us, 64 images 89 -> 57 us; 28 x 28: 197 -> 189, 87 -> 79,
   // 65 -> 51 us); below a quarter of the chip the three launches are timed against them.
   if (2 * big_blocks >= 64) return 2;
-  const BneckKey key(a.H, a.CM, a.N);
-  const char* path = getenv("SPK_TUNE_CACHE");
-  if (path && (!*path || !strcmp(path, "off"))) path = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(g_bneck_mu);
-    if (!g_bneck_loaded) {
-      g_bneck_loaded = true;
-      if (path)
-        if (FILE* f = fopen(path, "r")) {
-          char line[256];
-          int v[4];
-          while (fgets(line, sizeof line, f))
-            if (sscanf(line, "bneck %d %d %d %d", &v[0], &v[1], &v[2], &v[3]) == 4 && v[3] >= 0 && v[3] <= 2)
-              g_bneck_choice[BneckKey(v[0], v[1], v[2])] = v[3];
-          fclose(f);
-        }
-    }
-    auto it = g_bneck_choice.find(key);
-    if (it != g_bneck_choice.end()) return it->second;
-    for (const auto& kv : g_bneck_choice) {   // a ragged tail batch: the choice of a tuned batch within a factor of two
-      const int n2 = std::get<2>(kv.first);
-      if (std::get<0>(kv.first) == a.H && std::get<1>(kv.first) == a.CM && n2 <= 2 * a.N && a.N <= 2 * n2) return kv.second;
-    }
-  }
-  const bool tune = !getenv("SPK_AUTOTUNE") || atoi(getenv("SPK_AUTOTUNE")) != 0;
+  const int key[] = {a.H, a.CM, a.N};
   int choice = 2;
+  if (spk_tune_find(TUNE_BNECK, key, &choice) || !spk_autotune_on()) return choice;
+  SpkLaunchTimer timer;
+  if (!timer.ok) return choice;
+  BneckArgs as = a;
+  as.flags |= 4;
+  auto three = [&]() {
+    m->no_bneck_now = true;
+    int r = run_conv_eval(m, L, nb);
+    if (r == SPK_OK) r = run_conv_eval(m, m->layers[L.bn_c2], nb);
+    if (r == SPK_OK) r = run_conv_eval(m, m->layers[L.bn_c3], nb);
+    m->no_bneck_now = false;
+    return r;
+  };
+  auto one = [&]() { return spk_bneck_launch(as, m->stream); };
   float t_three = 0.f, t_one = 0.f;
-  hipEvent_t e0, e1;
-  if (tune && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
-    BneckArgs as = a;
-    as.flags |= 4;
-    auto three = [&]() {
-      m->no_bneck_now = true;
-      int r = run_conv_eval(m, L, nb);
-      if (r == SPK_OK) r = run_conv_eval(m, m->layers[L.bn_c2], nb);
-      if (r == SPK_OK) r = run_conv_eval(m, m->layers[L.bn_c3], nb);
-      m->no_bneck_now = false;
-      return r;
-    };
-    bool ok = three() == SPK_OK && spk_bneck_launch(as, m->stream) == 0;   // warm-up (and the other kernels' own tuning)
-    if (ok) {
-      (void)hipEventRecord(e0, m->stream);
-      for (int r = 0; r < 3; ++r) (void)three();
-      (void)hipEventRecord(e1, m->stream);
-      ok = hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&t_three, e0, e1) == hipSuccess;
-    }
-    if (ok) {
-      (void)hipEventRecord(e0, m->stream);
-      for (int r = 0; r < 3; ++r) (void)spk_bneck_launch(as, m->stream);
-      (void)hipEventRecord(e1, m->stream);
-      ok = hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&t_one, e0, e1) == hipSuccess;
-    }
-    choice = ok && t_one < t_three ? 2 : 0;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (getenv("SPK_TUNE_LOG"))
-      fprintf(stderr, "[spk tune bottleneck] N%d %dx%d %d->%d->%d: three kernels %.1f us, one (7-row blocks) %.1f us\n", a.N, a.H, a.W,
-              a.C4, a.CM, a.C4, t_three * 1000.f / 3.f, t_one * 1000.f / 3.f);
-    std::lock_guard<std::mutex> lk(g_bneck_mu);
-    g_bneck_choice[key] = choice;
-    if (path)
-      if (FILE* f = fopen(path, "a")) {
-        fprintf(f, "bneck %d %d %d %d\n", a.H, a.CM, a.N, choice);
-        fclose(f);
-      }
-  }
+  const bool ok = three() == SPK_OK && one() == 0 &&   // warm-up (and the other kernels' own tuning)
+                  timer.time(m->stream, 3, three, &t_three) && timer.time(m->stream, 3, one, &t_one);
+  choice = ok && t_one < t_three ? 2 : 0;
+  if (spk_tune_log())
+    fprintf(stderr, "[spk tune bottleneck] N%d %dx%d %d->%d->%d: three kernels %.1f us, one (7-row blocks) %.1f us\n", a.N, a.H, a.W,
+            a.C4, a.CM, a.C4, t_three * 1000.f / 3.f, t_one * 1000.f / 3.f);
+  spk_tune_store(TUNE_BNECK, key, &choice, true);
   return choice;
 }
 
@@ -1467,16 +1370,13 @@ static int run_conv_eval(spk_model* m, Layer& L, int nb) {
 // image of a channel slab in LDS, LDS-DMA double-buffered, one block walking over many images - was built for the
 // 14^2 / 7^2 layers and measured no faster than these two on any layer: those layers are VALU-bound, not latency-
 // bound; removed.)
-#include <map>
-#include <mutex>
-#include <tuple>
 static int dw_forced() {
   static const int v = getenv("SPK_DW_LDS") ? atoi(getenv("SPK_DW_LDS")) : -1;
   return v;
 }
-static std::map<std::tuple<int, int, int, int, int, int, int>, int> g_dw_choice;
-static std::mutex g_dw_mu;
 
+// The choice stays in the process and matches its problem exactly: the two kernels sum the pool partials in different
+// orders, so a choice carried to another run or another batch size would change the bits of that run.
 template <class F>
 static int dw_choose(int et, int nb, int h, int w, int c, int k, int s, hipStream_t st, F run, const int* chunks) {
   // candidates: 0 gather kernel, 1 LDS ring kernel; chunks[v] == 0: cannot run this problem
@@ -1485,32 +1385,22 @@ static int dw_choose(int et, int nb, int h, int w, int c, int k, int s, hipStrea
     if (v < 2 && chunks[v] > 0) return v;
     return 0;
   }
-  const auto key = std::make_tuple(et, nb, h, w, c, k, s);
-  {
-    std::lock_guard<std::mutex> lk(g_dw_mu);
-    auto it = g_dw_choice.find(key);
-    if (it != g_dw_choice.end()) return it->second;
-  }
-  hipEvent_t e0, e1;
+  const int key[] = {et, nb, h, w, c, k, s};
   int best = 0;
-  if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
+  if (spk_tune_find(TUNE_DW, key, &best)) return best;
+  SpkLaunchTimer timer;
+  if (timer.ok) {
     float t[2] = {1e30f, 1e30f};
     for (int v = 0; v < 2; ++v) {
       if (chunks[v] <= 0 || run(v) != 0) continue;   // warm-up
-      (void)hipEventRecord(e0, st);
-      for (int r = 0; r < 3; ++r) (void)run(v);
-      (void)hipEventRecord(e1, st);
-      if (hipEventSynchronize(e1) == hipSuccess) (void)hipEventElapsedTime(&t[v], e0, e1);
+      if (!timer.time(st, 3, [&] { return run(v); }, &t[v])) t[v] = 1e30f;
     }
     if (t[1] < t[0]) best = 1;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (getenv("SPK_TUNE_LOG"))
+    if (spk_tune_log())
       fprintf(stderr, "[spk tune] depthwise et %d N%d %dx%d C%d k%d s%d: gather %.1f us, lds ring %.1f us\n", et, nb, h, w, c, k, s,
               t[0] * 1000.f / 3.f, t[1] * 1000.f / 3.f);
   }
-  std::lock_guard<std::mutex> lk(g_dw_mu);
-  g_dw_choice[key] = best;
+  spk_tune_store(TUNE_DW, key, &best, false);
   return best;
 }
 

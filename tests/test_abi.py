@@ -46,7 +46,9 @@ def test_struct_layouts_match_header():
 def test_host_code_under_address_and_ub_sanitizers():
     """`csrc/build_asan.sh`: every translation unit with -fsanitize=address,undefined on its host pass + csrc/
     asan_driver.hip, which walks handle creation and its error paths, the parameter table (with a deliberately short
-    key buffer), spk_last_error and the three tuner-cache parsers (valid, truncated, garbage and over-long lines).
+    key buffer), spk_last_error and the tuner table: one parser for the seven tags of the tune-cache file (valid,
+    out-of-range, truncated, garbage, comment and over-long lines), the nearest-batch rule, the SPK_TUNE_CACHE path
+    rule, and the shipped seed (argv[1]) loaded and written back line for line through the function that appends.
     Without a GPU every HIP call fails and the error paths run; a sanitizer report aborts the driver (exit != 0)."""
     import os
     import subprocess
@@ -60,6 +62,7 @@ def test_host_code_under_address_and_ub_sanitizers():
         subprocess.run(["bash", str(recipe)], check=True, timeout=1500)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     env.pop("SPK_TUNE_CACHE", None)
-    r = subprocess.run([str(exe)], env=env, capture_output=True, text=True, timeout=300)
+    seed = ROOT / "syke-pic_amd" / "sykepic_hip" / "tune_seed_gfx950.txt"
+    r = subprocess.run([str(exe), str(seed)], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "asan_driver: ok" in r.stdout and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr

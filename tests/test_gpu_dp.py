@@ -219,6 +219,80 @@ def test_tune_cache_persists_and_is_reused(tmp_path):
     assert np.array_equal(np.load(tmp_path / "a.npy"), np.load(tmp_path / "b.npy"))
 
 
+def _cold_then_warm(tmp_path, code):
+    """Two fresh processes run `code` on one tune-cache file: (the cold one's stderr, the file's lines after it, the warm
+    one's stderr).  The warm process must leave the file as it found it."""
+    cache = tmp_path / "tune.txt"
+    env = dict(os.environ, SPK_TUNE_CACHE=str(cache), SPK_TUNE_LOG="1")
+    code = f"import sys\nsys.path[:0] = [{str(ROOT)!r}, {str(ROOT / 'syke-pic_amd')!r}]\n" + code
+    cold = subprocess.run([sys.executable, "-c", code, str(tmp_path / "a.npy")], env=env, capture_output=True, text=True,
+                          timeout=600)
+    assert cold.returncode == 0, cold.stderr[-2000:]
+    assert "[spk tune" in cold.stderr and cache.is_file()
+    lines = cache.read_text().splitlines()
+    warm = subprocess.run([sys.executable, "-c", code, str(tmp_path / "b.npy")], env=env, capture_output=True, text=True,
+                          timeout=600)
+    assert warm.returncode == 0, warm.stderr[-2000:]
+    assert cache.read_text().splitlines() == lines              # nothing re-tuned, nothing appended
+    return cold.stderr, lines, warm.stderr
+
+
+def test_tune_cache_covers_the_bottleneck_tuners(tmp_path):
+    """The tuners only a bottleneck network reaches - chained 1x1 convs ("chain"), the dual-source block-closing conv
+    ("pw2") and the whole-block kernel ("bneck": it exists at 14 x 14 and 28 x 28 only, i.e. at 224 x 224, and is timed
+    only below 32 large blocks) - persist and are re-used like the others: ResNet-50, calibrated precision, a batch of 4
+    and its first 3 images (nearest tuned batch).  The warm process tunes nothing and returns the same logits bit for
+    bit."""
+    code = (
+        "import numpy as np, torch\n"
+        "from sykepic_hip import arch, synth\n"
+        "from sykepic_hip.net import HipNet\n"
+        "g = arch.build_graph('resnet50', 50)\n"
+        "sd = synth.synth_state_dict(arch.param_specs(g), seed=2)\n"
+        "net = HipNet('resnet50', 50, weights=None)\n"
+        "net.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}); net.eval()\n"
+        "x = torch.from_numpy(synth.synth_images(4, 3, 224, 224, seed=5)).cuda()\n"
+        "net.calibrate(x)\n"
+        "net.set_precision('calibrated')\n"
+        "z = net.forward(x).cpu().numpy(); z3 = net.forward(x[:3]).cpu().numpy()\n"
+        "np.save(sys.argv[1], np.concatenate([z, z3]))\n")
+    _, lines, warm = _cold_then_warm(tmp_path, code)
+    tags = {ln.split()[0] for ln in lines}
+    assert {"conv", "pw1x1", "c3", "chain", "pw2", "bneck"} <= tags, tags
+    assert "[spk tune" not in warm
+    a, b = np.load(tmp_path / "a.npy"), np.load(tmp_path / "b.npy")
+    assert a.shape == (7, 50) and np.isfinite(a).all() and np.array_equal(a, b)
+
+
+def test_tune_cache_covers_the_training_tuners(tmp_path):
+    """Training: the weight-gradient pipeline depth ("wgrad") and the data-gradient convs ("conv" lines whose first field
+    is the dgrad mode) persist too.  ResNet-18, 64 x 64, batch 8, two Adam steps: the warm process tunes nothing and
+    ends on the same loss bit for bit.  (The tile choice groups the BatchNorm partial sums, but the cold process runs
+    every launch that counts on the winner it has just stored, which is the one the warm process loads.)"""
+    code = (
+        "import numpy as np, torch\n"
+        "from sykepic_hip import synth\n"
+        "from sykepic_hip.net import HipNet\n"
+        "from sykepic_hip.optim import HipOptimizer\n"
+        "net = HipNet('resnet18', 10, weights=None, head=(64, 32))\n"
+        "net.reset_parameters(seed=3); net.set_seed(3)\n"
+        "for p in net.parameters(): p.requires_grad = True\n"
+        "opt = HipOptimizer(net, 'Adam', [{'params': list(net.parameters()), 'lr': 1e-3}])\n"
+        "net.train()\n"
+        "for s in range(2):\n"
+        "    x = torch.from_numpy(synth.synth_images(8, 3, 64, 64, seed=100 + s)).cuda()\n"
+        "    y = torch.from_numpy(synth.synth_labels(8, 10, seed=200 + s)).cuda()\n"
+        "    net.reset_stats(); net.forward_backward(x, y); opt.step()\n"
+        "np.save(sys.argv[1], np.array(net.read_stats(), dtype=np.float64))\n")
+    _, lines, warm = _cold_then_warm(tmp_path, code)
+    assert any(ln.startswith("wgrad ") for ln in lines)
+    assert any(ln.startswith("conv 2 ") for ln in lines)        # CONV_MODE_DGRAD (csrc/spk_common.h)
+    assert "[spk tune" not in warm
+    a, b = np.load(tmp_path / "a.npy"), np.load(tmp_path / "b.npy")
+    print("loss * n, correct after step 2: cold", a.tolist(), "warm", b.tolist())
+    assert a[0] > 0 and np.array_equal(a, b)
+
+
 _ONE_RANK_RCCL = r"""
 import sys
 import numpy as np, torch, torch.distributed as dist
