@@ -467,6 +467,41 @@ int spk_op_stem3_train(const void* x_dev, const float* w_dev, const void* dy_dev
  *     0 the eval path's LDS-window kernel, 1 dw_dgrad_px_kernel, 2 the gather kernels, -1 none */
 int spk_op_mbconv_geometry(int kind, int m, int channels, int hw, int s_hidden, int out[8]);
 
+/* --- Test hooks: single operators of the classifier head, the loss and the pooling layers ---
+ * (csrc/head.hip, csrc/pointwise.hip, csrc/train_kernels.hip): the launches `net(x)`, `criterion(out, y)` and
+ * `loss.backward()` (sykepic/train/train.py:240-242, sykepic/compute/probability.py:189-194) reach for ONE such layer,
+ * through the launcher functions the model executor and the training step call.  Every pointer is device memory;
+ * head tensors are float32 row-major, pooling tensors NHWC with c a multiple of 8.  Synchronous.
+ *
+ * y [n][out] = x [n][in] . w [out][in]^T + b [out] (b may be NULL): the MFMA kernel when in % 4 == 0, else the GEMM. */
+int spk_op_linear(const float* x_dev, const float* w_dev, const float* b_dev, float* y_dev, int n, int in, int out,
+                  void* hip_stream);
+/* Its backward as the training step runs it: dw [out][in] = gy^T . x, db [out] = column sums of gy, dx [n][in] = gy . w;
+ * a NULL output is skipped (x is needed for dw only, w for dx only).  form: -1 the GEMM kernel the step uses
+ * (SPK_SGEMM_FMA), 0 the MFMA kernel, 1 the LDS-tiled FMA kernel. */
+int spk_op_linear_backward(const float* gy_dev, const float* x_dev, const float* w_dev, float* dw_dev, float* db_dev,
+                           float* dx_dev, int n, int in, int out, int form, void* hip_stream);
+/* p [n][c] = softmax(z * logf(base)) per row (the base-1.3 softmax of net_pass is base = 1.3). */
+int spk_op_softmax(const float* z_dev, float* p_dev, int n, int c, float base, void* hip_stream);
+/* CrossEntropyLoss(reduction mean) and its gradient: stats[0] += sum of the row losses, stats[1] += rows whose arg-max
+ * (lowest index among the maxima) is the label; dz [n][c] (may be NULL) = (softmax(z) - onehot) / n.  labels: int64 [n],
+ * each in [0, c). */
+int spk_op_cross_entropy(const float* z_dev, const int64_t* labels_dev, int n, int c, float* stats_dev, float* dz_dev,
+                         void* hip_stream);
+/* MaxPool2d(k, stride, pad): x [n,h,w,c] -> y [n,ho,wo,c].  idx == NULL: the eval path's kernel, dtype 0 bf16 / 1 fp16.
+ * idx [n,ho,wo,c] bytes: the training step's kernel (bf16 only), which also saves the tap r * k + s of each maximum (the
+ * first in that order among equal values).  c % 8 != 0: SPK_ERR_ARG; k * k > 255 or pad > k / 2: SPK_ERR_UNSUPPORTED. */
+int spk_op_maxpool(const void* x_dev, void* y_dev, unsigned char* idx_dev, int n, int h, int w, int c, int k, int stride,
+                   int pad, int dtype, void* hip_stream);
+/* Its backward: gx [n,h,w,c] bf16 = for each pixel the sum of gy over the windows whose saved tap points at it.
+ * form: -1 the kernel the step uses (SPK_POOL_PAIR), 0 the per-pixel kernel (compiled for k3 s2 p1, run-time k / stride /
+ * pad otherwise), 1 the pixel-pair kernel (k3 s2 p1 and an even width, else SPK_ERR_UNSUPPORTED). */
+int spk_op_maxpool_backward(const void* gy_dev, const unsigned char* idx_dev, void* gx_dev, int n, int h, int w, int c,
+                            int k, int stride, int pad, int form, void* hip_stream);
+/* AdaptiveAvgPool2d(1): x [n][hw][c] (dtype 0 bf16 / 1 fp16) -> y float32 [n][c]; backward gx [n][hw][c] bf16 = gy / hw. */
+int spk_op_gavgpool(const void* x_dev, float* y_dev, int n, int hw, int c, int dtype, void* hip_stream);
+int spk_op_gavgpool_backward(const float* gy_dev, void* gx_dev, int n, int hw, int c, void* hip_stream);
+
 /* --- ROI preprocessing straight from the .roi blob ---
  * One ROI of an IFCB sample: byte offset into the .roi blob, width, height
  * (columns 17/15/16 of the .adc line, sykepic/utils/ifcb.py:100-110). */

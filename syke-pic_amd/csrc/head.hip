@@ -12,11 +12,9 @@ namespace {
 
 // C[i][j] = sum_k A(i,k) * B(j,k) (+ bias[j]);  A(i,k) = A[i*sai + k*sak], B likewise.
 // 64x64 tile, 256 threads, 4x4 outputs per thread, K step 16.
-// accumulate != 0: C += result (used for gradient accumulation).
 __global__ __launch_bounds__(256) void sgemm_strided_kernel(
     const float* __restrict__ A, long sai, long sak, const float* __restrict__ B, long sbj, long sbk,
-    const float* __restrict__ bias, float* __restrict__ C, long sci, long scj, int M, int N, int K,
-    float alpha, int accumulate) {
+    const float* __restrict__ bias, float* __restrict__ C, long sci, long scj, int M, int N, int K) {
   __shared__ float sa[16][64 + 4];
   __shared__ float sb[16][64 + 4];
   const int tid = threadIdx.x;
@@ -58,9 +56,7 @@ __global__ __launch_bounds__(256) void sgemm_strided_kernel(
     for (int v = 0; v < 4; ++v) {
       const int gj = j0 + tx * 4 + v;
       if (gj >= N) continue;
-      float r = acc[u][v] * alpha + (bias ? bias[gj] : 0.f);
-      float* c = C + gi * sci + gj * scj;
-      *c = accumulate ? *c + r : r;
+      C[gi * sci + gj * scj] = acc[u][v] + (bias ? bias[gj] : 0.f);
     }
   }
 }
@@ -72,8 +68,7 @@ __global__ __launch_bounds__(256) void sgemm_strided_kernel(
 // GEMMs (2048 x 256 x 256 and smaller) took 37 us each on the LDS-tiled FMA kernel above, 0.22 ms of a ResNet-50 step.
 __global__ __launch_bounds__(256) void sgemm_mfma_strided_kernel(
     const float* __restrict__ A, long sai, long sak, const float* __restrict__ B, long sbj, long sbk,
-    const float* __restrict__ bias, float* __restrict__ C, long sci, long scj, int M, int N, int K,
-    float alpha, int accumulate) {
+    const float* __restrict__ bias, float* __restrict__ C, long sci, long scj, int M, int N, int K) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
   const int i0 = blockIdx.y * 32 + (wave >> 1) * 16, j0 = blockIdx.x * 32 + (wave & 1) * 16;
@@ -104,9 +99,7 @@ __global__ __launch_bounds__(256) void sgemm_mfma_strided_kernel(
   for (int e = 0; e < 4; ++e) {
     const int gi = i0 + g * 4 + e;
     if (gi >= M) continue;
-    float* c = C + gi * sci + gj * scj;
-    const float v = acc[e] * alpha + bj;
-    *c = accumulate ? *c + v : v;
+    C[gi * sci + gj * scj] = acc[e] + bj;
   }
 }
 
@@ -169,6 +162,10 @@ __device__ __forceinline__ float wave_sum(float v) {
 // one wave per row: p = softmax(z * scale)
 __global__ void softmax_kernel(const float* __restrict__ z, float* __restrict__ p, int n, int c,
                                float scale) {
+  // No contraction in this body: `zr[j] * scale - mx` as one fma subtracts the ROUNDED maximum from the UNROUNDED
+  // product, so the maximum's own exponent was not 0 and a row of equal logits did not come out as 1 / c
+  // (tests/test_gpu_head_pool_ops.py).  The product is rounded in all three passes, as in the max pass.
+#pragma clang fp contract(off)
   const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= n) return;
@@ -278,25 +275,45 @@ int spk_launch_predict(const float* p, int n, int c, const float* thr, float sca
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int spk_launch_sgemm(const float* A, long sai, long sak, const float* B, long sbj, long sbk,
-                     const float* bias, float* C, long sci, long scj, int M, int N, int K,
-                     float alpha, int accumulate, hipStream_t s) {
-  static const bool fma = getenv("SPK_SGEMM_FMA") && atoi(getenv("SPK_SGEMM_FMA")) != 0;   // the LDS-tiled FMA kernel (A/B runs)
+int spk_launch_sgemm_form(const float* A, long sai, long sak, const float* B, long sbj, long sbk,
+                          const float* bias, float* C, long sci, long scj, int M, int N, int K, bool fma,
+                          hipStream_t s) {
   if (!fma) {
     hipLaunchKernelGGL(sgemm_mfma_strided_kernel, dim3((N + 31) / 32, (M + 31) / 32), dim3(256), 0, s, A, sai, sak, B, sbj, sbk,
-                       bias, C, sci, scj, M, N, K, alpha, accumulate);
+                       bias, C, sci, scj, M, N, K);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
   dim3 grid((N + 63) / 64, (M + 63) / 64);
   hipLaunchKernelGGL(sgemm_strided_kernel, grid, dim3(256), 0, s, A, sai, sak, B, sbj, sbk, bias, C,
-                     sci, scj, M, N, K, alpha, accumulate);
+                     sci, scj, M, N, K);
   return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int spk_launch_sgemm(const float* A, long sai, long sak, const float* B, long sbj, long sbk,
+                     const float* bias, float* C, long sci, long scj, int M, int N, int K, hipStream_t s) {
+  static const bool fma = getenv("SPK_SGEMM_FMA") && atoi(getenv("SPK_SGEMM_FMA")) != 0;   // the LDS-tiled FMA kernel (A/B runs)
+  return spk_launch_sgemm_form(A, sai, sak, B, sbj, sbk, bias, C, sci, scj, M, N, K, fma, s);
+}
+
+// Backward of y = x . w^T + b for one Linear layer: the launches of a training step (and of spk_op_linear_backward).
+// dw [out][in], db [out], dx [n][in]: a null pointer skips that gradient.  form < 0: the kernel spk_launch_sgemm picks,
+// 0 the MFMA kernel, 1 the FMA kernel.
+int spk_linear_backward(const float* gy, const float* x, const float* w, float* dw, float* db, float* dx, int n, int in,
+                        int out, int form, hipStream_t s) {
+  auto gemm = [&](const float* A, long sai, long sak, const float* B, long sbj, long sbk, float* C, int M, int N, int K) {
+    return form < 0 ? spk_launch_sgemm(A, sai, sak, B, sbj, sbk, nullptr, C, N, 1, M, N, K, s)
+                    : spk_launch_sgemm_form(A, sai, sak, B, sbj, sbk, nullptr, C, N, 1, M, N, K, form != 0, s);
+  };
+  if (dw && gemm(gy, 1, out, x, 1, in, dw, out, in, n)) return -1;   // dW[o][i] = sum_n gy[n][o] * x[n][i]
+  if (db && spk_launch_colsum(gy, db, n, out, s)) return -1;
+  if (dx && gemm(gy, out, 1, w, 1, in, dx, n, in, out)) return -1;   // dX[n][i] = sum_o gy[n][o] * W[o][i]
+  return 0;
 }
 
 int spk_launch_linear_fwd(const float* x, const float* w, const float* b, float* y, int n, int in,
                           int out, hipStream_t s) {
   // y[n][out] = x[n][in] . w[out][in]^T + b
-  if (in % 4) return spk_launch_sgemm(x, in, 1, w, in, 1, b, y, out, 1, n, out, in, 1.f, 0, s);
+  if (in % 4) return spk_launch_sgemm(x, in, 1, w, in, 1, b, y, out, 1, n, out, in, s);
   hipLaunchKernelGGL(linear_mfma_kernel, dim3((out + 15) / 16, (n + 15) / 16), dim3(256), 0, s, x, w, b,
                      y, n, in, out);
   return hipGetLastError() == hipSuccess ? 0 : -1;

@@ -4,6 +4,9 @@
 // known operands and compare its output with autograd evaluated on the same (bf16-rounded) operands:
 //   conv + train-mode BatchNorm forward   torch Conv2d + BatchNorm2d(+add)(+ReLU), sykepic/train/train.py:240
 //   BatchNorm / conv backward             what loss.backward() runs for that layer,  sykepic/train/train.py:242
+//   Linear / softmax / CrossEntropyLoss    spk_op_linear, spk_op_linear_backward, spk_op_softmax, spk_op_cross_entropy
+//   MaxPool2d / AdaptiveAvgPool2d(1)       spk_op_maxpool, spk_op_maxpool_backward, spk_op_gavgpool, spk_op_gavgpool_backward
+//                                          (head.hip, pointwise.hip, train_kernels.hip; exact integer and float64 references)
 // Scratch is allocated and freed inside the call (these are not on any hot path).
 #include "model.h"
 #include "train_effnet.h"
@@ -796,4 +799,121 @@ extern "C" int spk_op_mbconv_geometry(int kind, int M, int C, int HW, int S, int
       return SPK_OK;
   }
   return ofail(SPK_ERR_ARG, "op_mbconv_geometry: kind 0 ... 4");
+}
+
+// ---- the classifier head, the loss and the pooling layers (head.hip, pointwise.hip, train_kernels.hip), one layer at a
+// time through the launchers model.hip and train.hip call.  Arguments are checked before any HIP call. ----
+namespace {
+bool below_2g(size_t a, size_t b, size_t c = 1, size_t d = 1) { return a * b * c * d < ((size_t)1 << 31); }
+}  // namespace
+
+extern "C" int spk_op_linear(const float* x, const float* w, const float* b, float* y, int n, int in, int out, void* stream) {
+  if (!x || !w || !y || n < 1 || in < 1 || out < 1) return ofail(SPK_ERR_ARG, "op_linear: bad arguments");
+  if (!below_2g(n, in) || !below_2g(out, in) || !below_2g(n, out))
+    return ofail(SPK_ERR_UNSUPPORTED, "op_linear: a tensor of 2^31 elements or more");
+  hipStream_t s = (hipStream_t)stream;
+  O_TRY(spk_launch_linear_fwd(x, w, b, y, n, in, out, s), "linear");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_linear: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_linear_backward(const float* gy, const float* x, const float* w, float* dw, float* db, float* dx, int n,
+                                      int in, int out, int form, void* stream) {
+  if (!gy || (!dw && !db && !dx) || (dw && !x) || (dx && !w) || n < 1 || in < 1 || out < 1 || form < -1 || form > 1)
+    return ofail(SPK_ERR_ARG, "op_linear_backward: bad arguments (form -1, 0 or 1)");
+  if (!below_2g(n, in) || !below_2g(out, in) || !below_2g(n, out))
+    return ofail(SPK_ERR_UNSUPPORTED, "op_linear_backward: a tensor of 2^31 elements or more");
+  hipStream_t s = (hipStream_t)stream;
+  O_TRY(spk_linear_backward(gy, x, w, dw, db, dx, n, in, out, form, s), "linear backward");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_linear_backward: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_softmax(const float* z, float* p, int n, int c, float base, void* stream) {
+  if (!z || !p || n < 1 || c < 1 || !(base > 0.f)) return ofail(SPK_ERR_ARG, "op_softmax: bad arguments");
+  if (!below_2g(n, c)) return ofail(SPK_ERR_UNSUPPORTED, "op_softmax: a tensor of 2^31 elements or more");
+  hipStream_t s = (hipStream_t)stream;
+  O_TRY(spk_launch_softmax(z, p, n, c, logf(base), s), "softmax");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_softmax: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_cross_entropy(const float* z, const int64_t* labels, int n, int c, float* stats, float* dz,
+                                    void* stream) {
+  if (!z || !labels || !stats || n < 1 || c < 1) return ofail(SPK_ERR_ARG, "op_cross_entropy: bad arguments");
+  if (!below_2g(n, c)) return ofail(SPK_ERR_UNSUPPORTED, "op_cross_entropy: a tensor of 2^31 elements or more");
+  hipStream_t s = (hipStream_t)stream;
+  O_TRY(spk_launch_ce(z, labels, n, c, stats, dz, s), "cross-entropy");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_cross_entropy: kernel failed");
+  return SPK_OK;
+}
+
+namespace {
+// shared argument rules of the two max-pool hooks; 0 when the problem can run
+int pool_args(const char* who, int n, int h, int w, int c, int k, int stride, int pad, int* ho, int* wo) {
+  if (n < 1 || h < 1 || w < 1 || c < 8 || c % 8 || k < 1 || stride < 1 || pad < 0)
+    return ofail(SPK_ERR_ARG, std::string(who) + ": bad arguments (c a multiple of 8)");
+  if (k * k > 255 || k > 15 || pad > k / 2)
+    return ofail(SPK_ERR_UNSUPPORTED, std::string(who) + ": the saved tap is one byte (k * k <= 255) and pad <= k / 2");
+  if (h + 2 * pad < k || w + 2 * pad < k) return ofail(SPK_ERR_ARG, std::string(who) + ": empty output");
+  *ho = (h + 2 * pad - k) / stride + 1;
+  *wo = (w + 2 * pad - k) / stride + 1;
+  if (!below_2g(n, h, w, c) || (size_t)n * h > 0x7fffffffull)
+    return ofail(SPK_ERR_UNSUPPORTED, std::string(who) + ": a tensor of 2^31 elements or more");
+  return SPK_OK;
+}
+}  // namespace
+
+extern "C" int spk_op_maxpool(const void* x, void* y, unsigned char* idx, int n, int h, int w, int c, int k, int stride,
+                              int pad, int dtype, void* stream) {
+  if (!x || !y || (dtype != DT_BF16 && dtype != DT_F16)) return ofail(SPK_ERR_ARG, "op_maxpool: bad arguments");
+  int ho = 0, wo = 0;
+  if (const int r = pool_args("op_maxpool", n, h, w, c, k, stride, pad, &ho, &wo)) return r;
+  if (idx && dtype != DT_BF16) return ofail(SPK_ERR_UNSUPPORTED, "op_maxpool: the kernel that saves the taps is bf16 only");
+  hipStream_t s = (hipStream_t)stream;
+  if (idx)
+    O_TRY(spk_launch_maxpool_idx((const bf16_t*)x, (bf16_t*)y, idx, n, h, w, c, k, stride, pad, ho, wo, s), "maxpool");
+  else
+    O_TRY(spk_launch_maxpool((const bf16_t*)x, (bf16_t*)y, n, h, w, c, k, stride, pad, ho, wo, dtype, s), "maxpool");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_maxpool: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_maxpool_backward(const void* gy, const unsigned char* idx, void* gx, int n, int h, int w, int c, int k,
+                                       int stride, int pad, int form, void* stream) {
+  if (!gy || !idx || !gx || form < -1 || form > 1)
+    return ofail(SPK_ERR_ARG, "op_maxpool_backward: bad arguments (form -1, 0 or 1)");
+  int ho = 0, wo = 0;
+  if (const int r = pool_args("op_maxpool_backward", n, h, w, c, k, stride, pad, &ho, &wo)) return r;
+  if (form == 1 && !spk_maxpool_pair_ok(h, w, k, stride, pad, ho, wo))
+    return ofail(SPK_ERR_UNSUPPORTED, "op_maxpool_backward: the pixel-pair kernel needs k 3, stride 2, pad 1 and an even width");
+  hipStream_t s = (hipStream_t)stream;
+  if (form < 0)
+    O_TRY(spk_launch_maxpool_bwd((const bf16_t*)gy, idx, (bf16_t*)gx, n, h, w, c, k, stride, pad, ho, wo, s), "maxpool bwd");
+  else
+    O_TRY(spk_launch_maxpool_bwd_form((const bf16_t*)gy, idx, (bf16_t*)gx, n, h, w, c, k, stride, pad, ho, wo, form == 1, s),
+          "maxpool bwd");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_maxpool_backward: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_gavgpool(const void* x, float* y, int n, int hw, int c, int dtype, void* stream) {
+  if (!x || !y || n < 1 || hw < 1 || c < 8 || c % 8 || (dtype != DT_BF16 && dtype != DT_F16))
+    return ofail(SPK_ERR_ARG, "op_gavgpool: bad arguments (c a multiple of 8)");
+  if (n > 65535 || !below_2g(n, hw, c))
+    return ofail(SPK_ERR_UNSUPPORTED, "op_gavgpool: more than 65535 images or a tensor of 2^31 elements or more");
+  hipStream_t s = (hipStream_t)stream;
+  O_TRY(spk_launch_gavgpool((const bf16_t*)x, y, n, hw, c, dtype, s), "avgpool");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_gavgpool: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_gavgpool_backward(const float* gy, void* gx, int n, int hw, int c, void* stream) {
+  if (!gy || !gx || n < 1 || hw < 1 || c < 8 || c % 8)
+    return ofail(SPK_ERR_ARG, "op_gavgpool_backward: bad arguments (c a multiple of 8)");
+  if (!below_2g(n, hw, c)) return ofail(SPK_ERR_UNSUPPORTED, "op_gavgpool_backward: a tensor of 2^31 elements or more");
+  hipStream_t s = (hipStream_t)stream;
+  O_TRY(spk_launch_gavgpool_bwd(gy, (bf16_t*)gx, n, hw, c, s), "avgpool bwd");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_gavgpool_backward: kernel failed");
+  return SPK_OK;
 }

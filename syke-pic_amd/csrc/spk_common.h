@@ -349,10 +349,17 @@ int spk_launch_dwconv_lds(int et, const void* x, const float* w, const float* sc
 // ---------------------------------------------------------------------------
 // Head (head.hip): fp32 Linear layers, softmax, cross-entropy
 // ---------------------------------------------------------------------------
-// C[i][j] (+)= alpha * sum_k A(i,k)*B(j,k) + bias[j], arbitrary element strides
+// C[i][j] = sum_k A(i,k)*B(j,k) + bias[j], arbitrary element strides.  spk_launch_sgemm: the MFMA kernel unless
+// SPK_SGEMM_FMA=1 (read once); spk_launch_sgemm_form: the kernel the caller names (fma: the LDS-tiled FMA kernel)
 int spk_launch_sgemm(const float* A, long sai, long sak, const float* B, long sbj, long sbk,
-                     const float* bias, float* C, long sci, long scj, int M, int N, int K,
-                     float alpha, int accumulate, hipStream_t s);
+                     const float* bias, float* C, long sci, long scj, int M, int N, int K, hipStream_t s);
+int spk_launch_sgemm_form(const float* A, long sai, long sak, const float* B, long sbj, long sbk,
+                          const float* bias, float* C, long sci, long scj, int M, int N, int K, bool fma,
+                          hipStream_t s);
+// weight, bias and data gradient of one Linear layer (gy [n][out], x [n][in], w [out][in]); a null output is skipped.
+// form < 0: spk_launch_sgemm's kernel, 0 / 1: spk_launch_sgemm_form(fma = form)
+int spk_linear_backward(const float* gy, const float* x, const float* w, float* dw, float* db, float* dx, int n, int in,
+                        int out, int form, hipStream_t s);
 int spk_launch_linear_fwd(const float* x, const float* w, const float* b, float* y, int n, int in,
                           int out, hipStream_t s);
 int spk_launch_softmax(const float* z, float* p, int n, int c, float scale, hipStream_t s);
@@ -402,8 +409,13 @@ int spk_launch_bn_bwd(const bf16_t* g, const unsigned char* mask, const bf16_t* 
                       int C, int relu, float* tmp, hipStream_t s, int pre_blocks = 0);
 int spk_launch_maxpool_idx(const bf16_t* x, bf16_t* y, unsigned char* idx, int n, int h, int w, int c,
                            int k, int stride, int pad, int ho, int wo, hipStream_t s);
+// spk_launch_maxpool_bwd: the pixel-pair kernel where spk_maxpool_pair_ok holds, unless SPK_POOL_PAIR=0 (read once);
+// spk_launch_maxpool_bwd_form: the caller's choice (pair where spk_maxpool_pair_ok does not hold: -2, nothing launched)
 int spk_launch_maxpool_bwd(const bf16_t* gy, const unsigned char* idx, bf16_t* gx, int n, int h, int w,
                            int c, int k, int stride, int pad, int ho, int wo, hipStream_t s);
+int spk_launch_maxpool_bwd_form(const bf16_t* gy, const unsigned char* idx, bf16_t* gx, int n, int h, int w,
+                                int c, int k, int stride, int pad, int ho, int wo, bool pair, hipStream_t s);
+bool spk_maxpool_pair_ok(int h, int w, int k, int stride, int pad, int ho, int wo);
 int spk_launch_gavgpool_bwd(const float* gy, bf16_t* gx, int n, int hw, int c, hipStream_t s);
 int spk_launch_colsum(const float* dy, float* db, int n, int c, hipStream_t s);
 int spk_launch_dropout_fwd(const float* x, float* y, unsigned char* mask, size_t n, float p, unsigned long long seed,

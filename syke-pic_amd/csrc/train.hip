@@ -754,16 +754,11 @@ extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, in
         const float* gy = (const float*)t->G(L.d.dst);
         const float* xin = (const float*)m->T(L.d.src);
         const int fin = L.d.cin, fout = L.d.cout;
-        if (m->params[L.p_w].requires_grad)  // dW[o][i] = sum_n gy[n][o] * x[n][i]
-          K_TRY(spk_launch_sgemm(gy, 1, fout, xin, 1, fin, nullptr, t->gbuf + m->params[L.p_w].off, fin, 1,
-                                 fout, fin, n, 1.f, 0, s), "linear wgrad");
-        if (m->params[L.p_b].requires_grad)
-          K_TRY(spk_launch_colsum(gy, t->gbuf + m->params[L.p_b].off, n, fout, s), "bias grad");
-        if (needs[L.d.src]) {   // dX[n][i] = sum_o gy[n][o] * W[o][i]
-          K_TRY(spk_launch_sgemm(gy, fout, 1, m->P(L.p_w), 1, fin, nullptr, (float*)t->G(L.d.src), fin, 1, n,
-                                 fin, fout, 1.f, 0, s), "linear dgrad");
-          has_grad[L.d.src] = 1;
-        }
+        K_TRY(spk_linear_backward(gy, xin, m->P(L.p_w),
+                                  m->params[L.p_w].requires_grad ? t->gbuf + m->params[L.p_w].off : nullptr,
+                                  m->params[L.p_b].requires_grad ? t->gbuf + m->params[L.p_b].off : nullptr,
+                                  needs[L.d.src] ? (float*)t->G(L.d.src) : nullptr, n, fin, fout, -1, s), "linear backward");
+        if (needs[L.d.src]) has_grad[L.d.src] = 1;
         mark(m, PH_HEAD_BWD);
         break;
       }

@@ -740,12 +740,16 @@ int spk_launch_maxpool_idx(const bf16_t* x, bf16_t* y, unsigned char* idx, int n
   return LAUNCH_OK();
 }
 
-int spk_launch_maxpool_bwd(const bf16_t* gy, const unsigned char* idx, bf16_t* gx, int n, int h, int w,
-                           int c, int k, int stride, int pad, int ho, int wo, hipStream_t s) {
+bool spk_maxpool_pair_ok(int h, int w, int k, int stride, int pad, int ho, int wo) {
+  return k == 3 && stride == 2 && pad == 1 && w % 2 == 0 && wo == w / 2 && ho == (h + 1) / 2;
+}
+
+int spk_launch_maxpool_bwd_form(const bf16_t* gy, const unsigned char* idx, bf16_t* gx, int n, int h, int w,
+                                int c, int k, int stride, int pad, int ho, int wo, bool pair, hipStream_t s) {
   const unsigned row_items = (unsigned)w * (c / 8);
   const dim3 grid((unsigned)n * h, std::min(65535u, (row_items + 255) / 256));
-  static const bool pair_on = !getenv("SPK_POOL_PAIR") || atoi(getenv("SPK_POOL_PAIR")) != 0;
-  if (k == 3 && stride == 2 && pad == 1 && pair_on && w % 2 == 0 && wo == w / 2 && ho == (h + 1) / 2) {
+  if (pair) {
+    if (!spk_maxpool_pair_ok(h, w, k, stride, pad, ho, wo)) return -2;
     const unsigned items = (unsigned)(w / 2) * (c / 8);
     hipLaunchKernelGGL(maxpool3s2_bwd_pair_kernel, dim3((unsigned)n * h, (items + 255) / 256), dim3(256), 0, s, gy, idx, gx,
                        h, w, c, ho, wo);
@@ -754,6 +758,13 @@ int spk_launch_maxpool_bwd(const bf16_t* gy, const unsigned char* idx, bf16_t* g
   else
     hipLaunchKernelGGL((maxpool_bwd_kernel<0, 0, 0>), grid, dim3(256), 0, s, gy, idx, gx, n, h, w, c, k, stride, pad, ho, wo);
   return LAUNCH_OK();
+}
+
+int spk_launch_maxpool_bwd(const bf16_t* gy, const unsigned char* idx, bf16_t* gx, int n, int h, int w,
+                           int c, int k, int stride, int pad, int ho, int wo, hipStream_t s) {
+  static const bool pair_on = !getenv("SPK_POOL_PAIR") || atoi(getenv("SPK_POOL_PAIR")) != 0;
+  return spk_launch_maxpool_bwd_form(gy, idx, gx, n, h, w, c, k, stride, pad, ho, wo,
+                                     pair_on && spk_maxpool_pair_ok(h, w, k, stride, pad, ho, wo), s);
 }
 
 int spk_launch_gavgpool_bwd(const float* gy, bf16_t* gx, int n, int hw, int c, hipStream_t s) {

@@ -116,6 +116,14 @@ SYMBOLS = {
     "spk_op_se_train_backward": (C.c_int, [_P] * 16 + [C.c_int] * 6 + [_P]),
     "spk_op_stem3_train": (C.c_int, [_P] * 5 + [C.c_int] * 6 + [_P]),
     "spk_op_mbconv_geometry": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)]),
+    "spk_op_linear": (C.c_int, [_P] * 4 + [C.c_int] * 3 + [_P]),
+    "spk_op_linear_backward": (C.c_int, [_P] * 6 + [C.c_int] * 4 + [_P]),
+    "spk_op_softmax": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, _P]),
+    "spk_op_cross_entropy": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "spk_op_maxpool": (C.c_int, [_P] * 3 + [C.c_int] * 8 + [_P]),
+    "spk_op_maxpool_backward": (C.c_int, [_P] * 3 + [C.c_int] * 8 + [_P]),
+    "spk_op_gavgpool": (C.c_int, [_P, _P] + [C.c_int] * 4 + [_P]),
+    "spk_op_gavgpool_backward": (C.c_int, [_P, _P] + [C.c_int] * 3 + [_P]),
     "spk_op_conv1x1": (C.c_int, [_P, _P, _P, _P, _P, _P] + [C.c_int] * 9 + [_P]),
     "spk_op_conv1x1_num_configs": (C.c_int, []),
     "spk_op_conv3x3": (C.c_int, [_P, _P, _P, _P, _P, _P] + [C.c_int] * 8 + [_P]),

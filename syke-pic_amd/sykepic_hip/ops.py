@@ -518,3 +518,108 @@ def stem3_train(x4, weight, c, dy=None, w_in=None):
         lib.check(so.spk_op_stem3_train(_p(_bf16c(x4)), _p(_f32c(weight)), _p(_bf16c(dy)) if dy is not None else None,
                                         _p(y), _p(dw), n, h, w, cin, cout, int(c), _stream(dev)))
     return {"y": y, "dw": dw}
+
+
+# ---- the classifier head, the loss and the pooling layers (csrc/head.hip, pointwise.hip, train_kernels.hip) ----
+def _h16c(t):
+    assert t.dtype in (torch.bfloat16, torch.float16) and t.is_contiguous() and t.is_cuda, \
+        "bf16 / fp16 contiguous device tensor expected"
+    return t
+
+
+def linear(x, w, b=None):
+    """y [N,out] = x [N,in] . w [out,in]^T + b (spk_op_linear: the launch of `spk_launch_linear_fwd`)."""
+    so = lib.load()
+    dev = x.device
+    n, fin = x.shape
+    fout = w.shape[0]
+    y = torch.full((n, fout), float("nan"), dtype=torch.float32, device=dev)   # poison: every element must be written
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_linear(_p(_f32c(x)), _p(_f32c(w)), _p(_f32c(b)), _p(y), n, fin, fout, _stream(dev)))
+    return y
+
+
+def linear_backward(gy, x, w, dw=None, db=None, dx=None, form=-1):
+    """The Linear layer's backward as a training step runs it (spk_op_linear_backward), into the caller's float32
+    buffers dw [out,in], db [out], dx [N,in]; None skips that gradient.  form: -1 production's GEMM, 0 MFMA, 1 FMA."""
+    so = lib.load()
+    dev = gy.device
+    n, fout = gy.shape
+    fin = x.shape[1] if x is not None else w.shape[1]
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_linear_backward(_p(_f32c(gy)), _p(_f32c(x)), _p(_f32c(w)), _p(_f32c(dw)), _p(_f32c(db)),
+                                            _p(_f32c(dx)), n, fin, fout, int(form), _stream(dev)))
+
+
+def softmax(z, base):
+    """p = softmax(z * log(base)) per row (spk_op_softmax)."""
+    so = lib.load()
+    dev = z.device
+    n, c = z.shape
+    p = torch.full((n, c), float("nan"), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_softmax(_p(_f32c(z)), _p(p), n, c, float(base), _stream(dev)))
+    return p
+
+
+def cross_entropy(z, labels, stats, dz=None):
+    """spk_op_cross_entropy: adds (sum of the row losses, correct rows) to stats [2] float32 and writes dz [N,c] (the
+    caller's buffer; None: no gradient)."""
+    so = lib.load()
+    dev = z.device
+    n, c = z.shape
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.is_cuda and labels.numel() == n
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_cross_entropy(_p(_f32c(z)), _p(labels), n, c, _p(_f32c(stats)), _p(_f32c(dz)), _stream(dev)))
+
+
+def maxpool(x, k, stride, pad, want_idx=False):
+    """MaxPool2d on x [N,H,W,C] bf16 / fp16 (spk_op_maxpool).  want_idx: the training kernel, which also returns the
+    saved taps [N,Ho,Wo,C] uint8; else the eval kernel.  Returns (y, idx or None)."""
+    so = lib.load()
+    dev = x.device
+    n, h, w, c = x.shape
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    y = torch.full((n, ho, wo, c), float("nan"), dtype=x.dtype, device=dev)
+    idx = torch.full((n, ho, wo, c), 255, dtype=torch.uint8, device=dev) if want_idx else None
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_maxpool(_p(_h16c(x)), _p(y), _p(idx), n, h, w, c, int(k), int(stride), int(pad),
+                                    int(x.dtype == torch.float16), _stream(dev)))
+    return y, idx
+
+
+def maxpool_backward(gy, idx, in_hw, k, stride, pad, form=-1):
+    """gx [N,H,W,C] bf16 from gy [N,Ho,Wo,C] bf16 and the saved taps (spk_op_maxpool_backward).  form: -1 production's
+    kernel, 0 per-pixel, 1 pixel-pair."""
+    so = lib.load()
+    dev = gy.device
+    n, _, _, c = gy.shape
+    h, w = in_hw
+    assert idx.dtype == torch.uint8 and idx.is_contiguous() and idx.shape == gy.shape
+    gx = torch.full((n, h, w, c), float("nan"), dtype=torch.bfloat16, device=dev)
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_maxpool_backward(_p(_bf16c(gy)), _p(idx), _p(gx), n, h, w, c, int(k), int(stride), int(pad),
+                                             int(form), _stream(dev)))
+    return gx
+
+
+def gavgpool(x):
+    """AdaptiveAvgPool2d(1) on x [N,HW,C] bf16 / fp16 -> float32 [N,C] (spk_op_gavgpool)."""
+    so = lib.load()
+    dev = x.device
+    n, hw, c = x.shape
+    y = torch.full((n, c), float("nan"), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_gavgpool(_p(_h16c(x)), _p(y), n, hw, c, int(x.dtype == torch.float16), _stream(dev)))
+    return y
+
+
+def gavgpool_backward(gy, hw):
+    """gx [N,HW,C] bf16 = gy [N,C] / HW (spk_op_gavgpool_backward)."""
+    so = lib.load()
+    dev = gy.device
+    n, c = gy.shape
+    gx = torch.full((n, hw, c), float("nan"), dtype=torch.bfloat16, device=dev)
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_gavgpool_backward(_p(_f32c(gy)), _p(gx), n, int(hw), c, _stream(dev)))
+    return gx

@@ -35,6 +35,38 @@ def test_error_reporting_without_gpu_or_bad_args():
     h = ctypes.c_void_p()
     rc = so.spk_model_create(None, 0, 3, 50, 0, ctypes.byref(h))
     assert rc != 0 and so.spk_last_error()
+    # the head / loss / pooling hooks check their arguments before any HIP call: one rejected call each
+    ARG, UNSUPPORTED = -1, -4      # SPK_ERR_ARG, SPK_ERR_UNSUPPORTED
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    bad = [
+        ("spk_op_linear", ARG, (None, p, None, p, 1, 4, 4, None)),
+        ("spk_op_linear", ARG, (p, p, None, p, 0, 4, 4, None)),
+        ("spk_op_linear_backward", ARG, (p, None, p, p, None, None, 1, 4, 4, -1, None)),      # dw without x
+        ("spk_op_linear_backward", ARG, (p, p, p, None, None, None, 1, 4, 4, -1, None)),      # nothing to compute
+        ("spk_op_linear_backward", ARG, (p, p, p, p, p, p, 1, 4, 4, 2, None)),                # form
+        ("spk_op_softmax", ARG, (p, None, 1, 4, 1.3, None)),
+        ("spk_op_softmax", ARG, (p, p, 1, 4, 0.0, None)),
+        ("spk_op_cross_entropy", ARG, (p, p, 1, 4, None, None, None)),
+        ("spk_op_cross_entropy", ARG, (p, p, 0, 4, p, None, None)),
+        ("spk_op_maxpool", ARG, (p, p, None, 1, 4, 4, 12, 3, 2, 1, 0, None)),                 # c % 8
+        ("spk_op_maxpool", ARG, (p, None, None, 1, 4, 4, 8, 3, 2, 1, 0, None)),
+        ("spk_op_maxpool", ARG, (p, p, None, 1, 4, 4, 8, 3, 2, 1, 2, None)),                  # dtype
+        ("spk_op_maxpool", UNSUPPORTED, (p, p, p, 1, 40, 40, 8, 16, 2, 1, 0, None)),          # k * k > 255
+        ("spk_op_maxpool", UNSUPPORTED, (p, p, p, 1, 4, 4, 8, 3, 2, 1, 1, None)),             # saved taps in fp16
+        ("spk_op_maxpool_backward", ARG, (p, None, p, 1, 4, 4, 8, 3, 2, 1, -1, None)),
+        ("spk_op_maxpool_backward", ARG, (p, p, p, 1, 4, 4, 12, 3, 2, 1, -1, None)),          # c % 8
+        ("spk_op_maxpool_backward", UNSUPPORTED, (p, p, p, 1, 4, 5, 8, 3, 2, 1, 1, None)),    # pair kernel, odd width
+        ("spk_op_maxpool_backward", UNSUPPORTED, (p, p, p, 1, 4, 4, 8, 3, 1, 1, 1, None)),    # pair kernel, stride 1
+        ("spk_op_gavgpool", ARG, (p, p, 0, 4, 8, 0, None)),
+        ("spk_op_gavgpool", ARG, (p, p, 1, 4, 12, 0, None)),
+        ("spk_op_gavgpool_backward", ARG, (None, p, 1, 4, 8, None)),
+        ("spk_op_gavgpool_backward", ARG, (p, p, 1, 4, 12, None)),
+    ]
+    for name, want, args in bad:
+        rc = getattr(so, name)(*args)
+        assert rc == want, f"{name}{args[-9:]}: rc {rc}, expected {want}"
+        assert name[4:].encode() in so.spk_last_error(), (name, so.spk_last_error())
 
 
 def test_struct_layouts_match_header():
