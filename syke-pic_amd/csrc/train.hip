@@ -43,7 +43,7 @@ struct ConvTrain {
   size_t se_off = 0;        // squeeze-excitation: pooled [n][C], u1 [n][S], h1 [n][S], gate [n][C] floats kept for backward,
                             // then du2 [n][C], du1 [n][S]: per layer, the side stream's weight-gradient kernel reads them
   size_t rs_off = 0;        // stochastic depth: per-image factor [n] floats (0: none)
-  size_t dy_off = 0;        // this layer's own pre-BatchNorm gradient tensor dy (side-stream weight gradients read it)
+  size_t dy_off = 0;        // this layer's own pre-BatchNorm gradient tensor dy (the weight gradient reads it, on either stream)
 };
 
 struct PhaseProf {
@@ -79,14 +79,13 @@ struct TrainState {
   void* arena = nullptr;
   int cap_n = 0, cap_h = 0, cap_w = 0;
   std::vector<size_t> goff;   // gradient tensor per activation id
-  size_t dy_off = 0, idx_off = 0, part_off = 0, coef_off = 0, slab_off = 0, tmp_off = 0;
+  size_t idx_off = 0, part_off = 0, coef_off = 0, slab_off = 0, tmp_off = 0;
   size_t fpart_off = 0;    // BatchNorm-backward partial sums written by the dgrad epilogue of the consumer layer
   size_t se_tmp_off = 0;   // squeeze-excitation scratch shared by the layers (pool partials, gate / hidden gradients)
   // Weight gradients on a second stream (ResNets): wgrad(i) needs only the layer's input activation and dy(i), so it runs
   // beside dgrad(i) and the HBM-bound BatchNorm backward of the next layer instead of in front of them.  Every conv layer
-  // has its own dy tensor (ConvTrain::dy_off, round 4); with SPK_DY_PER_LAYER=0 dy is double buffered as before: bn_bwd of
-  // layer i-2 may then overwrite a buffer only after the wgrad that read it has finished (ev_dy_free).
-  size_t dy2_off = 0;
+  // has its own dy tensor (ConvTrain::dy_off), so the main stream never waits for the side stream inside a step: the
+  // events below only order dy(i) -> wgrad(i).
   // The step's LAST weight gradient (the first layer's: its dy is the last tensor the backward makes) runs on the side
   // stream while the main stream has nothing left to do.  Unless somebody reads the gradients in between, the step
   // returns WITHOUT waiting for it: spk_optim_step updates every other parameter first and joins the side stream in
@@ -97,11 +96,9 @@ struct TrainState {
   bool grads_exported = false;   // spk_model_grad_buffer handed the flat buffer out: always join at the end of the step
   hipEvent_t ev_side_pre = nullptr;   // side stream, in front of the tail weight gradient
   hipStream_t side = nullptr;
-  hipEvent_t ev_dy_ready[2] = {nullptr, nullptr};   // main: dy buffer written
-  hipEvent_t ev_dy_free[2] = {nullptr, nullptr};    // side: wgrad has read the dy buffer
+  hipEvent_t ev_dy_ready[2] = {nullptr, nullptr};   // main: a layer's dy written (alternating: dy_slot)
   hipEvent_t ev_side_done = nullptr;
   hipEvent_t ev_se = nullptr;                       // main: gate gradients of a squeeze-excitation layer written
-  bool dy_busy[2] = {false, false};
   int dy_slot = 0;
   size_t part_floats = 0, slab_floats = 0;
 
@@ -122,10 +119,8 @@ void spk_train_free(spk_model* m) {
   if (t->dwt) hipFree(t->dwt);
   if (t->unit) hipFree(t->unit);
   if (t->side) hipStreamDestroy(t->side);
-  for (int i = 0; i < 2; ++i) {
+  for (int i = 0; i < 2; ++i)
     if (t->ev_dy_ready[i]) hipEventDestroy(t->ev_dy_ready[i]);
-    if (t->ev_dy_free[i]) hipEventDestroy(t->ev_dy_free[i]);
-  }
   if (t->ev_side_done) hipEventDestroy(t->ev_side_done);
   if (t->ev_side_pre) hipEventDestroy(t->ev_side_pre);
   if (t->ev_se) hipEventDestroy(t->ev_se);
@@ -207,10 +202,7 @@ static int ensure_state(spk_model* m) {
     // the events order two streams of ONE device: no system-scope fence (SPK_EVENT_SYSFENCE=1 keeps it, for A/B runs)
     static const bool sysfence = getenv("SPK_EVENT_SYSFENCE") && atoi(getenv("SPK_EVENT_SYSFENCE")) != 0;
     const unsigned evf = hipEventDisableTiming | (sysfence ? 0u : (unsigned)hipEventDisableSystemFence);
-    for (int i = 0; i < 2; ++i) {
-      HIP_TRY(hipEventCreateWithFlags(&t->ev_dy_ready[i], evf));
-      HIP_TRY(hipEventCreateWithFlags(&t->ev_dy_free[i], evf));
-    }
+    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreateWithFlags(&t->ev_dy_ready[i], evf));
     HIP_TRY(hipEventCreateWithFlags(&t->ev_side_done, evf));
     HIP_TRY(hipEventCreateWithFlags(&t->ev_side_pre, evf));
     HIP_TRY(hipEventCreateWithFlags(&t->ev_se, evf));
@@ -227,7 +219,7 @@ static int plan_train(spk_model* m, int n, int h, int w) {
   HIP_TRY(hipStreamSynchronize(m->stream));
   if (t->arena) hipFree(t->arena);
   t->arena = nullptr;
-  size_t total = 0, max_conv = 0, max_slab = 0, max_part = 0, max_c = 0, max_se = 0;
+  size_t total = 0, max_slab = 0, max_part = 0, max_c = 0, max_se = 0;
   t->goff.assign(m->n_tensors, 0);
   for (int id = 0; id < m->n_tensors; ++id) {
     const TDim& d = m->tdims[id];
@@ -248,7 +240,6 @@ static int plan_train(spk_model* m, int n, int h, int w) {
       total += al256(bytes);
       t->conv[i].mask_off = total;
       total += al256(bytes / 16);
-      max_conv = std::max(max_conv, bytes);
       const int M = n * o.h * o.w;
       if (L.d.kind == SPK_OP_DWCONV) {
         max_slab = std::max(max_slab, (size_t)spk_dw_wgrad_rows(M, C) * L.d.cout * L.d.k * L.d.k);
@@ -287,18 +278,14 @@ static int plan_train(spk_model* m, int n, int h, int w) {
       total += al256((size_t)n * o.c);
     }
   }
-  t->dy_off = total;      total += al256(max_conv);
-  t->dy2_off = total;     total += al256(max_conv);
-  // One dy tensor per conv layer (SPK_DY_PER_LAYER=0: the two shared buffers of rounds 3-4): the main stream then never waits
-  // for the weight-gradient stream to release a buffer - one barrier packet less in front of every BatchNorm backward,
-  // ResNet-50 22.97 -> 22.49 ms, EfficientNet-B4 27.93 -> 27.55 - and the weight gradients may lag as far as their own queue
-  // allows (5.6 GB at ResNet-50 batch 256 against 288 GB of HBM).  (Releasing the weight gradients of 2-6 layers behind ONE
-  // event record instead of one each was measured as well: 22.8-23.1 ms - the later start costs more than the packets.)
-  static const bool dy_per_layer = !getenv("SPK_DY_PER_LAYER") || atoi(getenv("SPK_DY_PER_LAYER")) != 0;
+  // One dy tensor per conv layer rather than two shared buffers: the main stream never waits for the weight-gradient stream
+  // to release a buffer - one barrier packet less in front of every BatchNorm backward, ResNet-50 22.97 -> 22.49 ms,
+  // EfficientNet-B4 27.93 -> 27.55 - and the weight gradients may lag as far as their own queue allows (5.6 GB at ResNet-50
+  // batch 256 against 288 GB of HBM).  (Releasing the weight gradients of 2-6 layers behind ONE event record instead of
+  // one each was measured as well: 22.8-23.1 ms - the later start costs more than the packets.)
   for (size_t i = 0; i < m->layers.size(); ++i) {
     const Layer& L = m->layers[i];
-    t->conv[i].dy_off = 0;
-    if (!dy_per_layer || (L.d.kind != SPK_OP_CONV && L.d.kind != SPK_OP_DWCONV)) continue;
+    if (L.d.kind != SPK_OP_CONV && L.d.kind != SPK_OP_DWCONV) continue;
     const TDim& o = m->tdims[L.d.dst];
     t->conv[i].dy_off = total;
     total += al256((size_t)n * o.h * o.w * o.c * 2);
@@ -489,6 +476,507 @@ int spk_conv_wgrad_reduce(const float* slabs, float* gw, int M, int cin, int cou
 static int grad_bucket_of(const spk_model* m, const Layer& L);
 static int grad_bucket_done(spk_model* m, int b);
 
+// ---------------------------------------------------------------------------
+// One training step: what its per-layer functions share.  The forward and backward loops of
+// spk_train_forward_backward own the order; every decision is taken by the layer function at the point of the loop
+// where it falls due, on the state below as it stands then.
+// ---------------------------------------------------------------------------
+struct StepCtx {
+  spk_model* m;
+  TrainState* t;
+  hipStream_t s;
+  int n, w;                      // batch size, width of the input image (the 3x3 stem reads the input tensor itself)
+  float *part, *fpart, *coef, *tmp, *slabs;
+  unsigned char* pool_idx;
+  bool side_on;                  // weight gradients on the side stream (the per-phase profile times a single-stream step)
+  bool tail_ok;                  // the step may return without waiting for its last weight gradient (TrainState::tail_pending)
+  int first_conv, tail_layer;
+  std::vector<char> has_grad;    // dL/dt has been written
+  std::vector<char> needs;       // dL/dt changes something (grads_needed)
+  // BatchNorm-backward reductions that ride on the data-gradient kernel of the consumer (conv_igemm.hip, bnb_raw): when the
+  // stride-1 dgrad of layer i is the LAST writer of dL/dt (no consumer of t comes earlier in the graph) and t is the output
+  // of conv layer P, its epilogue holds the complete fp32 gradient and emits P's per-channel sums; P's own reduce pass -
+  // one more read of the gradient and of P's raw output - is skipped.  fused_tiles[P] = partial rows waiting in `fpart`.
+  std::vector<int> fused_tiles;
+  // deferred[t] = i: the block-closing conv i did NOT write its shortcut gradient dz into dL/dt; the fused data gradient of
+  // t's other consumer (the block's first 1x1 conv) reads dz from its source - conv i's output gradient and ReLU bits - and
+  // writes the complete tensor once (one write and one read of every identity-block trunk gradient less)
+  std::vector<int> deferred;
+  int fpart_owner;               // the layer whose sums `fpart` holds, or -1
+  int squeezed;                  // the squeeze-excitation layer whose pooled means the depthwise layer before it has written
+};
+
+// needs[t]: some parameter that the optimizer updates sits at or upstream of the layer that produces tensor t, i.e.
+// dL/dt changes something.  Gradients nobody needs are not computed, as with autograd.  NOTE the reference's own
+// schedule never gets there: its freeze() (sykepic/train/network.py:149-172) leaves every BatchNorm of the "frozen"
+// base trainable and train.py:131 puts them into param group 0, so the data-gradient chain runs down to the stem's
+// BatchNorm from the first epoch on (head-only epochs: 20.3 ms per ResNet-50 step at batch 256 against 26.9 with
+// every conv trainable - only the weight-gradient kernels drop out).  The cut applies when a caller freezes the
+// BatchNorm layers as well, or keeps them out of the optimizer.  A parameter counts when it requires grad AND an
+// optimizer group holds it (without any optimizer every trainable tensor is in group 0).
+static std::vector<char> grads_needed(const spk_model* m) {
+  std::vector<char> needs(m->n_tensors, 0);
+  bool any_group = false;
+  for (const Param& p : m->params) any_group |= p.trainable && p.group >= 0;
+  auto trainable = [&](const Layer& Q) {
+    for (int pi : {Q.p_w, Q.p_g, Q.p_b, Q.p_w2, Q.p_b2})
+      if (pi >= 0 && m->params[pi].requires_grad && (!any_group || m->params[pi].group >= 0)) return true;
+    return false;
+  };
+  for (const Layer& Q : m->layers)
+    needs[Q.d.dst] = trainable(Q) || needs[Q.d.src] || (Q.d.kind == SPK_OP_CONV && Q.d.res >= 0 && needs[Q.d.res]);
+  return needs;
+}
+
+// SPK_BNB_FUSE (StepCtx::fused_tiles): bit 0 = 1x1 consumers that accumulate into a trunk gradient, bit 1 = other 1x1
+// consumers, bit 2 = 3x3 consumers; 0 = never (every BatchNorm backward runs its own reduce pass).  Default 3, measured per
+// category on one box (ResNet-50 step, ms): none 23.54 | trunk 23.11 | other 1x1 23.48 | 3x3 23.77 | trunk + other 1x1
+// 23.07 | all 23.11 - the trunk tensors are where the dropped pass is large (4 of a block's 6 tensor units) and the 1x1
+// data gradient short; a 3x3 data gradient is MFMA-bound with one block per CU, and the longer epilogue costs more than
+// the pass it replaces
+static int bnb_fuse_mask() {
+  static const int bnb_mask = getenv("SPK_BNB_FUSE") ? atoi(getenv("SPK_BNB_FUSE")) : 3;
+  return bnb_mask;
+}
+
+// producer layer whose reduction dgrad(i) can carry, or -1
+static int fuse_target(const StepCtx& c, int i) {
+  const spk_model* m = c.m;
+  const int bnb_mask = bnb_fuse_mask();
+  const Layer& L = m->layers[i];
+  if (!bnb_mask || m->effnet || L.d.stride != 1 || c.fpart_owner >= 0 || L.mode == CONV_MODE_GROUP) return -1;
+  const int cat = L.d.k == 1 ? (c.has_grad[L.d.src] || c.deferred[L.d.src] >= 0 ? 1 : 2) : 4;
+  if (!(bnb_mask & cat)) return -1;
+  int prod = -1;
+  for (int q = 0; q < i; ++q) {
+    const Layer& Q = m->layers[q];
+    if (Q.d.src == L.d.src || (Q.d.kind == SPK_OP_CONV && Q.d.res == L.d.src)) return -1;   // an earlier consumer writes later
+    if (Q.d.dst == L.d.src) prod = q;
+  }
+  if (prod < 0 || m->layers[prod].d.kind != SPK_OP_CONV || m->layers[prod].d.relu > 1) return -1;
+  return prod;
+}
+
+// may block-closing conv i leave its shortcut gradient to the data gradient of the tensor's other consumer?
+static bool can_defer(const StepCtx& c, int i) {
+  const spk_model* m = c.m;
+  static const bool defer_on = !getenv("SPK_BNB_DEFER") || atoi(getenv("SPK_BNB_DEFER")) != 0;
+  const Layer& L = m->layers[i];
+  if (!defer_on || !(bnb_fuse_mask() & 1) || m->effnet || L.d.res < 0 || !L.d.relu || c.has_grad[L.d.res] || !c.needs[L.d.res]) return false;
+  const int tr = L.d.res, nl = (int)m->layers.size();
+  int other = -1, count = 0, prod = -1;
+  for (int q = 0; q < nl; ++q) {
+    const Layer& Q = m->layers[q];
+    if (Q.d.dst == tr) prod = q;
+    if (Q.d.src == tr || (Q.d.kind == SPK_OP_CONV && Q.d.res == tr)) { ++count; if (q != i) other = q; }
+  }
+  if (count != 2 || other < 0 || other > i || prod < 0 || prod > other) return false;
+  const Layer& Q = m->layers[other];
+  const Layer& P = m->layers[prod];
+  return Q.d.kind == SPK_OP_CONV && Q.mode == CONV_MODE_GENERIC && Q.d.src == tr && Q.d.k == 1 && Q.d.stride == 1 &&
+         P.d.kind == SPK_OP_CONV && P.d.relu <= 1;
+}
+
+// Squeeze-excitation layer i: its own floats (ConvTrain::se_off) - pooled [n][C], u1 [n][S], h1 [n][S], gate [n][C] kept for
+// backward, then dgate [n][C] (becomes du2 in place) and du1 [n][S] - and the scratch the layers share (TrainState::se_tmp_off):
+// pool partials [n][chunks][C], then dpool [n][C] and the hidden-gradient partials
+struct SeBufs {
+  float *pooled, *u1, *h1, *gate, *dgate, *du1, *scratch, *dpool;
+};
+static SeBufs se_bufs(const StepCtx& c, int i) {
+  const Layer& L = c.m->layers[i];
+  const TDim& o = c.m->tdims[L.d.dst];
+  const size_t nC = (size_t)c.n * o.c, nS = (size_t)c.n * L.d.k;
+  SeBufs b;
+  b.pooled = (float*)((char*)c.t->arena + c.t->conv[i].se_off);
+  b.u1 = b.pooled + nC;
+  b.h1 = b.u1 + nS;
+  b.gate = b.h1 + nS;
+  b.dgate = b.gate + nC;
+  b.du1 = b.dgate + nC;
+  b.scratch = (float*)((char*)c.t->arena + c.t->se_tmp_off);
+  b.dpool = b.scratch + nC * spk_se_chunks(o.h * o.w);
+  return b;
+}
+
+// ------------------------------ forward, layer by layer ------------------------------
+// conv (3x3 stem, grouped, implicit GEMM) + train-mode BatchNorm (+ shortcut, ReLU / SiLU, stochastic depth)
+static int conv_forward(StepCtx& c, int i) {
+  spk_model* m = c.m; TrainState* t = c.t; hipStream_t s = c.s;
+  Layer& L = m->layers[i];
+  const TDim& in = m->tdims[L.d.src];
+  const TDim& o = m->tdims[L.d.dst];
+  const int n = c.n;
+  const int C = o.c;   // channels as laid out (= cout for the ResNets)
+  const int M = n * o.h * o.w;
+  float* st = t->stats + t->conv[i].stat_off;
+  int m_tiles = 0;
+  if (L.mode == CONV_MODE_STEM3) {
+    K_TRY(spk_launch_stem3_train_fwd((const bf16_t*)m->T(0), m->P(L.p_w), t->RAW(i), n, in.h, c.w, in.w, L.d.cin,
+                                     L.d.cout, C, o.h, o.w, s, 1.0f / SPK_INPUT_SCALE), "stem3 fwd");
+    K_TRY(spk_launch_col_stats(t->RAW(i), c.part, M, C, &m_tiles, s), "col_stats");
+  } else if (L.mode == CONV_MODE_GROUP) {
+    K_TRY(spk_launch_group_fwd((const bf16_t*)m->T(L.d.src), m->P(L.p_w), nullptr, nullptr, t->RAW(i), n, in.h, in.w,
+                               C, L.groups, L.d.stride, 0, DT_BF16, s), "grouped conv fwd");
+    K_TRY(spk_launch_col_stats(t->RAW(i), c.part, M, C, &m_tiles, s), "col_stats");
+  } else {
+    ConvArgs a;
+    fill_conv(a, (const bf16_t*)m->T(L.d.src), t->wpack + t->conv[i].wfwd_off, t->RAW(i), n, in.h, in.w,
+              in.c, o.h, o.w, C, L.d.k, L.d.stride, L.d.pad, L.kpad);
+    a.stats = c.part;
+    K_TRY(spk_conv_launch(a, L.mode, s, &m_tiles), "conv");
+  }
+  mark(m, PH_CONV_FWD);
+  L.nbt += 1;
+  if (!m->effnet) {
+    K_TRY(spk_launch_bn_finalize(c.part, m_tiles, C, (double)M, m->P(L.p_g), m->P(L.p_b),
+                                 m->P(L.p_mean), m->P(L.p_var), st, st + C, st + 2 * C, st + 3 * C,
+                                 m->bn_eps, m->bn_momentum, c.tmp, s), "bn_finalize");
+    K_TRY(spk_launch_bn_apply(t->RAW(i), st + 2 * C, st + 3 * C,
+                              L.d.res >= 0 ? (const bf16_t*)m->T(L.d.res) : nullptr,
+                              (bf16_t*)m->T(L.d.dst), t->MASK(i), (size_t)M * C, C, L.d.relu, s), "bn_apply");
+  } else {
+    K_TRY(spk_launch_bna_finalize(c.part, m_tiles, C, L.d.cout, (double)M, m->P(L.p_g), m->P(L.p_b), m->P(L.p_mean),
+                                  m->P(L.p_var), st, m->bn_eps, m->bn_momentum, c.tmp, s), "bn_finalize");
+    float* rs = nullptr;
+    if (t->conv[i].rs_off) {   // StochasticDepth(p, "row") on the residual branch, train mode
+      rs = (float*)((char*)t->arena + t->conv[i].rs_off);
+      K_TRY(spk_launch_sd_rowscale(rs, n, L.d.p,
+                                   (m->seed * 0x100000001B3ull) ^ (t->steps << 12) ^ (unsigned long long)i, s),
+            "stochastic depth");
+    }
+    K_TRY(spk_launch_bna_apply(t->RAW(i), st + 2 * C, st + 3 * C,
+                               L.d.res >= 0 ? (const bf16_t*)m->T(L.d.res) : nullptr, rs, (bf16_t*)m->T(L.d.dst), M,
+                               C, o.h * o.w, L.d.relu, s), "bn_apply");
+  }
+  mark(m, PH_BN_FWD);
+  return SPK_OK;
+}
+
+// depthwise conv + train-mode BatchNorm + activation
+static int dwconv_forward(StepCtx& c, int i) {
+  spk_model* m = c.m; TrainState* t = c.t; hipStream_t s = c.s;
+  Layer& L = m->layers[i];
+  const TDim& in = m->tdims[L.d.src];
+  const TDim& o = m->tdims[L.d.dst];
+  const int n = c.n, nl = (int)m->layers.size();
+  const int C = o.c, M = n * o.h * o.w;
+  float* st = t->stats + t->conv[i].stat_off;
+  int nbk = 0;
+  // the eval path's kernel in bf16 or dw_fwd_kernel: spk_dw_fwd_form (train_effnet.hip)
+  K_TRY(spk_dw_train_forward((const bf16_t*)m->T(L.d.src), t->dwt + t->conv[i].dwt_off, t->unit, t->unit_c, t->RAW(i),
+                             n, in.h, in.w, C, L.d.k, L.d.stride, L.d.pad, o.h, o.w, s), "depthwise fwd");
+  K_TRY(spk_launch_col_stats(t->RAW(i), c.part, M, C, &nbk, s), "col_stats");
+  mark(m, PH_CONV_FWD);
+  L.nbt += 1;
+  K_TRY(spk_launch_bna_finalize(c.part, nbk, C, L.d.cout, (double)M, m->P(L.p_g), m->P(L.p_b), m->P(L.p_mean),
+                                m->P(L.p_var), st, m->bn_eps, m->bn_momentum, c.tmp, s), "bn_finalize");
+  if (i + 1 < nl && m->layers[i + 1].d.kind == SPK_OP_SE && m->layers[i + 1].d.src == L.d.dst) {
+    // the squeeze of the layer behind rides on this pass (per-chunk channel sums into the shared scratch; that
+    // layer's first gate kernel turns them into its pooled means)
+    K_TRY(spk_launch_bna_apply_pool(t->RAW(i), st + 2 * C, st + 3 * C, (bf16_t*)m->T(L.d.dst),
+                                    (float*)((char*)t->arena + t->se_tmp_off), n, o.h * o.w, C, L.d.relu, s),
+          "bn_apply + squeeze");
+    c.squeezed = i + 1;
+  } else {
+    K_TRY(spk_launch_bna_apply(t->RAW(i), st + 2 * C, st + 3 * C, nullptr, nullptr, (bf16_t*)m->T(L.d.dst), M, C,
+                               o.h * o.w, L.d.relu, s), "bn_apply");
+  }
+  mark(m, PH_BN_FWD);
+  return SPK_OK;
+}
+
+// s = sigmoid(fc2(silu(fc1(mean_hw(a))))) (MobileNetV3: hardsigmoid, relu), out = a * s; fp32 on the [n][C] vectors
+static int se_forward(StepCtx& c, int i) {
+  spk_model* m = c.m; hipStream_t s = c.s;
+  const Layer& L = m->layers[i];
+  const TDim& o = m->tdims[L.d.dst];
+  const int n = c.n;
+  const int C = o.c, Cl = L.d.cout, S = L.d.k, HW = o.h * o.w;
+  const SeBufs b = se_bufs(c, i);
+  const bf16_t* a = (const bf16_t*)m->T(L.d.src);
+  if (c.squeezed != i)
+    K_TRY(spk_launch_pool_rows(a, nullptr, b.scratch, n, HW, C, s), "se pool");
+  K_TRY(spk_launch_se_gate_fwd(b.scratch, spk_se_chunks(HW), 1.f / (float)HW, b.pooled, m->P(L.p_w), m->P(L.p_b), m->P(L.p_w2), m->P(L.p_b2), b.u1, b.h1, b.gate, n, C, Cl, S,
+                               s, L.d.relu == SPK_ACT_RELU ? 1 : 0), "se gates");
+  K_TRY(spk_launch_se_scale(a, b.gate, (bf16_t*)m->T(L.d.dst), n, HW, C, s), "se scale");
+  mark(m, PH_BN_FWD);
+  return SPK_OK;
+}
+
+// ------------------------------ backward, layer by layer ------------------------------
+// BatchNorm (+ activation, shortcut) backward of conv / depthwise layer i: dL/d(output) -> *dy, the layer's own
+// pre-BatchNorm gradient tensor, dgamma / dbeta, and the shortcut gradient unless it is deferred.  *slot names the
+// ev_dy_ready event recorded behind it (side stream on).
+static int bn_backward(StepCtx& c, int i, bf16_t** dy_out, int* slot_out) {
+  spk_model* m = c.m; TrainState* t = c.t; hipStream_t s = c.s;
+  const Layer& L = m->layers[i];
+  const TDim& o = m->tdims[L.d.dst];
+  const int C = o.c, M = c.n * o.h * o.w;   // C: channels as laid out
+  float* st = t->stats + t->conv[i].stat_off;
+  const Param& pg = m->params[L.p_g];
+  const Param& pb = m->params[L.p_b];
+  bf16_t* g_res = L.d.res >= 0 && c.needs[L.d.res] ? (bf16_t*)t->G(L.d.res) : nullptr;
+  const bool defer = L.d.kind == SPK_OP_CONV && g_res && can_defer(c, i);
+  if (defer) {   // the shortcut gradient is picked up at its source by the data gradient that completes dL/d(res)
+    g_res = nullptr;
+    c.deferred[L.d.res] = i;
+  }
+  float* dgam = pg.requires_grad ? t->gbuf + pg.off : nullptr;
+  float* dbet = pb.requires_grad ? t->gbuf + pb.off : nullptr;
+  bf16_t* dy = (bf16_t*)((char*)t->arena + t->conv[i].dy_off);
+  int slot = 0;
+  if (c.side_on) {
+    slot = t->dy_slot;
+    t->dy_slot ^= 1;
+  }
+  if (!m->effnet) {
+    const int pre = c.fused_tiles[i];   // sums already made by the dgrad that completed this layer's output gradient
+    K_TRY(spk_launch_bn_bwd((const bf16_t*)t->G(L.d.dst), t->MASK(i), t->RAW(i), st, st + C, m->P(L.p_g),
+                            pre ? c.fpart : c.part, c.coef, dgam, dbet, dy, g_res, g_res ? c.has_grad[L.d.res] : 0, M, C,
+                            L.d.relu, c.tmp, s, pre), "bn bwd");
+    if (pre) { c.fused_tiles[i] = 0; c.fpart_owner = -1; }
+  } else {
+    const float* rs = t->conv[i].rs_off ? (const float*)((char*)t->arena + t->conv[i].rs_off) : nullptr;
+    const bf16_t* g = (const bf16_t*)t->G(L.d.dst);
+    int nbk = 0;
+    K_TRY(spk_launch_bna_bwd_reduce(g, t->RAW(i), st + 2 * C, st + 3 * C, st, st + C, rs, c.part, M, C, o.h * o.w,
+                                    L.d.relu, &nbk, s), "bn bwd reduce");
+    K_TRY(spk_launch_bna_bwd_finalize(c.part, nbk, C, L.d.cout, (double)M, m->P(L.p_g), st + C, dgam, dbet, c.coef, c.tmp, s),
+          "bn bwd finalize");
+    K_TRY(spk_launch_bna_bwd_apply(g, t->RAW(i), st + 2 * C, st + 3 * C, st, st + C, c.coef, rs, dy, g_res,
+                                   g_res ? c.has_grad[L.d.res] : 0, M, C, o.h * o.w, L.d.relu, s), "bn bwd apply");
+  }
+  mark(m, PH_BN_BWD);
+  // (6-9 us of idle main queue behind every one of these records; attaching the event to the apply kernel's own
+  // completion - hipExtLaunchKernelGGL's stopEvent - leaves the same gap: measured in round 5, not kept)
+  if (c.side_on) HIP_TRY(hipEventRecord(t->ev_dy_ready[slot], s));
+  if (g_res) c.has_grad[L.d.res] = 1;
+  *dy_out = dy;
+  *slot_out = slot;
+  return SPK_OK;
+}
+
+// The stream a layer's weight gradient runs on: the side stream, beside this layer's dgrad and the next layer's BatchNorm
+// backward, once the layer's dy is written (ev_dy_ready[slot]); the model's own stream in single-stream steps.
+static int wgrad_stream(StepCtx& c, int slot, hipStream_t* ws) {
+  *ws = c.side_on ? c.t->side : c.s;
+  if (c.side_on) HIP_TRY(hipStreamWaitEvent(*ws, c.t->ev_dy_ready[slot], 0));
+  return SPK_OK;
+}
+
+static int dwconv_backward(StepCtx& c, int i, const bf16_t* dy, int slot) {
+  spk_model* m = c.m; TrainState* t = c.t; hipStream_t s = c.s;
+  const Layer& L = m->layers[i];
+  const TDim& in = m->tdims[L.d.src];
+  const TDim& o = m->tdims[L.d.dst];
+  const int n = c.n, C = o.c;
+  const Param& pw = m->params[L.p_w];
+  const float* wt = t->dwt + t->conv[i].dwt_off;
+  if (c.needs[L.d.src]) {
+    // stride 1: dx = depthwise conv of dy with the flipped window (the forward kernel); else the px / gather
+    // kernels: spk_dw_dgrad_form (train_effnet.hip)
+    K_TRY(spk_dw_train_dgrad(dy, wt, t->unit, t->unit_c, (bf16_t*)t->G(L.d.src), c.has_grad[L.d.src] != 0, n, in.h,
+                             in.w, C, L.d.k, L.d.stride, L.d.pad, o.h, o.w, s), "depthwise dgrad");
+    mark(m, PH_CONV_DGRAD);
+    c.has_grad[L.d.src] = 1;
+  }
+  if (pw.requires_grad) {
+    int rows = 0;
+    hipStream_t ws;
+    SPK_TRY(wgrad_stream(c, slot, &ws));
+    K_TRY(spk_launch_dw_wgrad((const bf16_t*)m->T(L.d.src), dy, c.slabs, n, in.h, in.w, C, L.d.cout, L.d.k,
+                              L.d.stride, L.d.pad, o.h, o.w, &rows, ws), "depthwise wgrad");
+    mark(m, PH_CONV_WGRAD);
+    K_TRY(spk_launch_slab_reduce(c.slabs, t->gbuf + pw.off, (size_t)L.d.cout * L.d.k * L.d.k, rows, ws),
+          "depthwise wgrad reduce");
+    mark(m, PH_WGRAD_REDUCE);
+  }
+  return SPK_OK;
+}
+
+// conv_group.hip on the fp32 master weights
+static int group_backward(StepCtx& c, int i, const bf16_t* dy, int slot) {
+  spk_model* m = c.m; TrainState* t = c.t; hipStream_t s = c.s;
+  const Layer& L = m->layers[i];
+  const TDim& in = m->tdims[L.d.src];
+  const int n = c.n, C = m->tdims[L.d.dst].c;
+  const Param& pw = m->params[L.p_w];
+  if (c.needs[L.d.src]) {
+    if (c.deferred[L.d.src] >= 0)
+      return tfail(SPK_ERR_STATE, std::string("deferred shortcut gradient cannot land in grouped conv ") + L.d.name);
+    K_TRY(spk_launch_group_dgrad(dy, m->P(L.p_w), (bf16_t*)t->G(L.d.src), c.has_grad[L.d.src] != 0, n, in.h, in.w, C,
+                                 L.groups, L.d.stride, DT_BF16, s), "grouped conv dgrad");
+    mark(m, PH_CONV_DGRAD);
+    c.has_grad[L.d.src] = 1;
+  }
+  if (pw.requires_grad) {
+    hipStream_t ws;
+    SPK_TRY(wgrad_stream(c, slot, &ws));
+    int chunks = 0;
+    K_TRY(spk_launch_group_wgrad((const bf16_t*)m->T(L.d.src), dy, c.slabs, n, in.h, in.w, C, L.groups, L.d.stride,
+                                 DT_BF16, &chunks, ws), "grouped conv wgrad");
+    mark(m, PH_CONV_WGRAD);
+    K_TRY(spk_launch_slab_reduce(c.slabs, t->gbuf + pw.off, (size_t)pw.numel, chunks, ws), "grouped conv wgrad reduce");
+    mark(m, PH_WGRAD_REDUCE);
+  }
+  return SPK_OK;
+}
+
+// data gradient: implicit GEMM over the dgrad weight image (stride 2: one launch per parity class)
+static int conv_dgrad(StepCtx& c, int i, const bf16_t* dy) {
+  spk_model* m = c.m; TrainState* t = c.t;
+  const Layer& L = m->layers[i];
+  const TDim& in = m->tdims[L.d.src];
+  const TDim& o = m->tdims[L.d.dst];
+  if (L.d.src == 0 || !c.needs[L.d.src]) return SPK_OK;
+  const int pi = fuse_target(c, i);
+  const int dsrc = c.deferred[L.d.src];
+  if (dsrc >= 0 && pi < 0)
+    return tfail(SPK_ERR_STATE, std::string("deferred shortcut gradient of ") + m->layers[dsrc].d.name + " has no fused data gradient to land in");
+  BnbFuse fz;
+  fz.res_src = nullptr;
+  fz.res_bits = nullptr;
+  if (pi >= 0) {
+    const Layer& P = m->layers[pi];
+    float* stp = t->stats + t->conv[pi].stat_off;
+    fz.raw = t->RAW(pi);
+    fz.mask = P.d.relu ? t->MASK(pi) : nullptr;
+    fz.mean = stp;
+    fz.invstd = stp + in.c;
+    fz.partials = c.fpart;
+    fz.tiles = 0;
+    if (dsrc >= 0) {
+      fz.res_src = (const bf16_t*)t->G(m->layers[dsrc].d.dst);
+      fz.res_bits = t->MASK(dsrc);
+      c.deferred[L.d.src] = -1;
+    }
+  }
+  SPK_TRY(spk_conv_dgrad_all(dy, t->wpack + t->conv[i].wdg_off, (bf16_t*)t->G(L.d.src), c.has_grad[L.d.src] != 0, c.n,
+                             o.h, o.w, o.c, in.h, in.w, in.c, L.d.k, L.d.stride, L.d.pad, c.s, pi >= 0 ? &fz : nullptr));
+  if (pi >= 0 && fz.tiles > 0) { c.fused_tiles[pi] = fz.tiles; c.fpart_owner = pi; }
+  mark(m, PH_CONV_DGRAD);
+  c.has_grad[L.d.src] = 1;
+  return SPK_OK;
+}
+
+// weight gradient of a 3x3-stem, 7x7-stem or implicit-GEMM conv: split-K slabs and their fixed-order sum
+static int conv_wgrad(StepCtx& c, int i, const bf16_t* dy, int slot) {
+  spk_model* m = c.m; TrainState* t = c.t;
+  const Layer& L = m->layers[i];
+  const TDim& in = m->tdims[L.d.src];
+  const TDim& o = m->tdims[L.d.dst];
+  const int n = c.n, C = o.c, M = n * o.h * o.w;
+  const Param& pw = m->params[L.p_w];
+  if (!pw.requires_grad) return SPK_OK;
+  float* gw = t->gbuf + pw.off;
+  hipStream_t ws;
+  if (L.mode == CONV_MODE_STEM3) {
+    int nbk = 0;
+    SPK_TRY(wgrad_stream(c, slot, &ws));
+    K_TRY(spk_launch_stem3_wgrad((const bf16_t*)m->T(0), dy, c.slabs, n, in.h, c.w, in.w, L.d.cin, L.d.cout, C, o.h,
+                                 o.w, &nbk, ws), "stem3 wgrad");
+    mark(m, PH_CONV_WGRAD);
+    K_TRY(spk_launch_slab_reduce(c.slabs, gw, (size_t)L.d.cout * 9 * L.d.cin, nbk, ws, 1.0f / SPK_INPUT_SCALE),
+          "stem3 wgrad reduce");
+    mark(m, PH_WGRAD_REDUCE);
+    return SPK_OK;
+  }
+  const bool stem = L.mode == CONV_MODE_STEM;
+  const int cin_t = stem ? L.d.cin : in.c;   // channels of the stored input tensor (the 7x7 stem reads NHWC4 itself)
+  if (c.side_on && c.tail_ok && L.d.src == 0 && i == c.first_conv) {   // the step's last weight gradient: see tail_pending
+    HIP_TRY(hipEventRecord(t->ev_side_pre, t->side));
+    c.tail_layer = i;
+  }
+  SPK_TRY(wgrad_stream(c, slot, &ws));
+  SPK_TRY(spk_conv_wgrad_slabs((const bf16_t*)m->T(L.d.src), dy, c.slabs, n, in.h, in.w, cin_t, o.h, o.w, C, L.d.k,
+                               L.d.stride, L.d.pad, stem, ws));
+  mark(m, PH_CONV_WGRAD);
+  if (!stem && (C != L.d.cout || cin_t != L.d.cin)) {   // padded GEMM: keep the layer's own rows / columns
+    int sp, pps;
+    spk_wgrad_plan(M, C, L.d.k * L.d.k * cin_t, &sp, &pps);
+    K_TRY(spk_launch_slab_reduce_sub(c.slabs, gw, L.d.cout, L.d.k * L.d.k, L.d.cin, C, cin_t, sp, ws),
+          "wgrad reduce (padded)");
+  } else {
+    SPK_TRY(spk_conv_wgrad_reduce(c.slabs, gw, M, cin_t, C, L.d.k, stem, ws, stem ? 1.0f / SPK_INPUT_SCALE : 1.0f));
+  }
+  mark(m, PH_WGRAD_REDUCE);
+  return SPK_OK;
+}
+
+// out = a * s(pool(a)):  da = g * s + W1^T[ silu'(u1) * W2^T[ s(1-s) * sum_hw(g * a) ] ] / HW
+static int se_backward(StepCtx& c, int i) {
+  spk_model* m = c.m; TrainState* t = c.t; hipStream_t s = c.s;
+  const Layer& L = m->layers[i];
+  const TDim& o = m->tdims[L.d.dst];
+  const int n = c.n;
+  const int C = o.c, Cl = L.d.cout, S = L.d.k, HW = o.h * o.w;
+  const SeBufs b = se_bufs(c, i);
+  const bf16_t* g = (const bf16_t*)t->G(L.d.dst);
+  const bf16_t* a = (const bf16_t*)m->T(L.d.src);
+  K_TRY(spk_launch_pool_rows(g, a, b.scratch, n, HW, C, s), "se dgate");
+  const Param &w1 = m->params[L.p_w], &b1 = m->params[L.p_b], &w2 = m->params[L.p_w2], &b2 = m->params[L.p_b2];
+  K_TRY(spk_launch_se_gate_bwd(b.scratch, spk_se_chunks(HW), b.dgate, b.gate, b.u1, m->P(L.p_w), m->P(L.p_w2), b.du1, b.dpool, b.dpool + (size_t)n * C, n, C, Cl,
+                               S, s, L.d.relu == SPK_ACT_RELU ? 1 : 0), "se gates bwd");
+  hipStream_t ws = s;
+  if (c.side_on && (w1.requires_grad || b1.requires_grad || w2.requires_grad || b2.requires_grad)) {
+    ws = t->side;   // du2 / du1 are this layer's own: nothing on the main stream waits for the kernel
+    HIP_TRY(hipEventRecord(t->ev_se, s));
+    HIP_TRY(hipStreamWaitEvent(ws, t->ev_se, 0));
+  }
+  K_TRY(spk_launch_se_wgrad(b.dgate, b.h1, b.du1, b.pooled, w1.requires_grad ? t->gbuf + w1.off : nullptr,
+                            b1.requires_grad ? t->gbuf + b1.off : nullptr,
+                            w2.requires_grad ? t->gbuf + w2.off : nullptr,
+                            b2.requires_grad ? t->gbuf + b2.off : nullptr, n, C, Cl, S, ws), "se wgrad");
+  K_TRY(spk_launch_se_bwd_apply(g, b.gate, b.dpool, (bf16_t*)t->G(L.d.src), n, HW, C, s), "se bwd apply");
+  mark(m, PH_BN_BWD);
+  c.has_grad[L.d.src] = 1;
+  return SPK_OK;
+}
+
+// train-mode BatchNorm2d needs more than one value per channel (torch raises the same ValueError, e.g. for a
+// last batch of ONE image whose feature map has shrunk to 1x1); a batch of one larger image trains, as in torch
+static int check_bn_counts(const spk_model* m, int n) {
+  for (const Layer& L : m->layers) {
+    const TDim& o = m->tdims[L.d.dst];
+    if ((L.d.kind == SPK_OP_CONV || L.d.kind == SPK_OP_DWCONV) && (long)n * o.h * o.w < 2)
+      return tfail(SPK_ERR_ARG, std::string("Expected more than 1 value per channel when training, got input size [") +
+                                    std::to_string(n) + ", " + std::to_string(L.d.cout) + ", " + std::to_string(o.h) +
+                                    ", " + std::to_string(o.w) + "] at " + L.d.bn);
+  }
+  return SPK_OK;
+}
+
+// the context of a step on the planned arena: nothing has a gradient yet but the logits
+static StepCtx step_begin(spk_model* m, int n, int w) {
+  TrainState* t = m->train;
+  const int nl = (int)m->layers.size();
+  // deferred join of the side stream (TrainState::tail_pending): single-process steps whose gradients nobody reads in place
+  static const bool tail_env = !getenv("SPK_TAIL_DEFER") || atoi(getenv("SPK_TAIL_DEFER")) != 0;
+  StepCtx c;
+  c.m = m; c.t = t; c.s = m->stream; c.n = n; c.w = w;
+  c.part = (float*)((char*)t->arena + t->part_off);
+  c.fpart = (float*)((char*)t->arena + t->fpart_off);
+  c.coef = (float*)((char*)t->arena + t->coef_off);
+  c.tmp = (float*)((char*)t->arena + t->tmp_off);
+  c.slabs = (float*)((char*)t->arena + t->slab_off);
+  c.pool_idx = (unsigned char*)((char*)t->arena + t->idx_off);
+  c.side_on = t->side != nullptr && !t->prof.on;
+  c.tail_ok = tail_env && c.side_on && !m->grad_cb && !t->grads_exported;
+  c.first_conv = c.tail_layer = -1;
+  for (int q = 0; q < nl && c.first_conv < 0; ++q)
+    if (m->layers[q].d.kind == SPK_OP_CONV || m->layers[q].d.kind == SPK_OP_DWCONV) c.first_conv = q;
+  c.has_grad.assign(m->n_tensors, 0);
+  c.has_grad[m->layers.back().d.dst] = 1;
+  c.needs = grads_needed(m);
+  c.fused_tiles.assign(nl, 0);
+  c.deferred.assign(m->n_tensors, -1);
+  c.fpart_owner = -1;
+  c.squeezed = -1;
+  t->dy_slot = 0;
+  return c;
+}
+
 extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, int h, int w, int layout,
                                           int dtype, const int64_t* y, float* stats, float* logits_out) {
   if (!m || !x || !y || !stats || n < 1) return tfail(SPK_ERR_ARG, "train step: bad arguments");
@@ -499,31 +987,14 @@ extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, in
   SPK_TRY(repack_weights(m));
   TrainState* t = m->train;
   hipStream_t s = m->stream;
-  // train-mode BatchNorm2d needs more than one value per channel (torch raises the same ValueError, e.g. for a
-  // last batch of ONE image whose feature map has shrunk to 1x1); a batch of one larger image trains, as in torch
-  for (const Layer& L : m->layers) {
-    const TDim& o = m->tdims[L.d.dst];
-    if ((L.d.kind == SPK_OP_CONV || L.d.kind == SPK_OP_DWCONV) && (long)n * o.h * o.w < 2)
-      return tfail(SPK_ERR_ARG, std::string("Expected more than 1 value per channel when training, got input size [") +
-                                    std::to_string(n) + ", " + std::to_string(L.d.cout) + ", " + std::to_string(o.h) +
-                                    ", " + std::to_string(o.w) + "] at " + L.d.bn);
-  }
+  SPK_TRY(check_bn_counts(m, n));
   m->act_dt = DT_BF16;
   // every activation is really written by this pass: spk_model_read_activation must not "recompute" tensors that an earlier
   // EVAL forward on this handle left to a fused kernel (stem + pool, shortcut conv, squeeze-excitation scaling)
   m->last_eval_nb = 0;
-  float* part = (float*)((char*)t->arena + t->part_off);
-  float* coef = (float*)((char*)t->arena + t->coef_off);
-  float* tmp = (float*)((char*)t->arena + t->tmp_off);
-  float* slabs = (float*)((char*)t->arena + t->slab_off);
-  bf16_t* dy = (bf16_t*)((char*)t->arena + t->dy_off);
-  bf16_t* const dy_bufs[2] = {dy, (bf16_t*)((char*)t->arena + t->dy2_off)};
-  const bool side_on = t->side != nullptr && !t->prof.on;   // (the per-phase profile times a single-stream step)
-  t->dy_busy[0] = t->dy_busy[1] = false;
-  t->dy_slot = 0;
-  unsigned char* pool_idx = (unsigned char*)((char*)t->arena + t->idx_off);
   const int nl = (int)m->layers.size();
-  int squeezed = -1;   // the squeeze-excitation layer whose pooled means the depthwise layer before it has written
+  const int last = m->layers.back().d.dst;
+  StepCtx c = step_begin(m, n, w);
 
   // ------------------------------ forward ------------------------------
   mark(m, -1);
@@ -532,101 +1003,21 @@ extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, in
   K_TRY(spk_launch_to_nhwc4(x, layout, dtype, n, m->in_chans, h, w, (bf16_t*)m->T(0), DT_BF16, s, SPK_INPUT_SCALE), "to_nhwc4");
   mark(m, PH_INPUT);
   for (int i = 0; i < nl; ++i) {
-    Layer& L = m->layers[i];
+    const Layer& L = m->layers[i];
     const TDim& in = m->tdims[L.d.src];
     const TDim& o = m->tdims[L.d.dst];
     switch (L.d.kind) {
-      case SPK_OP_CONV: {
-        const int C = o.c;   // channels as laid out (= cout for the ResNets)
-        const int M = n * o.h * o.w;
-        float* st = t->stats + t->conv[i].stat_off;
-        int m_tiles = 0;
-        if (L.mode == CONV_MODE_STEM3) {
-          K_TRY(spk_launch_stem3_train_fwd((const bf16_t*)m->T(0), m->P(L.p_w), t->RAW(i), n, in.h, w, in.w, L.d.cin,
-                                           L.d.cout, C, o.h, o.w, s, 1.0f / SPK_INPUT_SCALE), "stem3 fwd");
-          K_TRY(spk_launch_col_stats(t->RAW(i), part, M, C, &m_tiles, s), "col_stats");
-        } else if (L.mode == CONV_MODE_GROUP) {
-          K_TRY(spk_launch_group_fwd((const bf16_t*)m->T(L.d.src), m->P(L.p_w), nullptr, nullptr, t->RAW(i), n, in.h, in.w,
-                                     C, L.groups, L.d.stride, 0, DT_BF16, s), "grouped conv fwd");
-          K_TRY(spk_launch_col_stats(t->RAW(i), part, M, C, &m_tiles, s), "col_stats");
-        } else {
-          ConvArgs a;
-          fill_conv(a, (const bf16_t*)m->T(L.d.src), t->wpack + t->conv[i].wfwd_off, t->RAW(i), n, in.h, in.w,
-                    in.c, o.h, o.w, C, L.d.k, L.d.stride, L.d.pad, L.kpad);
-          a.stats = part;
-          K_TRY(spk_conv_launch(a, L.mode, s, &m_tiles), "conv");
-        }
-        mark(m, PH_CONV_FWD);
-        L.nbt += 1;
-        if (!m->effnet) {
-          K_TRY(spk_launch_bn_finalize(part, m_tiles, C, (double)M, m->P(L.p_g), m->P(L.p_b),
-                                       m->P(L.p_mean), m->P(L.p_var), st, st + C, st + 2 * C, st + 3 * C,
-                                       m->bn_eps, m->bn_momentum, tmp, s), "bn_finalize");
-          K_TRY(spk_launch_bn_apply(t->RAW(i), st + 2 * C, st + 3 * C,
-                                    L.d.res >= 0 ? (const bf16_t*)m->T(L.d.res) : nullptr,
-                                    (bf16_t*)m->T(L.d.dst), t->MASK(i), (size_t)M * C, C, L.d.relu, s), "bn_apply");
-        } else {
-          K_TRY(spk_launch_bna_finalize(part, m_tiles, C, L.d.cout, (double)M, m->P(L.p_g), m->P(L.p_b), m->P(L.p_mean),
-                                        m->P(L.p_var), st, m->bn_eps, m->bn_momentum, tmp, s), "bn_finalize");
-          float* rs = nullptr;
-          if (t->conv[i].rs_off) {   // StochasticDepth(p, "row") on the residual branch, train mode
-            rs = (float*)((char*)t->arena + t->conv[i].rs_off);
-            K_TRY(spk_launch_sd_rowscale(rs, n, L.d.p,
-                                         (m->seed * 0x100000001B3ull) ^ (t->steps << 12) ^ (unsigned long long)i, s),
-                  "stochastic depth");
-          }
-          K_TRY(spk_launch_bna_apply(t->RAW(i), st + 2 * C, st + 3 * C,
-                                     L.d.res >= 0 ? (const bf16_t*)m->T(L.d.res) : nullptr, rs, (bf16_t*)m->T(L.d.dst), M,
-                                     C, o.h * o.w, L.d.relu, s), "bn_apply");
-        }
-        mark(m, PH_BN_FWD);
+      case SPK_OP_CONV:
+        SPK_TRY(conv_forward(c, i));
         break;
-      }
-      case SPK_OP_DWCONV: {
-        const int C = o.c, M = n * o.h * o.w;
-        float* st = t->stats + t->conv[i].stat_off;
-        int nbk = 0;
-        // the eval path's kernel in bf16 or dw_fwd_kernel: spk_dw_fwd_form (train_effnet.hip)
-        K_TRY(spk_dw_train_forward((const bf16_t*)m->T(L.d.src), t->dwt + t->conv[i].dwt_off, t->unit, t->unit_c, t->RAW(i),
-                                   n, in.h, in.w, C, L.d.k, L.d.stride, L.d.pad, o.h, o.w, s), "depthwise fwd");
-        K_TRY(spk_launch_col_stats(t->RAW(i), part, M, C, &nbk, s), "col_stats");
-        mark(m, PH_CONV_FWD);
-        L.nbt += 1;
-        K_TRY(spk_launch_bna_finalize(part, nbk, C, L.d.cout, (double)M, m->P(L.p_g), m->P(L.p_b), m->P(L.p_mean),
-                                      m->P(L.p_var), st, m->bn_eps, m->bn_momentum, tmp, s), "bn_finalize");
-        if (i + 1 < nl && m->layers[i + 1].d.kind == SPK_OP_SE && m->layers[i + 1].d.src == L.d.dst) {
-          // the squeeze of the layer behind rides on this pass (per-chunk channel sums into the shared scratch; that
-          // layer's first gate kernel turns them into its pooled means)
-          K_TRY(spk_launch_bna_apply_pool(t->RAW(i), st + 2 * C, st + 3 * C, (bf16_t*)m->T(L.d.dst),
-                                          (float*)((char*)t->arena + t->se_tmp_off), n, o.h * o.w, C, L.d.relu, s),
-                "bn_apply + squeeze");
-          squeezed = i + 1;
-        } else {
-          K_TRY(spk_launch_bna_apply(t->RAW(i), st + 2 * C, st + 3 * C, nullptr, nullptr, (bf16_t*)m->T(L.d.dst), M, C,
-                                     o.h * o.w, L.d.relu, s), "bn_apply");
-        }
-        mark(m, PH_BN_FWD);
+      case SPK_OP_DWCONV:
+        SPK_TRY(dwconv_forward(c, i));
         break;
-      }
-      case SPK_OP_SE: {
-        // s = sigmoid(fc2(silu(fc1(mean_hw(a))))) (MobileNetV3: hardsigmoid, relu), out = a * s; fp32 on the [n][C] vectors
-        const int C = o.c, Cl = L.d.cout, S = L.d.k, HW = o.h * o.w;
-        float* pooled = (float*)((char*)t->arena + t->conv[i].se_off);
-        float* u1 = pooled + (size_t)n * C;
-        float* h1 = u1 + (size_t)n * S;
-        float* gate = h1 + (size_t)n * S;
-        float* scratch = (float*)((char*)t->arena + t->se_tmp_off);
-        const bf16_t* a = (const bf16_t*)m->T(L.d.src);
-        if (squeezed != i)
-          K_TRY(spk_launch_pool_rows(a, nullptr, scratch, n, HW, C, s), "se pool");
-        K_TRY(spk_launch_se_gate_fwd(scratch, spk_se_chunks(HW), 1.f / (float)HW, pooled, m->P(L.p_w), m->P(L.p_b), m->P(L.p_w2), m->P(L.p_b2), u1, h1, gate, n, C, Cl, S,
-                                     s, L.d.relu == SPK_ACT_RELU ? 1 : 0), "se gates");
-        K_TRY(spk_launch_se_scale(a, gate, (bf16_t*)m->T(L.d.dst), n, HW, C, s), "se scale");
-        mark(m, PH_BN_FWD);
+      case SPK_OP_SE:
+        SPK_TRY(se_forward(c, i));
         break;
-      }
       case SPK_OP_MAXPOOL:
-        K_TRY(spk_launch_maxpool_idx((const bf16_t*)m->T(L.d.src), (bf16_t*)m->T(L.d.dst), pool_idx, n, in.h,
+        K_TRY(spk_launch_maxpool_idx((const bf16_t*)m->T(L.d.src), (bf16_t*)m->T(L.d.dst), c.pool_idx, n, in.h,
                                      in.w, in.c, L.d.k, L.d.stride, L.d.pad, o.h, o.w, s), "maxpool");
         mark(m, PH_POOL_FWD);
         break;
@@ -655,7 +1046,6 @@ extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, in
   m->dirty = true;  // running statistics moved: the eval-BN fold is stale
 
   // ------------------------- loss + dlogits -------------------------
-  const int last = m->layers.back().d.dst;
   const float* logits = (const float*)m->T(last);
   K_TRY(spk_launch_ce(logits, y, n, m->num_classes, stats, (float*)t->G(last), s), "cross-entropy");
   mark(m, PH_LOSS);
@@ -663,347 +1053,72 @@ extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, in
     HIP_TRY(hipMemcpyAsync(logits_out, logits, (size_t)n * m->num_classes * 4, hipMemcpyDeviceToDevice, s));
 
   // ------------------------------ backward ------------------------------
-  std::vector<char> has_grad(m->n_tensors, 0);
-  has_grad[last] = 1;
-  // needs[t]: some parameter that the optimizer updates sits at or upstream of the layer that produces tensor t, i.e.
-  // dL/dt changes something.  Gradients nobody needs are not computed, as with autograd.  NOTE the reference's own
-  // schedule never gets there: its freeze() (sykepic/train/network.py:149-172) leaves every BatchNorm of the "frozen"
-  // base trainable and train.py:131 puts them into param group 0, so the data-gradient chain runs down to the stem's
-  // BatchNorm from the first epoch on (head-only epochs: 20.3 ms per ResNet-50 step at batch 256 against 26.9 with
-  // every conv trainable - only the weight-gradient kernels drop out).  The cut applies when a caller freezes the
-  // BatchNorm layers as well, or keeps them out of the optimizer.  A parameter counts when it requires grad AND an
-  // optimizer group holds it (without any optimizer every trainable tensor is in group 0).
-  std::vector<char> needs(m->n_tensors, 0);
-  bool any_group = false;
-  for (const Param& p : m->params) any_group |= p.trainable && p.group >= 0;
-  auto trainable = [&](const Layer& Q) {
-    for (int pi : {Q.p_w, Q.p_g, Q.p_b, Q.p_w2, Q.p_b2})
-      if (pi >= 0 && m->params[pi].requires_grad && (!any_group || m->params[pi].group >= 0)) return true;
-    return false;
-  };
-  for (const Layer& Q : m->layers)
-    needs[Q.d.dst] = trainable(Q) || needs[Q.d.src] || (Q.d.kind == SPK_OP_CONV && Q.d.res >= 0 && needs[Q.d.res]);
-  // BatchNorm-backward reductions that ride on the data-gradient kernel of the consumer (conv_igemm.hip, bnb_raw): when the
-  // stride-1 dgrad of layer i is the LAST writer of dL/dt (no consumer of t comes earlier in the graph) and t is the output
-  // of conv layer P, its epilogue holds the complete fp32 gradient and emits P's per-channel sums; P's own reduce pass -
-  // one more read of the gradient and of P's raw output - is skipped.  fused_tiles[P] = partial rows waiting in `fpart`.
-  // SPK_BNB_FUSE: bit 0 = 1x1 consumers that accumulate into a trunk gradient, bit 1 = other 1x1 consumers, bit 2 = 3x3
-  // consumers; 0 = never (every BatchNorm backward runs its own reduce pass).  Default 3, measured per category on one box
-  // (ResNet-50 step, ms): none 23.54 | trunk 23.11 | other 1x1 23.48 | 3x3 23.77 | trunk + other 1x1 23.07 | all 23.11 -
-  // the trunk tensors are where the dropped pass is large (4 of a block's 6 tensor units) and the 1x1 data gradient short;
-  // a 3x3 data gradient is MFMA-bound with one block per CU, and the longer epilogue costs more than the pass it replaces
-  static const int bnb_mask = getenv("SPK_BNB_FUSE") ? atoi(getenv("SPK_BNB_FUSE")) : 3;
-  const bool bnb_on = bnb_mask != 0;
-  std::vector<int> fused_tiles(nl, 0);
-  // deferred[t] = i: the block-closing conv i did NOT write its shortcut gradient dz into dL/dt; the fused data gradient of
-  // t's other consumer (the block's first 1x1 conv) reads dz from its source - conv i's output gradient and ReLU bits - and
-  // writes the complete tensor once (one write and one read of every identity-block trunk gradient less)
-  static const bool defer_on = !getenv("SPK_BNB_DEFER") || atoi(getenv("SPK_BNB_DEFER")) != 0;
-  std::vector<int> deferred(m->n_tensors, -1);
-  int fpart_owner = -1;
-  float* fpart = (float*)((char*)t->arena + t->fpart_off);
-  auto fuse_target = [&](int i) -> int {   // producer layer whose reduction dgrad(i) can carry, or -1
-    const Layer& L = m->layers[i];
-    if (!bnb_on || m->effnet || L.d.stride != 1 || fpart_owner >= 0 || L.mode == CONV_MODE_GROUP) return -1;
-    const int cat = L.d.k == 1 ? (has_grad[L.d.src] || deferred[L.d.src] >= 0 ? 1 : 2) : 4;
-    if (!(bnb_mask & cat)) return -1;
-    int prod = -1;
-    for (int q = 0; q < i; ++q) {
-      const Layer& Q = m->layers[q];
-      if (Q.d.src == L.d.src || (Q.d.kind == SPK_OP_CONV && Q.d.res == L.d.src)) return -1;   // an earlier consumer writes later
-      if (Q.d.dst == L.d.src) prod = q;
-    }
-    if (prod < 0 || m->layers[prod].d.kind != SPK_OP_CONV || m->layers[prod].d.relu > 1) return -1;
-    return prod;
-  };
-  // may block-closing conv i leave its shortcut gradient to the data gradient of the tensor's other consumer?
-  auto can_defer = [&](int i) -> bool {
-    const Layer& L = m->layers[i];
-    if (!defer_on || !(bnb_mask & 1) || m->effnet || L.d.res < 0 || !L.d.relu || has_grad[L.d.res] || !needs[L.d.res]) return false;
-    const int tr = L.d.res;
-    int other = -1, count = 0, prod = -1;
-    for (int q = 0; q < nl; ++q) {
-      const Layer& Q = m->layers[q];
-      if (Q.d.dst == tr) prod = q;
-      if (Q.d.src == tr || (Q.d.kind == SPK_OP_CONV && Q.d.res == tr)) { ++count; if (q != i) other = q; }
-    }
-    if (count != 2 || other < 0 || other > i || prod < 0 || prod > other) return false;
-    const Layer& Q = m->layers[other];
-    const Layer& P = m->layers[prod];
-    return Q.d.kind == SPK_OP_CONV && Q.mode == CONV_MODE_GENERIC && Q.d.src == tr && Q.d.k == 1 && Q.d.stride == 1 &&
-           P.d.kind == SPK_OP_CONV && P.d.relu <= 1;
-  };
-  // deferred join of the side stream (TrainState::tail_pending): single-process steps whose gradients nobody reads in place
-  static const bool tail_env = !getenv("SPK_TAIL_DEFER") || atoi(getenv("SPK_TAIL_DEFER")) != 0;
-  const bool tail_ok = tail_env && side_on && !m->grad_cb && !t->grads_exported;
-  int first_conv = -1, tail_layer = -1;
-  for (int q = 0; q < nl && first_conv < 0; ++q)
-    if (m->layers[q].d.kind == SPK_OP_CONV || m->layers[q].d.kind == SPK_OP_DWCONV) first_conv = q;
   int cur_bucket = 0;
   for (int i = nl - 1; i >= 0; --i) {
-    Layer& L = m->layers[i];
+    const Layer& L = m->layers[i];
     const TDim& in = m->tdims[L.d.src];
     const TDim& o = m->tdims[L.d.dst];
     if (m->grad_cb && (L.d.kind == SPK_OP_CONV || L.d.kind == SPK_OP_LINEAR)) {
       const int b = grad_bucket_of(m, L);
       while (cur_bucket < b) SPK_TRY(grad_bucket_done(m, cur_bucket++));   // backward has left that stage
     }
-    if (!has_grad[L.d.dst] || !needs[L.d.dst]) continue;
+    if (!c.has_grad[L.d.dst] || !c.needs[L.d.dst]) continue;
     switch (L.d.kind) {
-      case SPK_OP_LINEAR: {
-        const float* gy = (const float*)t->G(L.d.dst);
-        const float* xin = (const float*)m->T(L.d.src);
-        const int fin = L.d.cin, fout = L.d.cout;
-        K_TRY(spk_linear_backward(gy, xin, m->P(L.p_w),
+      case SPK_OP_LINEAR:
+        K_TRY(spk_linear_backward((const float*)t->G(L.d.dst), (const float*)m->T(L.d.src), m->P(L.p_w),
                                   m->params[L.p_w].requires_grad ? t->gbuf + m->params[L.p_w].off : nullptr,
                                   m->params[L.p_b].requires_grad ? t->gbuf + m->params[L.p_b].off : nullptr,
-                                  needs[L.d.src] ? (float*)t->G(L.d.src) : nullptr, n, fin, fout, -1, s), "linear backward");
-        if (needs[L.d.src]) has_grad[L.d.src] = 1;
+                                  c.needs[L.d.src] ? (float*)t->G(L.d.src) : nullptr, n, L.d.cin, L.d.cout, -1, s),
+              "linear backward");
+        if (c.needs[L.d.src]) c.has_grad[L.d.src] = 1;
         mark(m, PH_HEAD_BWD);
         break;
-      }
       case SPK_OP_DROPOUT:
         K_TRY(spk_launch_dropout_bwd((const float*)t->G(L.d.dst), t->MASK(i), (float*)t->G(L.d.src), (size_t)n * in.c,
                                      L.d.p, s), "dropout bwd");
         mark(m, PH_HEAD_BWD);
-        has_grad[L.d.src] = 1;
+        c.has_grad[L.d.src] = 1;
         break;
       case SPK_OP_GAVGPOOL:
         K_TRY(spk_launch_gavgpool_bwd((const float*)t->G(L.d.dst), (bf16_t*)t->G(L.d.src), n, in.h * in.w,
                                       in.c, s), "avgpool bwd");
         mark(m, PH_POOL_BWD);
-        has_grad[L.d.src] = 1;
+        c.has_grad[L.d.src] = 1;
         break;
       case SPK_OP_MAXPOOL:
-        K_TRY(spk_launch_maxpool_bwd((const bf16_t*)t->G(L.d.dst), pool_idx, (bf16_t*)t->G(L.d.src), n, in.h,
+        K_TRY(spk_launch_maxpool_bwd((const bf16_t*)t->G(L.d.dst), c.pool_idx, (bf16_t*)t->G(L.d.src), n, in.h,
                                      in.w, in.c, L.d.k, L.d.stride, L.d.pad, o.h, o.w, s), "maxpool bwd");
         mark(m, PH_POOL_BWD);
-        has_grad[L.d.src] = 1;
+        c.has_grad[L.d.src] = 1;
         break;
       case SPK_OP_CONV:
       case SPK_OP_DWCONV: {
-        const int C = o.c, M = n * o.h * o.w;   // C: channels as laid out
-        float* st = t->stats + t->conv[i].stat_off;
-        const Param& pg = m->params[L.p_g];
-        const Param& pb = m->params[L.p_b];
-        bf16_t* g_res = L.d.res >= 0 && needs[L.d.res] ? (bf16_t*)t->G(L.d.res) : nullptr;
-        const bool defer = L.d.kind == SPK_OP_CONV && g_res && can_defer(i);
-        if (defer) {   // the shortcut gradient is picked up at its source by the data gradient that completes dL/d(res)
-          g_res = nullptr;
-          deferred[L.d.res] = i;
-        }
-        float* dgam = pg.requires_grad ? t->gbuf + pg.off : nullptr;
-        float* dbet = pb.requires_grad ? t->gbuf + pb.off : nullptr;
+        bf16_t* dy = nullptr;
         int slot = 0;
-        if (side_on) {   // this layer's dy buffer: free once the side-stream wgrad of two layers ago has read it
-          slot = t->dy_slot;
-          t->dy_slot ^= 1;
-          if (t->conv[i].dy_off) {   // its own tensor: nothing to wait for (the event ring below only orders dy -> wgrad)
-            dy = (bf16_t*)((char*)t->arena + t->conv[i].dy_off);
-          } else {
-            dy = dy_bufs[slot];
-            if (t->dy_busy[slot]) HIP_TRY(hipStreamWaitEvent(s, t->ev_dy_free[slot], 0));
-          }
-        }
-        if (!m->effnet) {
-          const int pre = fused_tiles[i];   // sums already made by the dgrad that completed this layer's output gradient
-          K_TRY(spk_launch_bn_bwd((const bf16_t*)t->G(L.d.dst), t->MASK(i), t->RAW(i), st, st + C, m->P(L.p_g),
-                                  pre ? fpart : part, coef, dgam, dbet, dy, g_res, g_res ? has_grad[L.d.res] : 0, M, C,
-                                  L.d.relu, tmp, s, pre), "bn bwd");
-          if (pre) { fused_tiles[i] = 0; fpart_owner = -1; }
-        } else {
-          const float* rs = t->conv[i].rs_off ? (const float*)((char*)t->arena + t->conv[i].rs_off) : nullptr;
-          const bf16_t* g = (const bf16_t*)t->G(L.d.dst);
-          int nbk = 0;
-          K_TRY(spk_launch_bna_bwd_reduce(g, t->RAW(i), st + 2 * C, st + 3 * C, st, st + C, rs, part, M, C, o.h * o.w,
-                                          L.d.relu, &nbk, s), "bn bwd reduce");
-          K_TRY(spk_launch_bna_bwd_finalize(part, nbk, C, L.d.cout, (double)M, m->P(L.p_g), st + C, dgam, dbet, coef, tmp, s),
-                "bn bwd finalize");
-          K_TRY(spk_launch_bna_bwd_apply(g, t->RAW(i), st + 2 * C, st + 3 * C, st, st + C, coef, rs, dy, g_res,
-                                         g_res ? has_grad[L.d.res] : 0, M, C, o.h * o.w, L.d.relu, s), "bn bwd apply");
-        }
-        mark(m, PH_BN_BWD);
-        // (6-9 us of idle main queue behind every one of these records; attaching the event to the apply kernel's own
-        // completion - hipExtLaunchKernelGGL's stopEvent - leaves the same gap: measured in round 5, not kept)
-        if (side_on) HIP_TRY(hipEventRecord(t->ev_dy_ready[slot], s));
-        if (g_res) has_grad[L.d.res] = 1;
-        const Param& pw = m->params[L.p_w];
+        SPK_TRY(bn_backward(c, i, &dy, &slot));
         if (L.d.kind == SPK_OP_DWCONV) {
-          const float* wt = t->dwt + t->conv[i].dwt_off;
-          if (needs[L.d.src]) {
-            // stride 1: dx = depthwise conv of dy with the flipped window (the forward kernel); else the px / gather
-            // kernels: spk_dw_dgrad_form (train_effnet.hip)
-            K_TRY(spk_dw_train_dgrad(dy, wt, t->unit, t->unit_c, (bf16_t*)t->G(L.d.src), has_grad[L.d.src] != 0, n, in.h,
-                                     in.w, C, L.d.k, L.d.stride, L.d.pad, o.h, o.w, s), "depthwise dgrad");
-            mark(m, PH_CONV_DGRAD);
-            has_grad[L.d.src] = 1;
-          }
-          if (pw.requires_grad) {
-            int rows = 0;
-            const hipStream_t ws = side_on ? t->side : s;   // weight gradients: second stream (see the conv case below)
-            if (side_on) HIP_TRY(hipStreamWaitEvent(ws, t->ev_dy_ready[slot], 0));
-            K_TRY(spk_launch_dw_wgrad((const bf16_t*)m->T(L.d.src), dy, slabs, n, in.h, in.w, C, L.d.cout, L.d.k,
-                                      L.d.stride, L.d.pad, o.h, o.w, &rows, ws), "depthwise wgrad");
-            mark(m, PH_CONV_WGRAD);
-            K_TRY(spk_launch_slab_reduce(slabs, t->gbuf + pw.off, (size_t)L.d.cout * L.d.k * L.d.k, rows, ws),
-                  "depthwise wgrad reduce");
-            if (side_on) {
-              if (!t->conv[i].dy_off) {
-                HIP_TRY(hipEventRecord(t->ev_dy_free[slot], ws));
-                t->dy_busy[slot] = true;
-              }
-            }
-            mark(m, PH_WGRAD_REDUCE);
-          }
-          break;
-        }
-        if (L.mode == CONV_MODE_GROUP) {   // conv_group.hip on the fp32 master weights
-          if (needs[L.d.src]) {
-            if (deferred[L.d.src] >= 0)
-              return tfail(SPK_ERR_STATE, std::string("deferred shortcut gradient cannot land in grouped conv ") + L.d.name);
-            K_TRY(spk_launch_group_dgrad(dy, m->P(L.p_w), (bf16_t*)t->G(L.d.src), has_grad[L.d.src] != 0, n, in.h, in.w, C,
-                                         L.groups, L.d.stride, DT_BF16, s), "grouped conv dgrad");
-            mark(m, PH_CONV_DGRAD);
-            has_grad[L.d.src] = 1;
-          }
-          if (pw.requires_grad) {
-            const hipStream_t ws = side_on ? t->side : s;
-            if (side_on) HIP_TRY(hipStreamWaitEvent(ws, t->ev_dy_ready[slot], 0));
-            int chunks = 0;
-            K_TRY(spk_launch_group_wgrad((const bf16_t*)m->T(L.d.src), dy, slabs, n, in.h, in.w, C, L.groups, L.d.stride,
-                                         DT_BF16, &chunks, ws), "grouped conv wgrad");
-            mark(m, PH_CONV_WGRAD);
-            K_TRY(spk_launch_slab_reduce(slabs, t->gbuf + pw.off, (size_t)pw.numel, chunks, ws), "grouped conv wgrad reduce");
-            if (side_on && !t->conv[i].dy_off) {
-              HIP_TRY(hipEventRecord(t->ev_dy_free[slot], ws));
-              t->dy_busy[slot] = true;
-            }
-            mark(m, PH_WGRAD_REDUCE);
-          }
-          break;
-        }
-        if (L.d.src != 0 && needs[L.d.src]) {
-          // data gradient: implicit GEMM over the dgrad weight image (stride 2: one launch per parity class)
-          const int pi = fuse_target(i);
-          const int dsrc = deferred[L.d.src];
-          if (dsrc >= 0 && pi < 0)
-            return tfail(SPK_ERR_STATE, std::string("deferred shortcut gradient of ") + m->layers[dsrc].d.name + " has no fused data gradient to land in");
-          BnbFuse fz;
-          fz.res_src = nullptr;
-          fz.res_bits = nullptr;
-          if (pi >= 0) {
-            const Layer& P = m->layers[pi];
-            float* stp = t->stats + t->conv[pi].stat_off;
-            fz.raw = t->RAW(pi);
-            fz.mask = P.d.relu ? t->MASK(pi) : nullptr;
-            fz.mean = stp;
-            fz.invstd = stp + in.c;
-            fz.partials = fpart;
-            fz.tiles = 0;
-            if (dsrc >= 0) {
-              fz.res_src = (const bf16_t*)t->G(m->layers[dsrc].d.dst);
-              fz.res_bits = t->MASK(dsrc);
-              deferred[L.d.src] = -1;
-            }
-          }
-          SPK_TRY(spk_conv_dgrad_all(dy, t->wpack + t->conv[i].wdg_off, (bf16_t*)t->G(L.d.src), has_grad[L.d.src] != 0, n,
-                                     o.h, o.w, C, in.h, in.w, in.c, L.d.k, L.d.stride, L.d.pad, s, pi >= 0 ? &fz : nullptr));
-          if (pi >= 0 && fz.tiles > 0) { fused_tiles[pi] = fz.tiles; fpart_owner = pi; }
-          mark(m, PH_CONV_DGRAD);
-          has_grad[L.d.src] = 1;
-        }
-        if (pw.requires_grad) {
-          float* gw = t->gbuf + pw.off;
-          if (L.mode == CONV_MODE_STEM3) {
-            int nbk = 0;
-            const hipStream_t ws3 = side_on ? t->side : s;
-            if (side_on) HIP_TRY(hipStreamWaitEvent(ws3, t->ev_dy_ready[slot], 0));
-            K_TRY(spk_launch_stem3_wgrad((const bf16_t*)m->T(0), dy, slabs, n, in.h, w, in.w, L.d.cin, L.d.cout, C, o.h,
-                                         o.w, &nbk, ws3), "stem3 wgrad");
-            mark(m, PH_CONV_WGRAD);
-            K_TRY(spk_launch_slab_reduce(slabs, gw, (size_t)L.d.cout * 9 * L.d.cin, nbk, ws3, 1.0f / SPK_INPUT_SCALE),
-                  "stem3 wgrad reduce");
-            if (side_on) {
-              if (!t->conv[i].dy_off) {
-                HIP_TRY(hipEventRecord(t->ev_dy_free[slot], ws3));
-                t->dy_busy[slot] = true;
-              }
-            }
-            mark(m, PH_WGRAD_REDUCE);
-            break;
-          }
-          const bool stem = L.mode == CONV_MODE_STEM;
-          const int cin_t = stem ? L.d.cin : in.c;   // channels of the stored input tensor (the 7x7 stem reads NHWC4 itself)
-          // ResNets: on the second stream, beside this layer's dgrad and the next layer's BatchNorm backward
-          const hipStream_t ws = side_on ? t->side : s;
-          if (side_on && tail_ok && L.d.src == 0 && i == first_conv) {   // the step's last weight gradient: see tail_pending
-            HIP_TRY(hipEventRecord(t->ev_side_pre, ws));
-            tail_layer = i;
-          }
-          if (side_on) HIP_TRY(hipStreamWaitEvent(ws, t->ev_dy_ready[slot], 0));
-          SPK_TRY(spk_conv_wgrad_slabs((const bf16_t*)m->T(L.d.src), dy, slabs, n, in.h, in.w, cin_t, o.h, o.w, C, L.d.k,
-                                       L.d.stride, L.d.pad, stem, ws));
-          mark(m, PH_CONV_WGRAD);
-          if (!stem && (C != L.d.cout || cin_t != L.d.cin)) {   // padded GEMM: keep the layer's own rows / columns
-            int sp, pps;
-            spk_wgrad_plan(M, C, L.d.k * L.d.k * cin_t, &sp, &pps);
-            K_TRY(spk_launch_slab_reduce_sub(slabs, gw, L.d.cout, L.d.k * L.d.k, L.d.cin, C, cin_t, sp, ws),
-                  "wgrad reduce (padded)");
-          } else {
-            SPK_TRY(spk_conv_wgrad_reduce(slabs, gw, M, cin_t, C, L.d.k, stem, ws, stem ? 1.0f / SPK_INPUT_SCALE : 1.0f));
-          }
-          if (side_on) {
-            if (!t->conv[i].dy_off) {
-              HIP_TRY(hipEventRecord(t->ev_dy_free[slot], ws));
-              t->dy_busy[slot] = true;
-            }
-          }
-          mark(m, PH_WGRAD_REDUCE);
+          SPK_TRY(dwconv_backward(c, i, dy, slot));
+        } else if (L.mode == CONV_MODE_GROUP) {
+          SPK_TRY(group_backward(c, i, dy, slot));
+        } else {
+          SPK_TRY(conv_dgrad(c, i, dy));
+          SPK_TRY(conv_wgrad(c, i, dy, slot));
         }
         break;
       }
-      case SPK_OP_SE: {
-        // out = a * s(pool(a)):  da = g * s + W1^T[ silu'(u1) * W2^T[ s(1-s) * sum_hw(g * a) ] ] / HW
-        const int C = o.c, Cl = L.d.cout, S = L.d.k, HW = o.h * o.w;
-        float* pooled = (float*)((char*)t->arena + t->conv[i].se_off);
-        float* u1 = pooled + (size_t)n * C;
-        float* h1 = u1 + (size_t)n * S;
-        float* gate = h1 + (size_t)n * S;
-        float* scratch = (float*)((char*)t->arena + t->se_tmp_off);
-        float* dgate = gate + (size_t)n * C;   // becomes du2 in place
-        float* du1 = dgate + (size_t)n * C;
-        float* dpool = scratch + (size_t)n * spk_se_chunks(HW) * C;
-        const bf16_t* g = (const bf16_t*)t->G(L.d.dst);
-        const bf16_t* a = (const bf16_t*)m->T(L.d.src);
-        K_TRY(spk_launch_pool_rows(g, a, scratch, n, HW, C, s), "se dgate");
-        const Param &w1 = m->params[L.p_w], &b1 = m->params[L.p_b], &w2 = m->params[L.p_w2], &b2 = m->params[L.p_b2];
-        K_TRY(spk_launch_se_gate_bwd(scratch, spk_se_chunks(HW), dgate, gate, u1, m->P(L.p_w), m->P(L.p_w2), du1, dpool, dpool + (size_t)n * C, n, C, Cl,
-                                     S, s, L.d.relu == SPK_ACT_RELU ? 1 : 0), "se gates bwd");
-        hipStream_t ws = s;
-        if (side_on && (w1.requires_grad || b1.requires_grad || w2.requires_grad || b2.requires_grad)) {
-          ws = t->side;   // du2 / du1 are this layer's own: nothing on the main stream waits for the kernel
-          HIP_TRY(hipEventRecord(t->ev_se, s));
-          HIP_TRY(hipStreamWaitEvent(ws, t->ev_se, 0));
-        }
-        K_TRY(spk_launch_se_wgrad(dgate, h1, du1, pooled, w1.requires_grad ? t->gbuf + w1.off : nullptr,
-                                  b1.requires_grad ? t->gbuf + b1.off : nullptr,
-                                  w2.requires_grad ? t->gbuf + w2.off : nullptr,
-                                  b2.requires_grad ? t->gbuf + b2.off : nullptr, n, C, Cl, S, ws), "se wgrad");
-        K_TRY(spk_launch_se_bwd_apply(g, gate, dpool, (bf16_t*)t->G(L.d.src), n, HW, C, s), "se bwd apply");
-        mark(m, PH_BN_BWD);
-        has_grad[L.d.src] = 1;
+      case SPK_OP_SE:
+        SPK_TRY(se_backward(c, i));
         break;
-      }
     }
   }
   if (m->grad_cb)
     while (cur_bucket < m->grad_buckets) SPK_TRY(grad_bucket_done(m, cur_bucket++));
-  if (side_on) {   // the step is complete on the caller's stream only when the side-stream weight gradients are
+  if (c.side_on) {   // the step is complete on the caller's stream only when the side-stream weight gradients are
     HIP_TRY(hipEventRecord(t->ev_side_done, t->side));
-    if (tail_layer >= 0) {   // ... all but the last one: whoever needs it joins (spk_train_join, spk_optim_step)
+    if (c.tail_layer >= 0) {   // ... all but the last one: whoever needs it joins (spk_train_join, spk_optim_step)
       HIP_TRY(hipStreamWaitEvent(s, t->ev_side_pre, 0));
       t->tail_pending = true;
-      t->tail_param = m->layers[tail_layer].p_w;
+      t->tail_param = m->layers[c.tail_layer].p_w;
     } else {
       HIP_TRY(hipStreamWaitEvent(s, t->ev_side_done, 0));
     }

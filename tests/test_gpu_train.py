@@ -520,6 +520,38 @@ def test_launch_forms_of_the_step_give_the_same_weights():
     assert len(set(seen.values())) == 1, seen
 
 
+@pytest.mark.parametrize("network", ["resnet50", "efficientnet_b0", "mobilenet_v3_small", "resnext50_32x4d"])
+def test_single_stream_step_gives_the_two_stream_gradients(network):
+    """The per-phase profile runs the step on ONE stream (weight gradients behind the data gradients, in line), every other
+    caller on two.  Same seed, same batch, same step counter - so dropout and stochastic depth draw the same masks - and
+    everything trainable: the second step of a handle that ran `forward_backward` twice and the single-stream step of
+    `profile_train` (behind its two-stream warm-up step) leave the same gradients, bit for bit.  ResNet-50: deferral and
+    the fused reductions; EfficientNet-B0: 3x3 stem, depthwise, squeeze-excitation, stochastic depth, the padded reduce;
+    MobileNetV3-Small: ReLU / Hardsigmoid gates; ResNeXt-50: grouped convs."""
+    from sykepic_hip.net import HipNet
+    classes, n, hw = 10, 6, 64
+    x = torch.from_numpy(synth.synth_images(n, 3, hw, hw, seed=10)).cuda()
+    y = torch.from_numpy(synth.synth_labels(n, classes, seed=11)).cuda()
+    grads = []
+    for single_stream in (False, True):
+        net = HipNet(network, classes, weights=None)
+        net.reset_parameters(seed=3)
+        net.set_seed(3)
+        for p in net.parameters():
+            p.requires_grad = True
+        net.train()
+        if single_stream:
+            net.profile_train(x, y, iters=1)
+        else:
+            net.forward_backward(x, y)
+            net.forward_backward(x, y)
+        grads.append({p.key: p.grad for p in net.parameters()})
+    assert len(grads[0]) > 0 and grads[0].keys() == grads[1].keys()
+    for k in grads[0]:
+        assert torch.isfinite(grads[0][k]).all(), k
+        assert torch.equal(grads[0][k], grads[1][k]), k
+
+
 def test_fresh_network_is_randomly_initialised_and_learns():
     """A HipNet built with weights=None starts from torch/torchvision's initial distributions (the
     reference's TorchVisionNet(weights=None)), reproducibly under torch.manual_seed, and a few Adam steps on one
