@@ -261,6 +261,37 @@ int spk_model_set_grad_ready_callback(spk_model* m, spk_grad_ready_fn cb, void* 
 /* Gradient of one tensor, copied to host in state_dict layout (tests). */
 int spk_model_read_grad(spk_model* m, const char* key, void* host, int64_t numel);
 
+/* --- Checkpointing a training run (resume; the reference saves the weights alone, sykepic/train/train.py:300) ---
+ * Everything the next spk_train_forward_backward + spk_optim_step reads that is neither a parameter nor a buffer of
+ * the state_dict, a hyper-parameter of spk_optim_desc, the group / requires_grad flags (set by key above) nor the
+ * input batch:
+ *   - the two moment buffers of the optimizer kernels, per tensor (slot 0 / 1; which torch.optim state entry each holds
+ *     depends on the optimizer kind: SGD momentum_buffer / -; Adam, AdamW, NAdam, RAdam exp_avg / exp_avg_sq; Adamax
+ *     exp_avg / exp_inf; RMSprop momentum_buffer / square_avg; Adagrad - / sum; Adadelta square_avg / acc_delta;
+ *     Rprop prev / step_size; ASGD none)
+ *   - per tensor: the step count (bias corrections, "first step" initialisations, Adagrad / ASGD / RAdam schedules)
+ *     and NAdam's running mu product (kept in double)
+ *   - per model: the number of training steps so far and the seed, which together with the layer index select the
+ *     Dropout and stochastic-depth masks of a step
+ * Nothing else survives a step: gradients, batch statistics, masks and the packed bf16 weight images are rebuilt by
+ * every step (the images whenever a parameter was loaded or stepped), the side-stream bookkeeping is joined by every
+ * reader, and the `sgd_started` flag of the training state is never read (a tensor's first step is step == 1).
+ *
+ * Moments of one tensor, float32 in state_dict layout (OIHW for conv weights) like spk_model_read_param: the state
+ * `optimizer.step()` (train.py:243) keeps for `getattr(optim, name)(groups)` (train.py:131-138).  Synchronous.  Before
+ * any training step a read returns zeros; a load creates the training state.  Unknown key: SPK_ERR_KEY; a buffer
+ * (no gradient), a size mismatch or a slot other than 0 / 1: SPK_ERR_ARG. */
+int spk_model_optim_state_read(spk_model* m, const char* key, int slot, float* host, int64_t numel);
+int spk_model_optim_state_load(spk_model* m, const char* key, int slot, const float* host, int64_t numel);
+/* Per-tensor counters of optimizer.step() (train.py:243): torch's state["step"] as an exact integer and NAdam's
+ * state["mu_product"] (1.0 for every other optimizer and before the first step). */
+int spk_model_param_counters_get(spk_model* m, const char* key, int64_t* step, double* mu_product);
+int spk_model_param_counters_set(spk_model* m, const char* key, int64_t step, double mu_product);
+/* Per-model counters: training steps run so far (spk_train_forward_backward calls, train.py:239-242) and the mask
+ * seed of spk_model_set_seed.  The setter creates the training state. */
+int spk_model_train_counters_get(spk_model* m, uint64_t* steps, uint64_t* seed);
+int spk_model_train_counters_set(spk_model* m, uint64_t steps, uint64_t seed);
+
 /* Test hook: copy activation `tensor_id` (spk_layer_desc.dst numbering) of the
  * most recent forward to the host as float32 NCHW ([n,c,h,w]; [n,c] for the
  * head).  The stem input (id 0) is not readable.  Synchronous. */

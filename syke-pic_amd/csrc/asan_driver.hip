@@ -165,6 +165,18 @@ int main(int argc, char** argv) {
   EXPECT(strlen(spk_last_error()) > 0);
   EXPECT(spk_model_num_params(nullptr) == 0);
   spk_model_destroy(nullptr);
+  {   // the checkpoint entry points look at their arguments before anything else
+    float f[4] = {0};
+    int64_t step = 0;
+    double mu = 0;
+    uint64_t steps = 0, seed = 0;
+    EXPECT(spk_model_optim_state_read(nullptr, "head.0.weight", 0, f, 4) == SPK_ERR_ARG);
+    EXPECT(spk_model_optim_state_load(nullptr, "head.0.weight", 1, f, 4) == SPK_ERR_ARG);
+    EXPECT(spk_model_param_counters_get(nullptr, "head.0.weight", &step, &mu) == SPK_ERR_ARG);
+    EXPECT(spk_model_param_counters_set(nullptr, "head.0.weight", 1, 1.0) == SPK_ERR_ARG);
+    EXPECT(spk_model_train_counters_get(nullptr, &steps, &seed) == SPK_ERR_ARG);
+    EXPECT(spk_model_train_counters_set(nullptr, 1, 2) == SPK_ERR_ARG);
+  }
 
   // ---- a small bottleneck graph: stem, pool, 1x1 / 3x3 / 1x1 + shortcut, pool, head ----
   std::vector<spk_layer_desc> g;
@@ -203,6 +215,10 @@ int main(int argc, char** argv) {
     EXPECT(spk_model_load_param(m, "base.0.weight", w.data(), (int64_t)w.size()) == SPK_OK);
     EXPECT(spk_model_set_requires_grad(m, "no.such.key", 1) == SPK_ERR_KEY);
     EXPECT(spk_model_set_param_group(m, "base.0.weight", 2) == SPK_OK);
+    std::vector<float> mom(w.size(), 1.f);
+    EXPECT(spk_model_optim_state_read(m, "no.such.key", 0, mom.data(), (int64_t)mom.size()) == SPK_ERR_KEY);
+    EXPECT(spk_model_optim_state_read(m, "base.0.weight", 0, mom.data(), 7) == SPK_ERR_ARG);
+    EXPECT(spk_model_optim_state_read(m, "base.0.weight", 0, mom.data(), (int64_t)mom.size()) == SPK_OK && mom[0] == 0.f);
     spk_model_destroy(m);
   }
 

@@ -209,6 +209,7 @@ int spk_run_layer_eval(spk_model* m, Layer& L, int nb);
 int spk_forward_eval_logits(spk_model* m, const void* x, int n, int h, int w, int layout, int dtype,
                             float* logits_dev);
 int spk_read_flat(spk_model* m, const float* flat, const Param& p, float* host);
+int spk_load_flat(spk_model* m, float* flat, const Param& p, const float* host);   // the inverse (state_dict -> device layout)
 void spk_train_free(spk_model* m);
 // backward of one convolution (train.hip): shared by the training step and the single-operator test hooks
 // fuse: (stride 1 only) the BatchNorm-backward reduction of the layer that produced the tensor dx is the gradient of,

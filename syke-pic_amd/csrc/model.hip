@@ -481,12 +481,20 @@ extern "C" int spk_model_load_param(spk_model* m, const char* key, const void* h
     m->layers[p->layer].nbt = *(const int64_t*)host;
     return SPK_OK;
   }
-  const float* src = (const float*)host;
+  SPK_TRY(spk_load_flat(m, m->pbuf, *p, (const float*)host));
+  m->dirty = true;
+  spk_train_mark_dirty(m);
+  return SPK_OK;
+}
+
+// inverse of spk_read_flat: one tensor in state_dict layout into its slice of a flat device buffer
+int spk_load_flat(spk_model* m, float* flat, const Param& p, const float* host) {
+  const float* src = host;
   std::vector<float> tmp;
-  if (p->kind == PK_CONV_W) {
+  if (p.kind == PK_CONV_W) {
     // OIHW (state_dict) -> O,H,W,I (device master layout, K = tap-major)
-    const int64_t O = p->shape[0], I = p->shape[1], H = p->shape[2], W = p->shape[3];
-    tmp.resize((size_t)numel);
+    const int64_t O = p.shape[0], I = p.shape[1], H = p.shape[2], W = p.shape[3];
+    tmp.resize((size_t)p.numel);
     for (int64_t o = 0; o < O; ++o)
       for (int64_t i = 0; i < I; ++i)
         for (int64_t h = 0; h < H; ++h)
@@ -494,9 +502,7 @@ extern "C" int spk_model_load_param(spk_model* m, const char* key, const void* h
             tmp[(size_t)(((o * H + h) * W + w) * I + i)] = src[(size_t)(((o * I + i) * H + h) * W + w)];
     src = tmp.data();
   }
-  HIP_TRY(hipMemcpy(m->pbuf + p->off, src, (size_t)numel * 4, hipMemcpyHostToDevice));
-  m->dirty = true;
-  spk_train_mark_dirty(m);
+  HIP_TRY(hipMemcpy(flat + p.off, src, (size_t)p.numel * 4, hipMemcpyHostToDevice));
   return SPK_OK;
 }
 

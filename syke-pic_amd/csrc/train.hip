@@ -1283,6 +1283,80 @@ extern "C" int spk_model_read_grad(spk_model* m, const char* key, void* host, in
   return spk_read_flat(m, m->train->gbuf, p, (float*)host);
 }
 
+// ---- checkpointing of what a training step leaves behind beside the parameters (include/sykepic_hip.h) ----
+static int optim_state_param(spk_model* m, const char* key, int slot, const void* host, int64_t numel, const char* fn,
+                             const Param** out) {
+  if (!m || !key || !host || slot < 0 || slot > 1) return tfail(SPK_ERR_ARG, std::string(fn) + ": bad arguments");
+  auto it = m->index.find(key);
+  if (it == m->index.end()) return tfail(SPK_ERR_KEY, std::string(fn) + ": unknown state_dict key: " + key);
+  const Param& p = m->params[it->second];
+  if (!p.trainable || p.numel != numel)
+    return tfail(SPK_ERR_ARG, std::string(fn) + ": no gradient / size mismatch for " + key);
+  *out = &p;
+  return SPK_OK;
+}
+
+extern "C" int spk_model_optim_state_read(spk_model* m, const char* key, int slot, float* host, int64_t numel) {
+  const Param* p = nullptr;
+  SPK_TRY(optim_state_param(m, key, slot, host, numel, "model_optim_state_read", &p));
+  if (!m->train) {   // no training step yet: the moments a first step would find
+    std::fill(host, host + numel, 0.f);
+    return SPK_OK;
+  }
+  HIP_TRY(hipSetDevice(m->device));
+  SPK_TRY(spk_train_join(m));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  return spk_read_flat(m, slot ? m->train->m2 : m->train->m1, *p, host);
+}
+
+extern "C" int spk_model_optim_state_load(spk_model* m, const char* key, int slot, const float* host, int64_t numel) {
+  const Param* p = nullptr;
+  SPK_TRY(optim_state_param(m, key, slot, host, numel, "model_optim_state_load", &p));
+  HIP_TRY(hipSetDevice(m->device));
+  SPK_TRY(ensure_state(m));
+  SPK_TRY(spk_train_join(m));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  return spk_load_flat(m, slot ? m->train->m2 : m->train->m1, *p, host);
+}
+
+extern "C" int spk_model_param_counters_get(spk_model* m, const char* key, int64_t* step, double* mu_product) {
+  if (!m || !key || !step || !mu_product) return tfail(SPK_ERR_ARG, "model_param_counters_get: bad arguments");
+  auto it = m->index.find(key);
+  if (it == m->index.end()) return tfail(SPK_ERR_KEY, std::string("model_param_counters_get: unknown state_dict key: ") + key);
+  const Param& p = m->params[it->second];
+  if (!p.trainable) return tfail(SPK_ERR_ARG, std::string("model_param_counters_get: ") + key + " is a buffer, not a parameter");
+  *step = (int64_t)p.step;
+  *mu_product = p.mu_product;
+  return SPK_OK;
+}
+
+extern "C" int spk_model_param_counters_set(spk_model* m, const char* key, int64_t step, double mu_product) {
+  if (!m || !key || step < 0) return tfail(SPK_ERR_ARG, "model_param_counters_set: bad arguments");
+  auto it = m->index.find(key);
+  if (it == m->index.end()) return tfail(SPK_ERR_KEY, std::string("model_param_counters_set: unknown state_dict key: ") + key);
+  Param& p = m->params[it->second];
+  if (!p.trainable) return tfail(SPK_ERR_ARG, std::string("model_param_counters_set: ") + key + " is a buffer, not a parameter");
+  p.step = (long)step;
+  p.mu_product = mu_product;
+  return SPK_OK;
+}
+
+extern "C" int spk_model_train_counters_get(spk_model* m, uint64_t* steps, uint64_t* seed) {
+  if (!m || !steps || !seed) return tfail(SPK_ERR_ARG, "model_train_counters_get: bad arguments");
+  *steps = m->train ? (uint64_t)m->train->steps : 0;
+  *seed = m->seed;
+  return SPK_OK;
+}
+
+extern "C" int spk_model_train_counters_set(spk_model* m, uint64_t steps, uint64_t seed) {
+  if (!m) return tfail(SPK_ERR_ARG, "model_train_counters_set: bad arguments");
+  HIP_TRY(hipSetDevice(m->device));
+  SPK_TRY(ensure_state(m));
+  m->train->steps = (unsigned long long)steps;
+  m->seed = seed;
+  return SPK_OK;
+}
+
 // Test hook: gradient w.r.t. activation `t` of the last training step, as
 // float32 NCHW ([n,c,h,w]; [n,c] in the head).
 extern "C" int spk_model_read_activation_grad(spk_model* m, int t, int n, float* host, int64_t numel) {

@@ -20,6 +20,11 @@ def build_parser():
                     help="Save a ROWS x COLUMNS grid of transformed images to PNG.")
     tp.add_argument("--dist", metavar="FILE", help="Save a class distribution plot to FILE")
     tp.add_argument("--save-images", metavar="DIR", help="Extract train, test, val images to this path")
+    # not in the reference, which cannot continue a run that stopped
+    tp.add_argument("--resume", metavar="MODEL_DIR",
+                    help="Continue the run that wrote MODEL_DIR/train_state.pth behind its last FINISHED epoch (a run "
+                         "killed inside an epoch repeats that epoch); raise max_epochs in the config to extend a "
+                         "finished run")
     tp.set_defaults(func=_train)
     for name in ("prob", "predict"):
         pp = sub.add_parser(name, description="Calculate class probabilities")

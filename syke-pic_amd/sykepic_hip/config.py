@@ -62,6 +62,8 @@ KEYS = {
     "train": {
         "gpu": (_flag, REQUIRED), "max_epochs": (int, REQUIRED), "early_stop_patience": (int, REQUIRED),
         "learning_rate": (float, REQUIRED), "optimizer": (str, REQUIRED),
+        # not in the reference: train_state.pth, written at the end of every epoch for `sykepic train --resume`
+        "save_train_state": (_flag, "yes"),
     },
     "lr_warmup": {
         "use": (_flag, REQUIRED), "factor_1": (float, REQUIRED), "factor_2": (float, REQUIRED), "step_1": (int, REQUIRED),

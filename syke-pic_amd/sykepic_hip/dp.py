@@ -245,14 +245,20 @@ def all_ok(ok, dist=None):
     return bool(int(t.item()))
 
 
+def gather_object(obj, dist=None, dst=0):
+    """Counterpart of `broadcast_object`: every rank's Python value on rank `dst`, in rank order ([obj] without a
+    process group; None on the other ranks).  A collective: every rank calls it."""
+    if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
+        return [obj]
+    out = [None] * dist.get_world_size() if dist.get_rank() == dst else None
+    dist.gather_object(obj, out, dst=dst)
+    return out
+
+
 def gather_parts(part, dist=None, dst=0):
     """Inference, array form: every rank's shard object (prob.ProbRows) on rank `dst` ([part] without a process
     group; None on the other ranks).  Host-side object gather like `gather_rows`."""
-    if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
-        return [part]
-    out = [None] * dist.get_world_size() if dist.get_rank() == dst else None
-    dist.gather_object(part, out, dst=dst)
-    return out
+    return gather_object(part, dist, dst)
 
 
 def gather_rows(rows, dist=None, dst=None):

@@ -96,6 +96,12 @@ SYMBOLS = {
     "spk_model_grad_buffer": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),
     "spk_model_set_grad_ready_callback": (C.c_int, [_P, _P, _P, _P, C.c_int]),
     "spk_model_read_grad": (C.c_int, [_P, C.c_char_p, _P, C.c_int64]),
+    "spk_model_optim_state_read": (C.c_int, [_P, C.c_char_p, C.c_int, _P, C.c_int64]),
+    "spk_model_optim_state_load": (C.c_int, [_P, C.c_char_p, C.c_int, _P, C.c_int64]),
+    "spk_model_param_counters_get": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "spk_model_param_counters_set": (C.c_int, [_P, C.c_char_p, C.c_int64, C.c_double]),
+    "spk_model_train_counters_get": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "spk_model_train_counters_set": (C.c_int, [_P, C.c_uint64, C.c_uint64]),
     "spk_model_read_activation": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64]),
     "spk_model_read_activation_grad": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64]),
     "spk_op_conv_bn_train_forward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P] + [C.c_int] * 9 + [_P]),

@@ -577,6 +577,45 @@ class HipNet:
                                                 int(buf.size)))
         return torch.from_numpy(buf)
 
+    # ---- what a training step leaves behind beside the state_dict (checkpoint / resume) ----
+    def _read_optim_state(self, key, slot, shape):
+        buf = np.empty(shape, dtype=np.float32)
+        lib.check(self._lib.spk_model_optim_state_read(self._h, key.encode(), int(slot), C.c_void_p(buf.ctypes.data),
+                                                       int(buf.size)))
+        return torch.from_numpy(buf)
+
+    def _load_optim_state(self, key, slot, value):
+        shape = self._params[key].shape
+        t = value.detach().cpu() if isinstance(value, torch.Tensor) else torch.as_tensor(value)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"optimizer state of {key}: shape {tuple(t.shape)}, the parameter has {tuple(shape)}")
+        a = np.ascontiguousarray(t.numpy().astype(np.float32))
+        with torch.cuda.device(self.device):
+            lib.check(self._lib.spk_model_optim_state_load(self._h, key.encode(), int(slot), C.c_void_p(a.ctypes.data),
+                                                           int(a.size)))
+
+    def param_counters(self, key):
+        """(step count, NAdam mu product) of one parameter: exact int and double."""
+        step, mu = C.c_int64(), C.c_double()
+        lib.check(self._lib.spk_model_param_counters_get(self._h, key.encode(), C.byref(step), C.byref(mu)))
+        return int(step.value), float(mu.value)
+
+    def set_param_counters(self, key, step, mu_product=1.0):
+        lib.check(self._lib.spk_model_param_counters_set(self._h, key.encode(), int(step), float(mu_product)))
+
+    def train_counters(self):
+        """{"steps": training steps so far, "seed": mask seed}: with the layer index they select a step's Dropout and
+        stochastic-depth masks."""
+        steps, seed = C.c_uint64(), C.c_uint64()
+        lib.check(self._lib.spk_model_train_counters_get(self._h, C.byref(steps), C.byref(seed)))
+        return {"steps": int(steps.value), "seed": int(seed.value)}
+
+    def set_train_counters(self, counters):
+        with torch.cuda.device(self.device):
+            lib.check(self._lib.spk_model_train_counters_set(self._h, int(counters["steps"]),
+                                                             int(counters["seed"]) & 0xFFFFFFFFFFFFFFFF))
+        return self
+
     def state_dict(self):
         """CPU tensors, NCHW fp32 (+ int64 counters): the on-disk contract of
         best_state.pth (reference train.py:300)."""

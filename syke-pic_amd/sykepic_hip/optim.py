@@ -22,6 +22,9 @@ _DEFAULTS = {
     "ASGD": dict(lambd=1e-4, alpha=0.75, t0=1e6, weight_decay=0.0),
     "Rprop": dict(etas=(0.5, 1.2), step_sizes=(1e-6, 50.0)),
 }
+# hyper-parameters torch's `step()` reads from a loaded group but does not default (`torch.optim.SGD.__setstate__`
+# fills in the others): this path fixes them at torch's defaults, `state_dict()` says so
+_TORCH_FIXED = {"SGD": dict(dampening=0.0, nesterov=False)}
 _KINDS = {"SGD": lib.OPT_SGD, "Adam": lib.OPT_ADAM, "AdamW": lib.OPT_ADAMW, "RMSprop": lib.OPT_RMSPROP,
           "Adagrad": lib.OPT_ADAGRAD, "Adamax": lib.OPT_ADAMAX, "NAdam": lib.OPT_NADAM, "RAdam": lib.OPT_RADAM,
           "Adadelta": lib.OPT_ADADELTA, "ASGD": lib.OPT_ASGD, "Rprop": lib.OPT_RPROP}
@@ -84,6 +87,95 @@ class HipOptimizer:
             d.beta1, d.beta2 = (float(v) for v in self.defaults["etas"])
             d.eps, d.alpha = (float(v) for v in self.defaults["step_sizes"])
         self.net.optim_step(d)
+
+    # ---- torch.optim.Optimizer.state_dict() / load_state_dict() of the class of the same name ----
+    def _slots(self):
+        """[(torch's state name, which of the library's two moment buffers holds it)] for this optimizer
+        (csrc/train_kernels.hip: sgd_multi_kernel, adam_multi_kernel and the table above opt_generic_kernel)."""
+        if self.name == "SGD":
+            return [("momentum_buffer", 0)] if float(self.defaults.get("momentum", 0.0)) != 0 else []
+        if self.name == "RMSprop":
+            return [("square_avg", 1)] + ([("momentum_buffer", 0)] if float(self.defaults.get("momentum", 0.0)) > 0 else [])
+        return {"Adam": [("exp_avg", 0), ("exp_avg_sq", 1)], "AdamW": [("exp_avg", 0), ("exp_avg_sq", 1)],
+                "RAdam": [("exp_avg", 0), ("exp_avg_sq", 1)], "NAdam": [("exp_avg", 0), ("exp_avg_sq", 1)],
+                "Adamax": [("exp_avg", 0), ("exp_inf", 1)], "Adagrad": [("sum", 1)],
+                "Adadelta": [("square_avg", 0), ("acc_delta", 1)], "Rprop": [("prev", 0), ("step_size", 1)],
+                "ASGD": []}[self.name]
+
+    def state_dict(self):
+        """The structure ``torch.optim.<name>.state_dict()`` has: ``param_groups`` with running parameter indices and
+        the hyper-parameters, ``state`` per index under torch's names (``step`` a float32 scalar tensor, as torch
+        stores it).  A parameter that was never stepped has no entry.  torch's float32 ``step`` / ``mu_product`` are
+        lossy copies of the library's int64 / double: the exact values travel under ``spk_exact``, a top-level key
+        ``torch.optim.Optimizer.load_state_dict`` ignores."""
+        import torch
+        groups, state, exact, idx = [], {}, {}, 0
+        slots = self._slots()
+        for g in self.param_groups:
+            ids = []
+            for p in g["params"]:
+                step, mu = self.net.param_counters(p.key)
+                if step > 0:
+                    exact[idx] = {"step": step, "mu_product": mu}
+                    st = {}
+                    if self.name != "SGD":
+                        st["step"] = torch.tensor(float(step), dtype=torch.float32)
+                    if self.name == "NAdam":
+                        st["mu_product"] = torch.tensor(mu, dtype=torch.float32)
+                    if self.name == "ASGD":   # eta / mu as torch leaves them after `step` steps; ax = the parameter (t0 large)
+                        lr, lam = float(g["lr"]), float(self.defaults["lambd"])
+                        st["eta"] = torch.as_tensor(lr / ((1 + lam * lr * step) ** float(self.defaults["alpha"])))
+                        st["mu"] = torch.as_tensor(1 / max(1, step - float(self.defaults["t0"])))
+                        st["ax"] = p.data
+                    for tname, slot in slots:
+                        st[tname] = self.net._read_optim_state(p.key, slot, p.shape)
+                    if st:                    # plain SGD keeps nothing per parameter
+                        state[idx] = st
+                ids.append(idx)
+                idx += 1
+            grp = dict(self.defaults)
+            grp.update(_TORCH_FIXED.get(self.name, {}))
+            grp["lr"] = g["lr"]
+            grp["params"] = ids
+            groups.append(grp)
+        return {"state": state, "param_groups": groups, "spk_exact": exact}
+
+    def load_state_dict(self, state_dict):
+        """Accepts `state_dict()` of this class or of the torch optimizer of the same name over the same parameters in
+        the same order: positions map saved indices to this optimizer's parameters, as in torch.  Restores the moments,
+        the counters (exact ones where the dict carries them), ``lr`` per group and the hyper-parameters."""
+        import torch
+        saved = state_dict["param_groups"]
+        if len(saved) != len(self.param_groups):
+            raise ValueError("loaded state dict has a different number of parameter groups")
+        if any(len(s["params"]) != len(g["params"]) for s, g in zip(saved, self.param_groups)):
+            raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group")
+        state, exact = state_dict.get("state", {}), state_dict.get("spk_exact", {})
+        for s, g in zip(saved, self.param_groups):
+            g["lr"] = s["lr"]
+            for k in self.defaults:      # one set of hyper-parameters serves every group here
+                if k in s and s["params"]:
+                    self.defaults[k] = s[k]
+        slots = self._slots()            # (SGD / RMSprop: depends on the momentum just loaded)
+        used = self.net.train_counters()["steps"] > 0   # a fresh model's moments are zero already
+        for s, g in zip(saved, self.param_groups):
+            for idx, p in zip(s["params"], g["params"]):
+                st, ex = state.get(idx, {}), exact.get(idx)
+                if ex is not None:
+                    step, mu = int(ex["step"]), float(ex["mu_product"])
+                else:
+                    step = int(round(float(st["step"]))) if "step" in st else (1 if st.get("momentum_buffer") is not None else 0)
+                    mu = float(st["mu_product"]) if "mu_product" in st else 1.0
+                self.net.set_param_counters(p.key, step, mu)
+                for tname, slot in slots:
+                    if st.get(tname) is not None:
+                        self.net._load_optim_state(p.key, slot, st[tname])
+                    elif step == 0:
+                        if used:
+                            self.net._load_optim_state(p.key, slot, torch.zeros(p.shape))
+                    else:
+                        raise ValueError(f"loaded state of parameter {idx} ({p.key}) has no {tname!r}")
+        self.sync_groups()
 
     def __repr__(self):
         lines = [f"{self.name} ("]

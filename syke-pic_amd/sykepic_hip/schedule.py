@@ -106,6 +106,15 @@ class ReduceLROnPlateau:
         self.num_bad_epochs = 0
         self.eps = 1e-8
 
+    def state_dict(self):
+        """What `step()` carries from one call to the next (plain floats / ints).  mode, factor, patience, threshold
+        and eps are constructor arguments: a resumed run takes them from its config file like every other setting."""
+        return {"best": float(self.best), "num_bad_epochs": int(self.num_bad_epochs)}
+
+    def load_state_dict(self, state):
+        self.best = float(state["best"])
+        self.num_bad_epochs = int(state["num_bad_epochs"])
+
     def _better(self, a):
         if self.mode == "min":
             return a < self.best * (1.0 - self.threshold)

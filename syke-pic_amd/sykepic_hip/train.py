@@ -101,13 +101,23 @@ def main(args):
     if external_test:
         extra_loader = data.extra_eval_dataloader(external_test, model_data, exclude=["Unclassified"])
 
-    # model directory <path>/<network>[_<id>]; id "auto" = next free number, picked by rank 0 for the whole job
-    # (another rank could already see the directory rank 0 has just made)
-    model_id = mo.id
-    if model_id == "auto":
-        model_id = dp.broadcast_object(data.auto_id(mo.network, mo.path) if chief else None, dist)
-    model_dir = mo.path / (mo.network + (f"_{model_id}" if model_id else ""))
-    if chief:
+    # `--resume MODEL_DIR`: that directory as it is (no `auto` id, no `exist_ok` complaint, its config.ini / class_names.txt /
+    # class_distribution.csv stay), everything else rebuilt from CONFIG as for a fresh run
+    resume = getattr(args, "resume", None)
+    state = None
+    if resume:
+        model_dir = Path(resume)
+        state = load_train_state(model_dir)
+        check_train_state(state, network=mo.network, classes=[str(c) for c in model_data.le.classes_],
+                          img_shape=img_shape, optimizer=tr.optimizer, world=world)
+    else:
+        # model directory <path>/<network>[_<id>]; id "auto" = next free number, picked by rank 0 for the whole job
+        # (another rank could already see the directory rank 0 has just made)
+        model_id = mo.id
+        if model_id == "auto":
+            model_id = dp.broadcast_object(data.auto_id(mo.network, mo.path) if chief else None, dist)
+        model_dir = mo.path / (mo.network + (f"_{model_id}" if model_id else ""))
+    if chief and not resume:
         model_dir.mkdir(parents=True, exist_ok=mo.exist_ok)
         from . import prob as _prob
         _prob.drop_act_means(model_dir)   # exist_ok = yes: means of an earlier run do not belong to the weights about to be written
@@ -119,11 +129,14 @@ def main(args):
     if not tr.gpu:
         raise RuntimeError("this build trains on the MI355X only; for `gpu = no` use the reference itself")
     device = torch.device("cuda", local)
-    net = get_network(config, num_classes, device=device)
+    # a resumed run loads every tensor from train_state.pth: no random / pretrained initialisation (and no draw from
+    # torch's generator for one)
+    net = get_network(config, num_classes, device=device, pretrained_ok=state is None)
     # Dropout masks are a function of (seed, step, layer): give every rank its own stream, otherwise the j-th sample of
     # every shard draws the same mask at every step.  A run stays deterministic for a given random_seed and world size.
     net.set_seed(seed * world + rank)
-    dp.broadcast_state(net, dist)   # every replica starts from rank 0's (random / pretrained) tensors
+    if state is None:
+        dp.broadcast_state(net, dist)   # every replica starts from rank 0's (random / pretrained) tensors
     schedule.freeze(net.base)
     initial = [p for p in net.parameters() if p.requires_grad]
     optimizer = HipOptimizer(net, tr.optimizer, [{"params": initial, "lr": tr.learning_rate},
@@ -140,8 +153,17 @@ def main(args):
         # quirk Q3: the reference passes `verbose` positionally into `threshold`
         lr_scheduler = schedule.ReduceLROnPlateau(optimizer, "min", red.factor, red.patience, red.verbose)
 
-    best_state = train_net(net, model_data.train_loader, model_data.val_loader, optimizer, None, tr.max_epochs,
-                           tr.early_stop_patience, model_dir, device, lr_scheduler, lr_warmup, dist=dist)
+    run_info = {"network": mo.network, "classes": [str(c) for c in model_data.le.classes_],
+                "img_shape": [int(v) for v in img_shape], "optimizer": tr.optimizer, "world": world}
+    if state is not None and (state["early_stopped"] or state["epoch"] >= tr.max_epochs):
+        # nothing left to train (raise `max_epochs` to extend a run that reached it): the reports of the best model
+        if chief:
+            print(f"[INFO] {model_dir}: training ended after epoch {state['epoch']}, nothing to resume")
+        best_state = Path(model_dir) / "best_state.pth"
+    else:
+        best_state = train_net(net, model_data.train_loader, model_data.val_loader, optimizer, None, tr.max_epochs,
+                               tr.early_stop_patience, model_dir, device, lr_scheduler, lr_warmup, dist=dist,
+                               run_info=run_info if tr.save_train_state else None, resume=state)
     if dist is not None:
         dist.barrier()
     net.load_state_dict(torch.load(best_state, map_location="cpu"))
@@ -167,10 +189,106 @@ def main(args):
         (model_dir / (f"test_report_{name}.txt" if name else "test_report.txt")).write_text(report)
 
 
+TRAIN_STATE_FILE = "train_state.pth"
+TRAIN_STATE_FORMAT = 1
+
+
+def save_atomically(obj, path):
+    """`torch.save` into a temporary file of the same directory, then `os.replace`: a kill or an error in the middle of
+    the write leaves the previous file as it was."""
+    path = Path(path)
+    tmp = path.with_name(f"{path.name}.{os.getpid()}.tmp")
+    try:
+        torch.save(obj, tmp)
+        os.replace(tmp, path)
+    finally:
+        if tmp.exists():
+            tmp.unlink()
+
+
+def load_train_state(model_dir):
+    """`train_state.pth` of a model directory: tensors and plain containers only (`weights_only=True`)."""
+    path = Path(model_dir) / TRAIN_STATE_FILE
+    if not path.is_file():
+        raise FileNotFoundError(f"{path} not found: nothing to resume (the file is written at the end of every epoch "
+                                "unless `[train] save_train_state = no`)")
+    return torch.load(path, map_location="cpu", weights_only=True)
+
+
+def check_train_state(state, network, classes, img_shape, optimizer, world):
+    """A resumed run must be the run that wrote the file: one line naming the first thing that differs."""
+    if state.get("format") != TRAIN_STATE_FORMAT:
+        raise ValueError(f"cannot resume: train_state.pth has format number {state.get('format')}, this version reads "
+                         f"{TRAIN_STATE_FORMAT}")
+    for what, key, now in (("network", "network", network), ("class list", "classes", [str(c) for c in classes]),
+                           ("image shape", "img_shape", [int(v) for v in img_shape]),
+                           ("optimizer", "optimizer", optimizer), ("world size", "world", int(world))):
+        was = state[key]
+        if was != now:
+            if what == "class list":
+                diff = sorted(set(was) ^ set(now))
+                was, now = f"{len(was)} classes", f"{len(now)} classes (differing: {', '.join(diff[:5]) or 'order'})"
+            raise ValueError(f"cannot resume: {what} differs, train_state.pth has {was}, the config gives {now}")
+
+
+def _rank_state(net):
+    """What differs from rank to rank: the positions of the generators the shuffle (torch) and the augmentation draws
+    (Python's `random`) come from, and the model's mask seed and step counter.  numpy's global generator is not
+    saved: nothing on the training path draws from it."""
+    import random
+    return {"torch_rng": torch.get_rng_state(), "python_rng": random.getstate(), "model": net.train_counters()}
+
+
+def _sampler_of(loader):
+    s = getattr(loader, "sampler", None)
+    return s if hasattr(s, "set_epoch") and hasattr(s, "epoch") else None
+
+
+def collect_train_state(run_info, epoch, ended, early_stopped, net, optimizer, lr_scheduler, book, ranks, train_loader):
+    """Everything `train_net` needs to go on with epoch `epoch + 1` as if it had never stopped."""
+    sampler = _sampler_of(train_loader)
+    return {
+        "format": TRAIN_STATE_FORMAT, **run_info,
+        "epoch": int(epoch), "ended": bool(ended), "early_stopped": bool(early_stopped),
+        "net": dict(net.state_dict()),
+        "optimizer_state": optimizer.state_dict(),     # ("optimizer" is its name, from run_info)
+        "groups": [[p.key for p in g["params"]] for g in optimizer.param_groups],
+        "requires_grad": {p.key: bool(p.requires_grad) for p in net.parameters()},
+        "lr_scheduler": lr_scheduler.state_dict() if lr_scheduler is not None else None,
+        "sampler_epoch": int(sampler.epoch) if sampler is not None else None,
+        "book": book, "ranks": ranks,
+    }
+
+
+def restore_train_state(state, net, optimizer, lr_scheduler, rank, train_loader):
+    """Inverse of `collect_train_state`; returns the book-keeping of the epoch loop."""
+    import random
+    net.load_state_dict(state["net"])
+    params = dict(net.named_parameters())
+    for key, flag in state["requires_grad"].items():
+        params[key].requires_grad = flag
+    for g, keys in zip(optimizer.param_groups, state["groups"]):   # LRWarmup's edits, by key
+        g["params"] = [params[k] for k in keys]
+    optimizer.sync_groups()
+    optimizer.load_state_dict(state["optimizer_state"])
+    if lr_scheduler is not None and state["lr_scheduler"] is not None:
+        lr_scheduler.load_state_dict(state["lr_scheduler"])
+    sampler = _sampler_of(train_loader)
+    if sampler is not None and state["sampler_epoch"] is not None:
+        sampler.set_epoch(state["sampler_epoch"])
+    mine = state["ranks"][rank]
+    net.set_train_counters(mine["model"])
+    torch.set_rng_state(mine["torch_rng"])
+    random.setstate(mine["python_rng"])
+    return state["book"]
+
+
 def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epochs, early_stop_patience,
-              model_dir, device, lr_scheduler=None, lr_warmup=None, dist=None):
+              model_dir, device, lr_scheduler=None, lr_warmup=None, dist=None, run_info=None, resume=None):
     """loss_fn is accepted for signature compatibility; CrossEntropyLoss is
-    fused into the training step (the only loss the reference constructs)."""
+    fused into the training step (the only loss the reference constructs).
+    run_info (network, classes, img_shape, optimizer, world): write `train_state.pth` at the end of every epoch;
+    resume: the loaded file of an earlier run to continue behind its last finished epoch."""
     net = net.to(device)
     chief = dist is None or dist.get_rank() == 0
     parallel = dist is not None and dist.is_initialized() and dist.get_world_size() > 1
@@ -178,13 +296,22 @@ def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epo
     max_val_acc, min_val_loss, no_improvement = 0, 0, 0
     train_accs, train_losses, val_accs, val_losses = [], [], [], []
     best_state = Path(model_dir) / "best_state.pth"
+    first_epoch = 1
+    if resume is not None:
+        book = restore_train_state(resume, net, optimizer, lr_scheduler, dp.rank_world(dist)[0], train_dataloader)
+        max_val_acc, min_val_loss, no_improvement = book["max_val_acc"], book["min_val_loss"], book["no_improvement"]
+        train_accs, train_losses = list(book["train_accs"]), list(book["train_losses"])
+        val_accs, val_losses = list(book["val_accs"]), list(book["val_losses"])
+        first_epoch = resume["epoch"] + 1
+        if chief:
+            print(f"[INFO] Resuming after epoch {resume['epoch']}")
     try:
         from tqdm import tqdm
     except ImportError:  # pragma: no cover
         def tqdm(x, **kw):
             return x
     try:
-        for epoch in range(1, max_epochs + 1):
+        for epoch in range(first_epoch, max_epochs + 1):
             if chief:
                 print(f"\n----- Epoch {epoch} -----")
             if lr_warmup:
@@ -229,7 +356,10 @@ def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epo
                 max_val_acc = val_acc
                 if chief:
                     print("[INFO] Increased accuracy, saving model state")
-                    torch.save(net.state_dict(), best_state)
+                    try:
+                        save_atomically(net.state_dict(), best_state)
+                    except Exception as e:  # noqa: BLE001 - the previous best model is still there, the run goes on
+                        print(f"[INFO] Could not write {best_state.name} ({e}); the previous one stays")
             if val_loss < min_val_loss or epoch == 1:
                 no_improvement = 0
                 min_val_loss = val_loss
@@ -237,12 +367,28 @@ def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epo
                 no_improvement += 1
                 if chief:
                     print(f"[INFO] No reduction in loss for {no_improvement} epochs")
-            if no_improvement >= early_stop_patience:
+            stop = no_improvement >= early_stop_patience
+            if stop:
                 if chief:
                     print("[INFO] Stopping early")
-                break
-            if lr_scheduler and (not lr_warmup or epoch > lr_warmup.step_3):
+            elif lr_scheduler and (not lr_warmup or epoch > lr_warmup.step_3):
                 lr_scheduler.step(val_loss)
+            if run_info is not None:
+                # after every decision of this epoch; the generators stand where the loaders left them (their batch
+                # thread has ended with the epoch's last batch), the ranks' positions are gathered into the one file
+                ranks = dp.gather_object(_rank_state(net), dist)
+                if chief:
+                    book = {"max_val_acc": max_val_acc, "min_val_loss": min_val_loss, "no_improvement": no_improvement,
+                            "train_accs": train_accs, "train_losses": train_losses, "val_accs": val_accs,
+                            "val_losses": val_losses}
+                    try:
+                        save_atomically(collect_train_state(run_info, epoch, stop or epoch == max_epochs, stop, net,
+                                                            optimizer, lr_scheduler, book, ranks, train_dataloader),
+                                        Path(model_dir) / TRAIN_STATE_FILE)
+                    except Exception as e:  # noqa: BLE001 - a recovery file, never a reason to lose the run
+                        print(f"[INFO] Could not write {TRAIN_STATE_FILE} ({e}); the previous one stays")
+            if stop:
+                break
     except KeyboardInterrupt:
         print("[INFO] Stopping early")
         sync.close()
