@@ -292,6 +292,18 @@ int spk_model_param_counters_set(spk_model* m, const char* key, int64_t step, do
 int spk_model_train_counters_get(spk_model* m, uint64_t* steps, uint64_t* seed);
 int spk_model_train_counters_set(spk_model* m, uint64_t steps, uint64_t seed);
 
+/* loss_fn = nn.CrossEntropyLoss(weight, label_smoothing) (sykepic/train/train.py:127) for spk_train_forward_backward
+ * AND spk_eval_step (the reference validates with the same loss_fn).  class_weights_host: float32 [num_classes] or NULL
+ * (all ones).  Checked before any HIP call: a weight that is not finite or not above 0, or a label_smoothing outside
+ * [0, 1], is SPK_ERR_ARG.  With weights or label_smoothing > 0 the steps run the weighted / smoothed kernel, stats[0]
+ * accumulates n * loss of that loss, and the per-class counters below are kept; (NULL, 0) - the state of a new
+ * handle - returns to the plain kernel, bit for bit.  Synchronous. */
+int spk_model_set_loss(spk_model* m, const float* class_weights_host, float label_smoothing);
+/* Per class (rows seen, rows correct) over the training and validation steps since the last reset, int64
+ * [num_classes][2]; reset != 0 zeroes the counters after the read.  SPK_ERR_UNSUPPORTED while the loss is the default
+ * one (no counters are kept).  Synchronous. */
+int spk_model_class_counts_read(spk_model* m, int64_t* host, int reset);
+
 /* Test hook: copy activation `tensor_id` (spk_layer_desc.dst numbering) of the
  * most recent forward to the host as float32 NCHW ([n,c,h,w]; [n,c] for the
  * head).  The stem input (id 0) is not readable.  Synchronous. */
@@ -519,6 +531,12 @@ int spk_op_softmax(const float* z_dev, float* p_dev, int n, int c, float base, v
  * each in [0, c). */
 int spk_op_cross_entropy(const float* z_dev, const int64_t* labels_dev, int n, int c, float* stats_dev, float* dz_dev,
                          void* hip_stream);
+/* CrossEntropyLoss(weight = w, label_smoothing, reduction mean), the kernel spk_model_set_loss switches the steps to:
+ * stats[0] += n * loss, stats[1] as above; dz [n][c] (may be NULL) = d loss / d z; w_dev float32 [c] of positive weights
+ * or NULL (all ones); counts_dev int32 [c][2] (may be NULL) += per class (rows seen, rows correct).  label_smoothing
+ * outside [0, 1]: SPK_ERR_ARG.  Equal inputs give equal bits. */
+int spk_op_cross_entropy_ex(const float* z_dev, const int64_t* labels_dev, int n, int c, const float* w_dev,
+                            float label_smoothing, float* stats_dev, int* counts_dev, float* dz_dev, void* hip_stream);
 /* MaxPool2d(k, stride, pad): x [n,h,w,c] -> y [n,ho,wo,c].  idx == NULL: the eval path's kernel, dtype 0 bf16 / 1 fp16.
  * idx [n,ho,wo,c] bytes: the training step's kernel (bf16 only), which also saves the tap r * k + s of each maximum (the
  * first in that order among equal values).  c % 8 != 0: SPK_ERR_ARG; k * k > 255 or pad > k / 2: SPK_ERR_UNSUPPORTED. */

@@ -9,6 +9,7 @@
 #include "model.h"
 #include "tune_table.h"
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -176,6 +177,14 @@ int main(int argc, char** argv) {
     EXPECT(spk_model_param_counters_set(nullptr, "head.0.weight", 1, 1.0) == SPK_ERR_ARG);
     EXPECT(spk_model_train_counters_get(nullptr, &steps, &seed) == SPK_ERR_ARG);
     EXPECT(spk_model_train_counters_set(nullptr, 1, 2) == SPK_ERR_ARG);
+    // ... and so do the loss's: a null handle, a smoothing value outside [0, 1] (NaN included), null operands
+    int64_t counts[4] = {0};
+    int64_t labels[1] = {0};
+    EXPECT(spk_model_set_loss(nullptr, f, 0.1f) == SPK_ERR_ARG);
+    EXPECT(spk_model_class_counts_read(nullptr, counts, 1) == SPK_ERR_ARG);
+    EXPECT(spk_op_cross_entropy_ex(f, labels, 1, 4, nullptr, 1.5f, f, nullptr, nullptr, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_op_cross_entropy_ex(f, labels, 1, 4, nullptr, NAN, f, nullptr, nullptr, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_op_cross_entropy_ex(f, nullptr, 1, 4, f, 0.1f, f, nullptr, nullptr, nullptr) == SPK_ERR_ARG);
   }
 
   // ---- a small bottleneck graph: stem, pool, 1x1 / 3x3 / 1x1 + shortcut, pool, head ----

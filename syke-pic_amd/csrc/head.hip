@@ -231,6 +231,98 @@ __global__ __launch_bounds__(1024) void ce_kernel(const float* __restrict__ z,
   }
 }
 
+// F.cross_entropy(z, y, weight = w, label_smoothing = eps, reduction = "mean") with the same fused extras, in the same one
+// block of a row per wave.  With p = softmax(z_i), W = sum_i w[y_i], Sw = sum_c w[c]:
+//   loss     = [ (1 - eps) sum_i w[y_i] (lse_i - z[i][y_i]) + (eps / c) sum_i sum_j w[j] (lse_i - z[i][j]) ] / W
+//   dz[i][j] = [ (1 - eps) w[y_i] (p[i][j] - [j == y_i]) + (eps / c) (p[i][j] Sw - w[j]) ] / W
+// w == nullptr: all ones (W = n, Sw = c, exactly).  Every float sum has a fixed order (a thread's own terms in ascending
+// index, the xor butterfly of a wave, then the 16 waves in ascending order), so equal inputs give equal bits; the only
+// atomics are the integer adds of the per-class counters.  The smoothing sum is formed term by term as w[j] (lse - z[j]):
+// lse Sw - sum w z would cancel.  stats[0] += n loss (the reference accumulates loss.item() * len(y)), stats[1] += rows
+// whose arg-max (lowest index among the maxima) is the label; counts [c][2] (may be null) += per class (rows, correct rows).
+__global__ __launch_bounds__(1024) void ce_ex_kernel(const float* __restrict__ z, const int64_t* __restrict__ y, int n,
+                                                    int c, const float* __restrict__ w, float eps,
+                                                    float* __restrict__ stats, int* __restrict__ counts,
+                                                    float* __restrict__ dz) {
+  constexpr int WAVES = 16;
+  __shared__ float s_w[WAVES];
+  __shared__ float s_loss[WAVES];
+  __shared__ float s_corr[WAVES];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  // W: the pass over the labels in front of the row loop; every thread ends with the same bits
+  float W = (float)n, Sw = (float)c;
+  if (w) {
+    float part = 0.f;
+    for (int i = threadIdx.x; i < n; i += WAVES * 64) part += w[(int)y[i]];
+    part = wave_sum(part);
+    if (lane == 0) s_w[wave] = part;
+    __syncthreads();
+    W = 0.f;
+    for (int q = 0; q < WAVES; ++q) W += s_w[q];
+    float sp = 0.f;
+    for (int j = lane; j < c; j += 64) sp += w[j];
+    Sw = wave_sum(sp);
+  }
+  const bool smooth = eps > 0.f;
+  const float invW = 1.0f / W;
+  const float a = 1.0f - eps, b = eps / (float)c;
+  const float cb = b * invW;
+  float loss = 0.f, corr = 0.f;
+  for (int row = wave; row < n; row += WAVES) {
+    const float* zr = z + (size_t)row * c;
+    const int label = (int)y[row];
+    float mx = -INFINITY;
+    int arg = 0x7fffffff;
+    for (int j = lane; j < c; j += 64) {
+      const float v = zr[j];
+      if (v > mx) { mx = v; arg = j; }
+    }
+    // arg-max with torch's tie rule: lowest index among the maxima
+    for (int d = 32; d; d >>= 1) {
+      const float om = __shfl_xor(mx, d);
+      const int oa = __shfl_xor(arg, d);
+      if (om > mx || (om == mx && oa < arg)) { mx = om; arg = oa; }
+    }
+    float s = 0.f;
+    for (int j = lane; j < c; j += 64) s += expf(zr[j] - mx);
+    s = wave_sum(s);
+    const float lse = mx + logf(s);
+    float sm = 0.f;
+    if (smooth) {
+      for (int j = lane; j < c; j += 64) sm += (w ? w[j] : 1.f) * (lse - zr[j]);
+      sm = wave_sum(sm);
+    }
+    const float aw = a * (w ? w[label] : 1.f);
+    if (lane == 0) {
+      const bool hit = arg == label;
+      loss += aw * (lse - zr[label]) + b * sm;
+      corr += hit ? 1.f : 0.f;
+      if (counts && (unsigned)label < (unsigned)c) {
+        atomicAdd(counts + 2 * label, 1);
+        if (hit) atomicAdd(counts + 2 * label + 1, 1);
+      }
+    }
+    if (dz) {
+      const float inv = 1.0f / s;
+      const float ca = aw * invW;
+      for (int j = lane; j < c; j += 64) {
+        const float p = expf(zr[j] - mx) * inv;
+        float g = ca * (p - (j == label ? 1.f : 0.f));
+        if (smooth) g += cb * (p * Sw - (w ? w[j] : 1.f));
+        dz[(size_t)row * c + j] = g;
+      }
+    }
+  }
+  if (lane == 0) { s_loss[wave] = loss; s_corr[wave] = corr; }
+  __syncthreads();
+  if (threadIdx.x == 0) {   // fixed order
+    float tl = 0.f, tc = 0.f;
+    for (int q = 0; q < WAVES; ++q) { tl += s_loss[q]; tc += s_corr[q]; }
+    stats[0] += tl * invW * (float)n;
+    stats[1] += tc;
+  }
+}
+
 // SURVEY.md §8f rank 2 — per-ROI prediction from probabilities and per-class
 // thresholds (reference sykepic/compute/prediction.py:49-71): the
 // highest-probability class that clears ITS OWN threshold wins (lowest index on
@@ -327,5 +419,11 @@ int spk_launch_softmax(const float* z, float* p, int n, int c, float scale, hipS
 int spk_launch_ce(const float* z, const int64_t* y, int n, int c, float* stats, float* dlogits,
                   hipStream_t s) {
   hipLaunchKernelGGL(ce_kernel, dim3(1), dim3(1024), 0, s, z, y, n, c, stats, dlogits);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int spk_launch_ce_ex(const float* z, const int64_t* y, int n, int c, const float* w, float label_smoothing, float* stats,
+                     int* counts, float* dlogits, hipStream_t s) {
+  hipLaunchKernelGGL(ce_ex_kernel, dim3(1), dim3(1024), 0, s, z, y, n, c, w, label_smoothing, stats, counts, dlogits);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -175,6 +175,13 @@ struct spk_model {
   int grad_buckets = 0;
   hipEvent_t grad_ev[3] = {nullptr, nullptr, nullptr};
 
+  // the loss of spk_train_forward_backward and spk_eval_step (spk_model_set_loss): with neither weights nor smoothing
+  // the steps launch ce_kernel, otherwise ce_ex_kernel, which also fills the per-class counters
+  float* loss_w = nullptr;      // class weights [num_classes] on the device, or null
+  float loss_eps = 0.f;         // label smoothing
+  int* class_counts = nullptr;  // int32 [num_classes][2] on the device: (rows seen, rows correct) since the last reset
+  bool loss_ex() const { return loss_w != nullptr || loss_eps > 0.f; }
+
   uint64_t seed = 0;
   float bn_eps = 1e-5f, bn_momentum = 0.1f;   // BatchNorm2d(eps, momentum) of the graph (spk_model_set_bn)
   TrainState* train = nullptr;

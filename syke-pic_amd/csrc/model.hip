@@ -433,6 +433,8 @@ extern "C" void spk_model_destroy(spk_model* m) {
   if (m->w8pack) hipFree(m->w8pack);
   if (m->fp8_shadow) hipFree(m->fp8_shadow);
   if (m->s8) hipFree(m->s8);
+  if (m->loss_w) hipFree(m->loss_w);
+  if (m->class_counts) hipFree(m->class_counts);
   if (m->half_stream) hipStreamDestroy(m->half_stream);
   if (m->half_fork) hipEventDestroy(m->half_fork);
   if (m->half_join) hipEventDestroy(m->half_join);
@@ -1853,7 +1855,10 @@ extern "C" int spk_eval_step(spk_model* m, const void* x, int n, int h, int w, i
   float* logits = logits_out ? logits_out : (float*)((char*)m->arena + m->logits_off);
   SPK_TRY(spk_forward_eval_logits(m, x, n, h, w, layout, dtype, logits));
   // CrossEntropyLoss is a batch mean; the caller accumulates loss*n (train.py:269)
-  if (spk_launch_ce(logits, y, n, m->num_classes, stats, nullptr, m->stream))
+  // validation uses the loss the training step uses, as the reference's single loss_fn (spk_model_set_loss)
+  if (m->loss_ex() ? spk_launch_ce_ex(logits, y, n, m->num_classes, m->loss_w, m->loss_eps, stats, m->class_counts, nullptr,
+                                      m->stream)
+                   : spk_launch_ce(logits, y, n, m->num_classes, stats, nullptr, m->stream))
     return fail(SPK_ERR_HIP, "cross-entropy launch failed");
   return SPK_OK;
 }

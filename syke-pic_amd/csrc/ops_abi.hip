@@ -4,7 +4,8 @@
 // known operands and compare its output with autograd evaluated on the same (bf16-rounded) operands:
 //   conv + train-mode BatchNorm forward   torch Conv2d + BatchNorm2d(+add)(+ReLU), sykepic/train/train.py:240
 //   BatchNorm / conv backward             what loss.backward() runs for that layer,  sykepic/train/train.py:242
-//   Linear / softmax / CrossEntropyLoss    spk_op_linear, spk_op_linear_backward, spk_op_softmax, spk_op_cross_entropy
+//   Linear / softmax / CrossEntropyLoss    spk_op_linear, spk_op_linear_backward, spk_op_softmax, spk_op_cross_entropy,
+//                                          spk_op_cross_entropy_ex (class weights, label smoothing, per-class counters)
 //   MaxPool2d / AdaptiveAvgPool2d(1)       spk_op_maxpool, spk_op_maxpool_backward, spk_op_gavgpool, spk_op_gavgpool_backward
 //                                          (head.hip, pointwise.hip, train_kernels.hip; exact integer and float64 references)
 // Scratch is allocated and freed inside the call (these are not on any hot path).
@@ -845,6 +846,18 @@ extern "C" int spk_op_cross_entropy(const float* z, const int64_t* labels, int n
   hipStream_t s = (hipStream_t)stream;
   O_TRY(spk_launch_ce(z, labels, n, c, stats, dz, s), "cross-entropy");
   if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_cross_entropy: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_cross_entropy_ex(const float* z, const int64_t* labels, int n, int c, const float* w,
+                                       float label_smoothing, float* stats, int* counts, float* dz, void* stream) {
+  if (!z || !labels || !stats || n < 1 || c < 1) return ofail(SPK_ERR_ARG, "op_cross_entropy_ex: bad arguments");
+  if (!(label_smoothing >= 0.f && label_smoothing <= 1.f))
+    return ofail(SPK_ERR_ARG, "op_cross_entropy_ex: label_smoothing must be in [0, 1]");
+  if (!below_2g(n, c)) return ofail(SPK_ERR_UNSUPPORTED, "op_cross_entropy_ex: a tensor of 2^31 elements or more");
+  hipStream_t s = (hipStream_t)stream;
+  O_TRY(spk_launch_ce_ex(z, labels, n, c, w, label_smoothing, stats, counts, dz, s), "cross-entropy");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_cross_entropy_ex: kernel failed");
   return SPK_OK;
 }
 

@@ -366,6 +366,10 @@ int spk_launch_softmax(const float* z, float* p, int n, int c, float scale, hipS
 // stats[0] += sum_i CE_i ; stats[1] += #(argmax == y); dlogits (may be null) = (softmax - onehot)/n
 int spk_launch_ce(const float* z, const int64_t* y, int n, int c, float* stats, float* dlogits,
                   hipStream_t s);
+// the same with class weights w [c] (null: ones) and label smoothing: stats[0] += n * loss (the weighted mean), dlogits its
+// gradient; counts [c][2] int32 (may be null) += per class (rows seen, rows correct)
+int spk_launch_ce_ex(const float* z, const int64_t* y, int n, int c, const float* w, float label_smoothing, float* stats,
+                     int* counts, float* dlogits, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // Training kernels (train_kernels.hip, conv_wgrad.hip)

@@ -1047,7 +1047,11 @@ extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, in
 
   // ------------------------- loss + dlogits -------------------------
   const float* logits = (const float*)m->T(last);
-  K_TRY(spk_launch_ce(logits, y, n, m->num_classes, stats, (float*)t->G(last), s), "cross-entropy");
+  if (m->loss_ex())
+    K_TRY(spk_launch_ce_ex(logits, y, n, m->num_classes, m->loss_w, m->loss_eps, stats, m->class_counts,
+                           (float*)t->G(last), s), "cross-entropy");
+  else
+    K_TRY(spk_launch_ce(logits, y, n, m->num_classes, stats, (float*)t->G(last), s), "cross-entropy");
   mark(m, PH_LOSS);
   if (logits_out)
     HIP_TRY(hipMemcpyAsync(logits_out, logits, (size_t)n * m->num_classes * 4, hipMemcpyDeviceToDevice, s));
@@ -1354,6 +1358,56 @@ extern "C" int spk_model_train_counters_set(spk_model* m, uint64_t steps, uint64
   SPK_TRY(ensure_state(m));
   m->train->steps = (unsigned long long)steps;
   m->seed = seed;
+  return SPK_OK;
+}
+
+// loss_fn = nn.CrossEntropyLoss(weight, label_smoothing) of the training and validation steps (train.py:127).  The
+// arguments are checked before any HIP call; (NULL, 0) frees the buffers and the steps launch ce_kernel again.
+extern "C" int spk_model_set_loss(spk_model* m, const float* class_weights, float label_smoothing) {
+  if (!m) return tfail(SPK_ERR_ARG, "model_set_loss: null model");
+  if (!(label_smoothing >= 0.f && label_smoothing <= 1.f))
+    return tfail(SPK_ERR_ARG, "model_set_loss: label_smoothing must be in [0, 1]");
+  for (int c = 0; class_weights && c < m->num_classes; ++c)
+    if (!std::isfinite(class_weights[c]) || !(class_weights[c] > 0.f))
+      return tfail(SPK_ERR_ARG, "model_set_loss: weight of class " + std::to_string(c) + " is not a finite number above 0");
+  HIP_TRY(hipSetDevice(m->device));
+  HIP_TRY(hipStreamSynchronize(m->stream));   // a step still in flight reads the buffers about to change
+  const bool ex = class_weights != nullptr || label_smoothing > 0.f;
+  if (class_weights) {
+    if (!m->loss_w) HIP_TRY(hipMalloc((void**)&m->loss_w, (size_t)m->num_classes * sizeof(float)));
+    HIP_TRY(hipMemcpy(m->loss_w, class_weights, (size_t)m->num_classes * sizeof(float), hipMemcpyHostToDevice));
+  } else if (m->loss_w) {
+    HIP_TRY(hipFree(m->loss_w));
+    m->loss_w = nullptr;
+  }
+  if (ex && !m->class_counts) {
+    HIP_TRY(hipMalloc((void**)&m->class_counts, (size_t)m->num_classes * 2 * sizeof(int)));
+    HIP_TRY(hipMemsetAsync(m->class_counts, 0, (size_t)m->num_classes * 2 * sizeof(int), m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+  } else if (!ex && m->class_counts) {
+    HIP_TRY(hipFree(m->class_counts));
+    m->class_counts = nullptr;
+  }
+  m->loss_eps = label_smoothing;
+  return SPK_OK;
+}
+
+// Per-class (rows seen, rows correct) of the steps since the last reset, widened to int64.  Without a loss that counts
+// (spk_model_set_loss never called, or set back to the defaults) there is nothing to read: SPK_ERR_UNSUPPORTED.
+extern "C" int spk_model_class_counts_read(spk_model* m, int64_t* host, int reset) {
+  if (!m || !host) return tfail(SPK_ERR_ARG, "model_class_counts_read: bad arguments");
+  if (!m->class_counts)
+    return tfail(SPK_ERR_UNSUPPORTED, "model_class_counts_read: the default loss keeps no per-class counters "
+                                      "(spk_model_set_loss with weights or label smoothing does)");
+  HIP_TRY(hipSetDevice(m->device));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  std::vector<int> tmp((size_t)m->num_classes * 2);
+  HIP_TRY(hipMemcpy(tmp.data(), m->class_counts, tmp.size() * sizeof(int), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < tmp.size(); ++i) host[i] = tmp[i];
+  if (reset) {
+    HIP_TRY(hipMemsetAsync(m->class_counts, 0, tmp.size() * sizeof(int), m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+  }
   return SPK_OK;
 }
 

@@ -35,6 +35,26 @@ def _flag(s):
         raise ValueError(f"Not a boolean: {s}") from None
 
 
+def _smoothing(s):
+    v = float(s) if s.strip() else 0.0
+    if not 0.0 <= v <= 1.0:
+        raise ValueError(f"label_smoothing must be between 0.0 and 1.0. Got: {v}")
+    return v
+
+
+def _class_weights(s):
+    """``none`` / ``balanced`` (lower-cased) or the path of a file of ``name weight`` lines (loss.read_weight_file)."""
+    v = s.strip()
+    return (v.lower() or "none") if v.lower() in ("", "none", "balanced") else v
+
+
+def _checkpoint_on(s):
+    v = s.strip().lower() or "accuracy"
+    if v not in ("accuracy", "balanced_accuracy"):
+        raise ValueError(f"checkpoint_on must be accuracy or balanced_accuracy. Got: {s}")
+    return v
+
+
 def _index_prob_pairs(s):
     """``dropout = 1,0.5;2,0.3`` -> [(1, 0.5), (2, 0.3)] (list index in the head, probability)."""
     return [(int(i), float(p)) for i, p in (pair.split(",") for pair in s.split(";"))] if s else []
@@ -64,6 +84,10 @@ KEYS = {
         "learning_rate": (float, REQUIRED), "optimizer": (str, REQUIRED),
         # not in the reference: train_state.pth, written at the end of every epoch for `sykepic train --resume`
         "save_train_state": (_flag, "yes"),
+        # not in the reference either (its loss is nn.CrossEntropyLoss() with the defaults): the options of the fused
+        # loss (loss.py) and which validation figure selects best_state.pth; the defaults are the reference's behaviour
+        "label_smoothing": (_smoothing, "0"), "class_weights": (_class_weights, "none"),
+        "checkpoint_on": (_checkpoint_on, "accuracy"),
     },
     "lr_warmup": {
         "use": (_flag, REQUIRED), "factor_1": (float, REQUIRED), "factor_2": (float, REQUIRED), "step_1": (int, REQUIRED),

@@ -161,6 +161,17 @@ class GradSync:
         self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM)
         return tuple(float(v) for v in t.tolist())
 
+    def reduce_class_counts(self, counts):
+        """Per-class (rows seen, rows correct) of `HipNet.read_class_counts`, int64 [C, 2], summed over the ranks: every
+        rank gets the counters of the whole (sharded) pass, so balanced accuracy and what it decides are the same
+        everywhere.  Integers: the sum is exact."""
+        counts = torch.as_tensor(counts, dtype=torch.int64)
+        if self.world == 1:
+            return counts
+        t = counts.to(self.flat.device).contiguous().clone()
+        self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM)
+        return t.cpu()
+
 
 def _comm_device(dist, device):
     """Tensors of a collective live on the GPU for nccl (= RCCL) and on the host for gloo."""

@@ -102,6 +102,8 @@ SYMBOLS = {
     "spk_model_param_counters_set": (C.c_int, [_P, C.c_char_p, C.c_int64, C.c_double]),
     "spk_model_train_counters_get": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "spk_model_train_counters_set": (C.c_int, [_P, C.c_uint64, C.c_uint64]),
+    "spk_model_set_loss": (C.c_int, [_P, _P, C.c_float]),
+    "spk_model_class_counts_read": (C.c_int, [_P, _P, C.c_int]),
     "spk_model_read_activation": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64]),
     "spk_model_read_activation_grad": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64]),
     "spk_op_conv_bn_train_forward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P] + [C.c_int] * 9 + [_P]),
@@ -126,6 +128,7 @@ SYMBOLS = {
     "spk_op_linear_backward": (C.c_int, [_P] * 6 + [C.c_int] * 4 + [_P]),
     "spk_op_softmax": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, _P]),
     "spk_op_cross_entropy": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "spk_op_cross_entropy_ex": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_float, _P, _P, _P, _P]),
     "spk_op_maxpool": (C.c_int, [_P] * 3 + [C.c_int] * 8 + [_P]),
     "spk_op_maxpool_backward": (C.c_int, [_P] * 3 + [C.c_int] * 8 + [_P]),
     "spk_op_gavgpool": (C.c_int, [_P, _P] + [C.c_int] * 4 + [_P]),

@@ -500,6 +500,30 @@ class HipNet:
         s = self._stats_buf().tolist()
         return float(s[0]), float(s[1])
 
+    def set_loss(self, class_weights=None, label_smoothing=0.0):
+        """The loss of `forward_backward` and `eval_step`: ``nn.CrossEntropyLoss(weight=class_weights,
+        label_smoothing=label_smoothing)`` (spk_model_set_loss).  With weights or smoothing the steps also keep
+        per-class counters (`read_class_counts`); ``set_loss()`` returns to the plain loss, bit for bit."""
+        w = None
+        if class_weights is not None:
+            w = torch.as_tensor(class_weights, dtype=torch.float32).detach().cpu().contiguous().reshape(-1)
+            if w.numel() != self.num_classes:
+                raise ValueError(f"class_weights has {w.numel()} entries, the network has {self.num_classes} classes")
+        with torch.cuda.device(self.device):
+            lib.check(self._lib.spk_model_set_stream(self._h, self._stream()))
+            lib.check(self._lib.spk_model_set_loss(self._h, C.c_void_p(w.data_ptr()) if w is not None else None,
+                                                   float(label_smoothing)))
+        return self
+
+    def read_class_counts(self, reset=False):
+        """int64 [num_classes, 2]: per class (rows seen, rows correct) over the steps since the last reset.  Only a
+        loss with weights or smoothing keeps them (`set_loss`); with the plain loss the library refuses."""
+        out = torch.zeros((self.num_classes, 2), dtype=torch.int64)
+        with torch.cuda.device(self.device):
+            lib.check(self._lib.spk_model_set_stream(self._h, self._stream()))
+            lib.check(self._lib.spk_model_class_counts_read(self._h, C.c_void_p(out.data_ptr()), int(bool(reset))))
+        return out
+
     def eval_step(self, x, y, want_logits=False):
         self._ensure_init()
         x, n, h, w, layout, dtype = self._prep(x)

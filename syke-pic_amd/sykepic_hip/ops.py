@@ -573,6 +573,22 @@ def cross_entropy(z, labels, stats, dz=None):
         lib.check(so.spk_op_cross_entropy(_p(_f32c(z)), _p(labels), n, c, _p(_f32c(stats)), _p(_f32c(dz)), _stream(dev)))
 
 
+def cross_entropy_ex(z, labels, stats, weight=None, label_smoothing=0.0, counts=None, dz=None):
+    """spk_op_cross_entropy_ex: CrossEntropyLoss(weight, label_smoothing).  Adds (n * loss, correct rows) to stats [2]
+    float32 and per class (rows, correct rows) to counts [c, 2] int32 (None: no counters); writes dz [N,c] (the caller's
+    buffer; None: no gradient).  weight: float32 [c] on the device or None (all ones)."""
+    so = lib.load()
+    dev = z.device
+    n, c = z.shape
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.is_cuda and labels.numel() == n
+    assert weight is None or weight.numel() == c
+    assert counts is None or (counts.dtype == torch.int32 and counts.is_contiguous() and counts.is_cuda
+                              and counts.numel() == 2 * c)
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_cross_entropy_ex(_p(_f32c(z)), _p(labels), n, c, _p(_f32c(weight)), float(label_smoothing),
+                                             _p(_f32c(stats)), _p(counts), _p(_f32c(dz)), _stream(dev)))
+
+
 def maxpool(x, k, stride, pad, want_idx=False):
     """MaxPool2d on x [N,H,W,C] bf16 / fp16 (spk_op_maxpool).  want_idx: the training kernel, which also returns the
     saved taps [N,Ho,Wo,C] uint8; else the eval kernel.  Returns (y, idx or None)."""

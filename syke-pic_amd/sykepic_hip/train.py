@@ -24,6 +24,7 @@ from pathlib import Path
 import torch
 
 from . import arch, data, schedule
+from . import loss as loss_mod
 from .config import Settings, get_network, get_transforms
 from . import dp
 from .dp import GradSync
@@ -97,6 +98,12 @@ def main(args):
     model_data.set_data_loaders(im.batch_size, im.num_workers, train_transform, eval_transform, img_shape[0],
                                 rank=rank, world=world, device=gpu_tf)
     num_classes = len(model_data.le.classes_)
+    classes = [str(c) for c in model_data.le.classes_]
+    # the loss (loss.py): `balanced` weighs by the labels the train loader iterates, oversampled copies included
+    train_labels = list(model_data.train_y) + (list(model_data.over_y) if model_data.oversampled else [])
+    loss_fn = loss_mod.CrossEntropyLoss(loss_mod.resolve_class_weights(tr.class_weights, classes, train_labels),
+                                        tr.label_smoothing)
+    checkpoint_on = tr.checkpoint_on
     external_test = ds.external_test
     if external_test:
         extra_loader = data.extra_eval_dataloader(external_test, model_data, exclude=["Unclassified"])
@@ -108,8 +115,8 @@ def main(args):
     if resume:
         model_dir = Path(resume)
         state = load_train_state(model_dir)
-        check_train_state(state, network=mo.network, classes=[str(c) for c in model_data.le.classes_],
-                          img_shape=img_shape, optimizer=tr.optimizer, world=world)
+        check_train_state(state, network=mo.network, classes=classes, img_shape=img_shape, optimizer=tr.optimizer,
+                          world=world, loss=loss_fn.describe(), checkpoint_on=checkpoint_on)
     else:
         # model directory <path>/<network>[_<id>]; id "auto" = next free number, picked by rank 0 for the whole job
         # (another rank could already see the directory rank 0 has just made)
@@ -123,6 +130,8 @@ def main(args):
         _prob.drop_act_means(model_dir)   # exist_ok = yes: means of an earlier run do not belong to the weights about to be written
         model_data.save(model_dir)
         shutil.copy(args.config, model_dir / "config.ini")
+        if loss_fn.weight is not None:
+            loss_mod.write_weight_file(model_dir, classes, loss_fn.weight)
     if dist is not None:
         dist.barrier()
 
@@ -153,17 +162,18 @@ def main(args):
         # quirk Q3: the reference passes `verbose` positionally into `threshold`
         lr_scheduler = schedule.ReduceLROnPlateau(optimizer, "min", red.factor, red.patience, red.verbose)
 
-    run_info = {"network": mo.network, "classes": [str(c) for c in model_data.le.classes_],
-                "img_shape": [int(v) for v in img_shape], "optimizer": tr.optimizer, "world": world}
+    run_info = {"network": mo.network, "classes": classes, "img_shape": [int(v) for v in img_shape],
+                "optimizer": tr.optimizer, "world": world, "loss": loss_fn.describe(), "checkpoint_on": checkpoint_on}
     if state is not None and (state["early_stopped"] or state["epoch"] >= tr.max_epochs):
         # nothing left to train (raise `max_epochs` to extend a run that reached it): the reports of the best model
         if chief:
             print(f"[INFO] {model_dir}: training ended after epoch {state['epoch']}, nothing to resume")
         best_state = Path(model_dir) / "best_state.pth"
     else:
-        best_state = train_net(net, model_data.train_loader, model_data.val_loader, optimizer, None, tr.max_epochs,
+        best_state = train_net(net, model_data.train_loader, model_data.val_loader, optimizer, loss_fn, tr.max_epochs,
                                tr.early_stop_patience, model_dir, device, lr_scheduler, lr_warmup, dist=dist,
-                               run_info=run_info if tr.save_train_state else None, resume=state)
+                               run_info=run_info if tr.save_train_state else None, resume=state,
+                               checkpoint_on=checkpoint_on)
     if dist is not None:
         dist.barrier()
     net.load_state_dict(torch.load(best_state, map_location="cpu"))
@@ -215,8 +225,10 @@ def load_train_state(model_dir):
     return torch.load(path, map_location="cpu", weights_only=True)
 
 
-def check_train_state(state, network, classes, img_shape, optimizer, world):
-    """A resumed run must be the run that wrote the file: one line naming the first thing that differs."""
+def check_train_state(state, network, classes, img_shape, optimizer, world, loss=None, checkpoint_on="accuracy"):
+    """A resumed run must be the run that wrote the file: one line naming the first thing that differs.
+    loss: `CrossEntropyLoss.describe()` of the config (None: the defaults); a file without the key - every file written
+    before the loss had options - was trained with the defaults, and likewise for `checkpoint_on`."""
     if state.get("format") != TRAIN_STATE_FORMAT:
         raise ValueError(f"cannot resume: train_state.pth has format number {state.get('format')}, this version reads "
                          f"{TRAIN_STATE_FORMAT}")
@@ -229,6 +241,17 @@ def check_train_state(state, network, classes, img_shape, optimizer, world):
                 diff = sorted(set(was) ^ set(now))
                 was, now = f"{len(was)} classes", f"{len(now)} classes (differing: {', '.join(diff[:5]) or 'order'})"
             raise ValueError(f"cannot resume: {what} differs, train_state.pth has {was}, the config gives {now}")
+    if not loss_mod.same_loss(state.get("loss"), loss):
+        def show(d):
+            d = d or {}
+            w = d.get("class_weights")
+            return (f"label_smoothing {float(d.get('label_smoothing') or 0.0)}, "
+                    f"class_weights {'none' if w is None else [round(float(v), 6) for v in w[:4]] + (['...'] if len(w) > 4 else [])}")
+        raise ValueError(f"cannot resume: loss differs, train_state.pth has {show(state.get('loss'))}, the config gives "
+                         f"{show(loss)}")
+    if state.get("checkpoint_on", "accuracy") != checkpoint_on:
+        raise ValueError(f"cannot resume: checkpoint_on differs, train_state.pth has {state.get('checkpoint_on', 'accuracy')}, "
+                         f"the config gives {checkpoint_on}")
 
 
 def _rank_state(net):
@@ -284,15 +307,33 @@ def restore_train_state(state, net, optimizer, lr_scheduler, rank, train_loader)
 
 
 def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epochs, early_stop_patience,
-              model_dir, device, lr_scheduler=None, lr_warmup=None, dist=None, run_info=None, resume=None):
-    """loss_fn is accepted for signature compatibility; CrossEntropyLoss is
-    fused into the training step (the only loss the reference constructs).
+              model_dir, device, lr_scheduler=None, lr_warmup=None, dist=None, run_info=None, resume=None,
+              checkpoint_on="accuracy"):
+    """loss_fn: None (nn.CrossEntropyLoss() as the reference constructs it), a `loss.CrossEntropyLoss` or a
+    `torch.nn.CrossEntropyLoss`: its `weight` and `label_smoothing` go to the loss kernel fused into the training and
+    validation steps (`HipNet.set_loss`); another reduction than "mean" is a ValueError.
+    checkpoint_on: "accuracy" (the reference's rule) or "balanced_accuracy" - the mean per-class recall of the
+    validation pass, from the per-class counters the weighted / smoothed kernel keeps.  With the default loss that
+    choice runs the same kernel with unit weights (the same loss up to float32 round-off) for its counters.  With
+    any of the three away from its default the validation line also prints `Val Balanced Acc`; with all of them at
+    their defaults the step, the lines and the files are those of the plain loss.
+    Data parallelism: every rank normalises its loss by the weights of ITS batch (W = sum_i w[y_i]) and the gradients
+    are averaged over the ranks, as DistributedDataParallel does - not the mean of one global batch.
     run_info (network, classes, img_shape, optimizer, world): write `train_state.pth` at the end of every epoch;
     resume: the loaded file of an earlier run to continue behind its last finished epoch."""
+    loss = loss_mod.from_loss_fn(loss_fn)
+    if checkpoint_on not in ("accuracy", "balanced_accuracy"):
+        raise ValueError(f"checkpoint_on must be accuracy or balanced_accuracy. Got: {checkpoint_on}")
     net = net.to(device)
     chief = dist is None or dist.get_rank() == 0
     parallel = dist is not None and dist.is_initialized() and dist.get_world_size() > 1
     sync = GradSync(net, dist)
+    extended = not loss.is_default or checkpoint_on != "accuracy"
+    if extended:
+        unit = [1.0] * net.num_classes if loss.is_default else None     # (for the counters: see the docstring)
+        net.set_loss(loss.weight if unit is None else unit, loss.label_smoothing)
+    elif hasattr(net, "set_loss"):
+        net.set_loss(None, 0.0)
     max_val_acc, min_val_loss, no_improvement = 0, 0, 0
     train_accs, train_losses, val_accs, val_losses = [], [], [], []
     best_state = Path(model_dir) / "best_state.pth"
@@ -340,6 +381,8 @@ def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epo
             dp.sync_buffers(net, dist)
             net.eval()
             net.reset_stats()
+            if extended:
+                net.read_class_counts(reset=True)      # drop the training pass's counts
             seen = 0
             for batch in val_dataloader:
                 net.eval_step(batch[0], batch[1])
@@ -349,13 +392,23 @@ def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epo
             val_acc, val_loss = correct / seen, loss_sum / seen
             val_accs.append(val_acc)
             val_losses.append(val_loss)
+            criterion = val_acc
+            if extended:
+                counts = sync.reduce_class_counts(net.read_class_counts(reset=True))
+                val_bal = loss_mod.balanced_accuracy(counts.tolist())
+                if checkpoint_on == "balanced_accuracy":
+                    criterion = val_bal
             if chief:
-                print(f"[STAT] Val Acc: {val_acc:.3f}, Val Loss: {val_loss:.3f}")
+                if extended:
+                    print(f"[STAT] Val Acc: {val_acc:.3f}, Val Loss: {val_loss:.3f}, Val Balanced Acc: {val_bal:.3f}")
+                else:
+                    print(f"[STAT] Val Acc: {val_acc:.3f}, Val Loss: {val_loss:.3f}")
                 _plot(train_accs, train_losses, val_accs, val_losses, Path(model_dir), epoch)
-            if val_acc > max_val_acc:
-                max_val_acc = val_acc
+            if criterion > max_val_acc:
+                max_val_acc = criterion
                 if chief:
-                    print("[INFO] Increased accuracy, saving model state")
+                    print("[INFO] Increased balanced accuracy, saving model state"
+                          if checkpoint_on == "balanced_accuracy" else "[INFO] Increased accuracy, saving model state")
                     try:
                         save_atomically(net.state_dict(), best_state)
                     except Exception as e:  # noqa: BLE001 - the previous best model is still there, the run goes on
