@@ -510,6 +510,48 @@ int spk_op_stem3_train(const void* x_dev, const float* w_dev, const void* dy_dev
  *     0 the eval path's LDS-window kernel, 1 dw_dgrad_px_kernel, 2 the gather kernels, -1 none */
 int spk_op_mbconv_geometry(int kind, int m, int channels, int hw, int s_hidden, int out[8]);
 
+/* --- Test hooks: single operators of the MBConv EVAL path and the eval stems ---
+ * (csrc/conv_igemm.hip PADC / GATE, csrc/effnet.hip, csrc/conv_stem.hip): the pack and launch calls the model executor
+ * makes for ONE such layer, through its own dispatch functions.  Every pointer is device memory, activations are fp16
+ * NHWC with exactly the stated channel count stored, parameters float32.  Synchronous.
+ *
+ * 1x1 conv + folded BatchNorm (+ shortcut) + activation on tensors whose channel counts are multiples of 8 only: the
+ * GEMM is padded to multiples of 64 inside (spk_launch_pack_padded, ConvArgs::cin_s / cout_s).  x [n,h,w,cin], w
+ * [cout][cin], res (optional) and y [n,h,w,cout].  gate (optional) float32 [n][cin]: the activation operand is
+ * fp16(x * gate), the squeeze-excitation scaling multiplied in where the conv stages its operand (spk_set_gate).
+ * act: SPK_ACT_*.  Honours spk_op_conv_pin; SPK_ERR_UNSUPPORTED ("does not fit") for a pinned flavour the padded or gated
+ * path does not instantiate. */
+int spk_op_conv1x1_padded(const void* x_dev, const float* w_dev, const float* bn_scale_dev, const float* bn_bias_dev,
+                          const void* res_dev, const float* gate_dev, void* y_dev, int n, int h, int w, int cin, int cout,
+                          int act, int split, void* hip_stream);
+/* Squeeze-excitation of the eval path from the caller's pool partials [n][chunks][c] (sums over hw, as the depthwise
+ * kernels leave them): hid [n][sq] = act1(W1 . mean + b1), scale [n][c] = act2(W2 . hid + b2), y = x * scale (y NULL:
+ * the gates only).  w1 [sq][c], w2 [c][sq] (transposed inside, as spk_commit does).  gate_kind 0: SiLU, Sigmoid; 1: ReLU,
+ * Hardsigmoid.  The kernels keep hid directly behind the gates: hid_out must be scale_out + n * c (one buffer). */
+int spk_op_se_eval(const void* x_dev, const float* partial_dev, int chunks, const float* w1_dev, const float* b1_dev,
+                   const float* w2_dev, const float* b2_dev, float* hid_out_dev, float* scale_out_dev, void* y_dev, int n,
+                   int hw, int channels, int squeeze, int gate_kind, void* hip_stream);
+/* The 3x3 stride-2 pad-1 RGB stem of the eval path: x [n][h][w rounded up to even][4] fp16 holding pixel values x 255
+ * (zeros in channel 3 and the pad column), w [cout][3][3][3], y [n,ho,wo,cout]; 1 / 255 is folded into the epilogue
+ * scale as spk_commit does.  cout a multiple of 8, at most 256. */
+int spk_op_stem3_eval(const void* x_dev, const float* w_dev, const float* bn_scale_dev, const float* bn_bias_dev,
+                      void* y_dev, int n, int h, int w, int cout, int act, void* hip_stream);
+/* The 7x7 stride-2 pad-3 stem (3 -> 64, ReLU) of the eval path on the same input layout, w [64][7][7][3], split: hi +
+ * lo fp16 weight images.  pool_y NULL: y [n,ho,wo,64].  pool_y set: the kernel variant that also applies the 3x3
+ * stride-2 pad-1 max-pool and writes ONLY pool_y [n,(ho-1)/2+1,(wo-1)/2+1,64] (y is not touched and may be NULL). */
+int spk_op_stem7_eval(const void* x_dev, const float* w_dev, const float* bn_scale_dev, const float* bn_bias_dev,
+                      void* y_dev, void* pool_y_dev, int n, int h, int w, int split, void* hip_stream);
+/* What the launchers of those kernels choose (host arithmetic only, no GPU needed; the launchers' own helpers):
+ *   kind 0 (squeeze-excitation gates: a = n, b = chunks, c = channels, d = hidden units): out = CH instantiation of
+ *     se_fc1 (0: the run-time loop), clamped surplus loads of the run-time loop's last step, images of the last block,
+ *     hidden units the last fc1 block leaves out, staging passes of se_fc2, channel tiles of se_fc2, channels of the last
+ *     tile, image blocks
+ *   kind 1 (se_scale: a = n, b = hw, c = channels): out = grid x, blocks that would cover one image once
+ *   kind 2 (3x3 stem: a = ho, b = wo, c = cout): out = GT instantiation (0: run-time divisions)
+ *   kind 3 (padded / gated 1x1 conv: a = tile config, b = main-loop flavour, c = GEMM couts, d = split + 2 x gated):
+ *     out = narrowed tile config, DMA template argument of the instantiation or -3 when there is none */
+int spk_op_mbconv_eval_geometry(int kind, int a, int b, int c, int d, int out[8]);
+
 /* --- Test hooks: single operators of the classifier head, the loss and the pooling layers ---
  * (csrc/head.hip, csrc/pointwise.hip, csrc/train_kernels.hip): the launches `net(x)`, `criterion(out, y)` and
  * `loss.backward()` (sykepic/train/train.py:240-242, sykepic/compute/probability.py:189-194) reach for ONE such layer,

@@ -778,7 +778,7 @@ int launch_cfg(const ConvArgs& a, int mode, hipStream_t s, int* m_tiles_out) {
   }
   if (a.dt == DT_F16 && a.pool_y) {
     // gated activation operand (spk_set_gate): the register-staged flavour only
-    if (a.kh != 1 || a.stride != 1 || a.pad != 0 || a.dma != 0) return -3;
+    if (a.kh != 1 || a.stride != 1 || a.pad != 0 || spk_conv_padc_flavour(a.dma, true) < 0) return -3;
     if (a.splitw) return launch_one<BM, BN, WARPS_M, WARPS_N, CONV_MODE_GENERIC, DT_F16, 1, 0, 3>(a, s, m_tiles, n_tiles);
     return launch_one<BM, BN, WARPS_M, WARPS_N, CONV_MODE_GENERIC, DT_F16, 0, 0, 3>(a, s, m_tiles, n_tiles);
   }
@@ -787,9 +787,10 @@ int launch_cfg(const ConvArgs& a, int mode, hipStream_t s, int* m_tiles_out) {
     // stored channels != padded GEMM channels: the three flavours instantiated with the channel checks
 #define SPK_GO_PAD(SW)                                                                                        \
   do {                                                                                                        \
-    if (a.dma == 0) return launch_one<BM, BN, WARPS_M, WARPS_N, CONV_MODE_GENERIC, DT_F16, SW, 0, 2>(a, s, m_tiles, n_tiles); \
-    if (a.dma < 0 || a.dma == 3) return launch_one<BM, BN, WARPS_M, WARPS_N, CONV_MODE_GENERIC, DT_F16, SW, 2, 2>(a, s, m_tiles, n_tiles); \
-    if (a.dma == 6) return launch_one<BM, BN, WARPS_M, WARPS_N, CONV_MODE_GENERIC, DT_F16, SW, 4, 2>(a, s, m_tiles, n_tiles); \
+    const int fl = spk_conv_padc_flavour(a.dma, false);                                                       \
+    if (fl == 0) return launch_one<BM, BN, WARPS_M, WARPS_N, CONV_MODE_GENERIC, DT_F16, SW, 0, 2>(a, s, m_tiles, n_tiles); \
+    if (fl == 2) return launch_one<BM, BN, WARPS_M, WARPS_N, CONV_MODE_GENERIC, DT_F16, SW, 2, 2>(a, s, m_tiles, n_tiles); \
+    if (fl == 4) return launch_one<BM, BN, WARPS_M, WARPS_N, CONV_MODE_GENERIC, DT_F16, SW, 4, 2>(a, s, m_tiles, n_tiles); \
     return -3;                                                                                                \
   } while (0)
     if (a.splitw) SPK_GO_PAD(1);
@@ -834,9 +835,22 @@ int spk_conv_m_tiles(int M, int Cout, int mode) {
   return (M + bm - 1) / bm;
 }
 
+int spk_conv_narrow_cfg(int cfg, int Cout, int splitw) {
+  if (cfg == 5 && (Cout % 256 || splitw)) cfg = 4;
+  if ((cfg == 0 || cfg == 4) && Cout % 128) cfg = 3;
+  return cfg;
+}
+
+int spk_conv_padc_flavour(int dma, bool gated) {
+  if (gated) return dma == 0 ? 0 : -3;   // gated activation operand: the register-staged flavour only
+  if (dma == 0) return 0;                // register-staged
+  if (dma < 0 || dma == 3) return 2;     // LDS-DMA, two stages (also the default)
+  if (dma == 6) return 4;                // LDS-DMA, one stage
+  return -3;
+}
+
 static int launch_with(const ConvArgs& a, int mode, int cfg, hipStream_t s, int* m_tiles_out) {
-  if (cfg == 5 && (a.Cout % 256 || a.splitw)) cfg = 4;
-  if ((cfg == 0 || cfg == 4) && a.Cout % 128) cfg = 3;
+  cfg = spk_conv_narrow_cfg(cfg, a.Cout, a.splitw);
   switch (cfg) {
     case 0: return launch_cfg<128, 128, 2, 2>(a, mode, s, m_tiles_out);
     case 1: return launch_cfg<256, 64, 4, 1>(a, mode, s, m_tiles_out);

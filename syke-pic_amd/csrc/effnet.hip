@@ -12,6 +12,7 @@
 #include "dw_util.h"
 
 #include <algorithm>
+#include <vector>
 
 namespace {
 
@@ -276,6 +277,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const bf16_t* __restrict__ 
 // IPB images - with one image per block the two excitation kernels re-read the fc weights once per image through L2
 // (c 2688: 2 x 300 MB per layer) and ran 30-100 us; fixed-order shuffle + LDS reduction.  hid[img][sq].
 constexpr int SE_IPB = 8;
+constexpr int SE_FC2_STAGE = 4 * 256;   // hid values se_fc2_kernel stages per pass: four loads per thread
 // CH: the number of pool-partial rows per image when it is 1 ... 4 or 8 (what the depthwise kernels write at batch >= 32),
 // else 0 = run-time count.  With a compile-time count the IPB x CH partial loads of a channel are all in flight
 // together; the run-time loop issued them one after the other, a chain of up to 32 L2 round trips per block (the kernel
@@ -368,7 +370,7 @@ __global__ __launch_bounds__(256) void se_fc2_kernel(const float* __restrict__ h
   extern __shared__ float sh[];  // hid[sq][IPB]
   const int img0 = blockIdx.x * SE_IPB;
   const int nim = min(SE_IPB, n - img0);
-  for (int k0 = 0; k0 < sq * SE_IPB; k0 += 4 * 256) {   // four loads in flight per thread, then the stores
+  for (int k0 = 0; k0 < sq * SE_IPB; k0 += SE_FC2_STAGE) {   // four loads in flight per thread, then the stores
     float hv[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -447,6 +449,18 @@ int spk_launch_pack_tapmajor(const float* w, float* out, int c, int rows, int c_
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+int spk_pack_stem3(const float* w_dev, float* out_dev, int cout, int cin, int cout_p, hipStream_t s) {
+  std::vector<float> w((size_t)cout * 9 * cin), out((size_t)36 * cout_p, 0.f);
+  if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(w.data(), w_dev, w.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return -1;
+  for (int co = 0; co < cout; ++co)
+    for (int t = 0; t < 9; ++t)
+      for (int c = 0; c < cin; ++c) out[(size_t)(t * 4 + c) * cout_p + co] = w[((size_t)co * 9 + t) * cin + c];
+  return hipMemcpy(out_dev, out.data(), out.size() * 4, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+}
+
+int spk_stem3_gt(int c) { return (c / 8 >= 4 && c / 8 <= 6) ? c / 8 : 0; }
+
 int spk_launch_stem3x3(const bf16_t* x, const float* w, const float* scale, const float* bias, bf16_t* y, int n, int h,
                        int wid, int wstride, int ho, int wo, int c, int c_p, int act, int dt, hipStream_t s) {
   const size_t total = (size_t)n * ho * wo * (c / 8);
@@ -455,7 +469,7 @@ int spk_launch_stem3x3(const bf16_t* x, const float* w, const float* scale, cons
 #define SPK_STEM(GT) \
   hipLaunchKernelGGL((stem3x3_kernel<DT_F16, GT>), grid, dim3(256), (size_t)29 * c * 4, s, x, w, scale, bias, y, n, h, wid, \
                      wstride, ho, wo, c, c_p, act)
-  switch (c / 8) {
+  switch (spk_stem3_gt(c)) {
     case 4: SPK_STEM(4); break;
     case 5: SPK_STEM(5); break;
     case 6: SPK_STEM(6); break;
@@ -498,6 +512,16 @@ int spk_launch_dwconv(const bf16_t* x, const float* w, const float* scale, const
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+int spk_se_fc1_ch(int chunks) { return (chunks >= 1 && chunks <= 4) || chunks == 8 ? chunks : 0; }
+int spk_se_ipb() { return SE_IPB; }
+int spk_se_fc2_stage() { return SE_FC2_STAGE; }
+int spk_se_scale_grid(int n, size_t per_img) {
+  int gx = (int)((per_img + 255) / 256);
+  const int want = std::max(1, 4096 / n);  // about 16 blocks per CU over the whole batch
+  if (gx > want) gx = want;
+  return gx;
+}
+
 // squeeze-excitation gate on a depthwise output whose pool partials [n][chunks][c_p] the depthwise kernel wrote
 int spk_launch_se(const bf16_t* x, bf16_t* y, const float* partial, int chunks, float* scale, const float* w1,
                   const float* b1, const float* w2t, const float* b2, int n, int hw, int c, int c_p, int sq, int dt,
@@ -509,7 +533,7 @@ int spk_launch_se(const bf16_t* x, bf16_t* y, const float* partial, int chunks, 
   hipLaunchKernelGGL((se_fc1_kernel<CH, G>), dim3(ig, (sq + 3) / 4), dim3(256), 0, s, partial, chunks, 1.0f / (float)hw, w1, \
                      b1, hid, n, c, c_p, sq)
 #define SPK_FC1_ALL(G)                 \
-  switch (chunks) {                    \
+  switch (spk_se_fc1_ch(chunks)) {     \
     case 1: SPK_FC1(1, G); break;      \
     case 2: SPK_FC1(2, G); break;      \
     case 3: SPK_FC1(3, G); break;      \
@@ -529,9 +553,6 @@ int spk_launch_se(const bf16_t* x, bf16_t* y, const float* partial, int chunks, 
   if (!y) return hipGetLastError() == hipSuccess ? 0 : -1;   // gates only
   const size_t per_img = (size_t)hw * (c_p / 8);
   if (per_img >= ((size_t)1 << 31)) return -2;
-  int gx = (int)((per_img + 255) / 256);
-  const int want = std::max(1, 4096 / n);  // about 16 blocks per CU over the whole batch
-  if (gx > want) gx = want;
-  hipLaunchKernelGGL(se_scale_kernel<DT_F16>, dim3(gx, n), dim3(256), 0, s, x, scale, y, hw, c_p);
+  hipLaunchKernelGGL(se_scale_kernel<DT_F16>, dim3(spk_se_scale_grid(n, per_img), n), dim3(256), 0, s, x, scale, y, hw, c_p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

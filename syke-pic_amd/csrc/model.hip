@@ -630,17 +630,9 @@ static bool layer_zero_sum(const spk_model* m, const Layer& L) {
          (L.mode == CONV_MODE_GENERIC || L.mode == CONV_MODE_STEM) && !layer_split(m, L);
 }
 
-// 3x3 RGB stem: master [cout][3][3][cin<=3] -> fp32 [9 taps][4][cout_p] (host repack: 1.3k floats, once per load)
+// 3x3 RGB stem: master [cout][3][3][cin<=3] -> fp32 [9 taps][4][cout_p] (spk_pack_stem3, effnet.hip)
 static int pack_stem3(spk_model* m, const Layer& L) {
-  const int cin = L.d.cin, cout = L.d.cout, cp = L.cout_p;
-  std::vector<float> w((size_t)cout * 9 * cin), out((size_t)36 * cp, 0.f);
-  if (hipStreamSynchronize(m->stream) != hipSuccess ||
-      hipMemcpy(w.data(), m->P(L.p_w), w.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
-    return -1;
-  for (int co = 0; co < cout; ++co)
-    for (int t = 0; t < 9; ++t)
-      for (int c = 0; c < cin; ++c) out[(size_t)(t * 4 + c) * cp + co] = w[((size_t)co * 9 + t) * cin + c];
-  return hipMemcpy(m->dwpack + L.wpack_off, out.data(), out.size() * 4, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+  return spk_pack_stem3(m->P(L.p_w), m->dwpack + L.wpack_off, L.d.cout, L.d.cin, L.cout_p, m->stream);
 }
 
 int spk_commit(spk_model* m) {

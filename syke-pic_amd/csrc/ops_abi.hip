@@ -802,6 +802,176 @@ extern "C" int spk_op_mbconv_geometry(int kind, int M, int C, int HW, int S, int
   return ofail(SPK_ERR_ARG, "op_mbconv_geometry: kind 0 ... 4");
 }
 
+// ---- the MBConv EVAL kernels and the eval stems, one layer at a time: the pack and launch calls spk_commit and
+// run_conv_eval / spk_run_layer_eval (model.hip) make for a padded-channel 1x1 conv (with or without the squeeze-
+// excitation gates in its operand), a squeeze-excitation layer, the 3x3/2 RGB stem and the 7x7/2 ResNet stem (with or
+// without the fused max-pool), on caller-provided fp16 buffers.  Arguments are checked before any HIP call. ----
+namespace {
+int pad64(int c) { return (c + 63) / 64 * 64; }
+bool act_ok(int act) { return act == SPK_ACT_NONE || act == SPK_ACT_RELU || act == SPK_ACT_SILU || act == SPK_ACT_HSWISH; }
+// folded BatchNorm vectors as spk_commit lays them out: [scale x factor | shift], cout_p entries each, zeros on padding
+float* staged_scale_bias(Scratch& sc, const float* scale, const float* bias, int cout, int cout_p, float factor, hipStream_t s) {
+  float* f = sc.get<float>((size_t)2 * cout_p);
+  if (!f) return nullptr;
+  if (hipMemsetAsync(f, 0, (size_t)2 * cout_p * 4, s) != hipSuccess ||
+      hipMemcpyAsync(f, scale, (size_t)cout * 4, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(f + cout_p, bias, (size_t)cout * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return nullptr;
+  if (factor != 1.f && spk_launch_scale_inplace(f, factor, cout, s)) return nullptr;
+  return f;
+}
+}  // namespace
+
+extern "C" int spk_op_conv1x1_padded(const void* x, const float* w, const float* bn_scale, const float* bn_bias,
+                                     const void* res, const float* gate, void* y, int n, int h, int wd, int cin, int cout,
+                                     int act, int split, void* stream) {
+  if (!x || !w || !bn_scale || !bn_bias || !y || n < 1 || h < 1 || wd < 1 || cin < 8 || cout < 8 || cin % 8 || cout % 8 ||
+      !act_ok(act))
+    return ofail(SPK_ERR_ARG, "op_conv1x1_padded: bad arguments (channels multiples of 8, act 0 ... 3)");
+  const int cin_p = pad64(cin), cout_p = pad64(cout), M = n * h * wd;
+  if ((size_t)n * h * wd * cin * 2 >= 0x80000000ull || (size_t)n * h * wd * cout * 2 >= 0x80000000ull)
+    return ofail(SPK_ERR_UNSUPPORTED, "op_conv1x1_padded: an operand of 2 GiB or more (split the batch)");
+  hipStream_t s = (hipStream_t)stream;
+  Scratch sc;
+  bf16_t* wp = sc.get<bf16_t>((size_t)2 * cout_p * cin_p);
+  if (!wp) return ofail(SPK_ERR_HIP, "hipMalloc failed");
+  float* sb = staged_scale_bias(sc, bn_scale, bn_bias, cout, cout_p, 1.f, s);
+  if (!sb) return ofail(SPK_ERR_HIP, "op_conv1x1_padded: staging failed");
+  O_TRY(spk_launch_pack_padded(w, wp, cout, 1, cin, cout_p, cin_p, DT_F16, split != 0, s), "pack_padded");
+  ConvArgs a;
+  memset(&a, 0, sizeof a);
+  a.cfg = a.dma = -1;
+  a.cls_ph = a.cls_pw = -1;
+  a.x = (const bf16_t*)x; a.w = wp; a.y = (bf16_t*)y; a.res = (const bf16_t*)res; a.scale = sb; a.bias = sb + cout_p;
+  a.N = n; a.H = h; a.W = wd; a.Cin = cin_p; a.Ho = h; a.Wo = wd; a.Cout = cout_p;
+  a.cin_s = cin != cin_p ? cin : 0;
+  a.cout_s = cout != cout_p ? cout : 0;
+  a.kh = a.kw = 1; a.stride = 1; a.M = M; a.K = cin_p; a.relu = act; a.dt = DT_F16; a.splitw = split != 0;
+  a.x_bytes = (unsigned)((size_t)M * cin * 2);
+  a.w_bytes = (unsigned)((size_t)cout_p * cin_p * 2 * (split ? 2 : 1));
+  if (gate) spk_set_gate(a, gate, cin);
+  O_CONV(spk_conv_launch(a, CONV_MODE_GENERIC, s, nullptr), "padded conv1x1 launch");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_conv1x1_padded: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_se_eval(const void* x, const float* partial, int chunks, const float* w1, const float* b1,
+                              const float* w2, const float* b2, float* hid_out, float* scale_out, void* y, int n, int hw,
+                              int c, int sq, int gate_kind, void* stream) {
+  if (!partial || !w1 || !b1 || !w2 || !b2 || !hid_out || !scale_out || (y && !x) || chunks < 1 || n < 1 || hw < 1 ||
+      c < 8 || c % 8 || sq < 1 || (gate_kind != 0 && gate_kind != 1))
+    return ofail(SPK_ERR_ARG, "op_se_eval: bad arguments (c a multiple of 8, gate kind 0 or 1)");
+  // spk_launch_se keeps its hidden vector directly behind the gates, as the model's scratch does
+  if (hid_out != scale_out + (size_t)n * c)
+    return ofail(SPK_ERR_ARG, "op_se_eval: hid_out must be scale_out + n * c (one buffer, the layout of the model's scratch)");
+  if ((size_t)n * hw * c >= ((size_t)1 << 31) || (size_t)n * chunks * c >= ((size_t)1 << 31))
+    return ofail(SPK_ERR_UNSUPPORTED, "op_se_eval: a tensor of 2^31 elements or more");
+  hipStream_t s = (hipStream_t)stream;
+  Scratch sc;
+  float* w2t = sc.get<float>((size_t)sq * c);
+  if (!w2t) return ofail(SPK_ERR_HIP, "hipMalloc failed");
+  O_TRY(spk_launch_pack_tapmajor(w2, w2t, c, sq, c, s), "pack_tapmajor");
+  O_TRY(spk_launch_se(y ? (const bf16_t*)x : nullptr, (bf16_t*)y, partial, chunks, scale_out, w1, b1, w2t, b2, n, hw, c, c,
+                      sq, DT_F16, s, gate_kind), "squeeze-excitation");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_se_eval: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_stem3_eval(const void* x, const float* w, const float* bn_scale, const float* bn_bias, void* y, int n,
+                                 int h, int wd, int cout, int act, void* stream) {
+  if (!x || !w || !bn_scale || !bn_bias || !y || n < 1 || h < 1 || wd < 1 || cout < 8 || cout % 8 || !act_ok(act))
+    return ofail(SPK_ERR_ARG, "op_stem3_eval: bad arguments (cout a multiple of 8, act 0 ... 3)");
+  if (cout > 256) return ofail(SPK_ERR_UNSUPPORTED, "op_stem3_eval: 256 output channels at most");
+  hipStream_t s = (hipStream_t)stream;
+  const int cout_p = pad64(cout), wst = (wd + 1) & ~1, ho = (h - 1) / 2 + 1, wo = (wd - 1) / 2 + 1;
+  Scratch sc;
+  float* wt = sc.get<float>((size_t)36 * cout_p);
+  if (!wt) return ofail(SPK_ERR_HIP, "hipMalloc failed");
+  float* sb = staged_scale_bias(sc, bn_scale, bn_bias, cout, cout_p, 1.0f / SPK_INPUT_SCALE, s);
+  if (!sb) return ofail(SPK_ERR_HIP, "op_stem3_eval: staging failed");
+  O_TRY(spk_pack_stem3(w, wt, cout, 3, cout_p, s), "pack_stem3");
+  const int r = spk_launch_stem3x3((const bf16_t*)x, wt, sb, sb + cout_p, (bf16_t*)y, n, h, wst, wst, ho, wo, cout, cout_p,
+                                   act, DT_F16, s);
+  if (r == -2) return ofail(SPK_ERR_UNSUPPORTED, "op_stem3_eval: shape not supported");
+  if (r) return ofail(SPK_ERR_HIP, "op_stem3_eval: launch failed");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_stem3_eval: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_stem7_eval(const void* x, const float* w, const float* bn_scale, const float* bn_bias, void* y,
+                                 void* pool_y, int n, int h, int wd, int split, void* stream) {
+  if (!x || !w || !bn_scale || !bn_bias || (!y && !pool_y) || n < 1 || h < 1 || wd < 1)
+    return ofail(SPK_ERR_ARG, "op_stem7_eval: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  const int wst = (wd + 1) & ~1, ho = (h - 1) / 2 + 1, wo = (wd - 1) / 2 + 1, kpad = 256;
+  if ((size_t)n * h * wst * 8 >= 0x80000000ull || (size_t)n * ho * wo * 128 >= 0x80000000ull)
+    return ofail(SPK_ERR_UNSUPPORTED, "op_stem7_eval: an operand of 2 GiB or more (split the batch)");
+  Scratch sc;
+  bf16_t* wp = sc.get<bf16_t>((size_t)2 * 64 * kpad);
+  if (!wp) return ofail(SPK_ERR_HIP, "hipMalloc failed");
+  float* sb = staged_scale_bias(sc, bn_scale, bn_bias, 64, 64, 1.0f / SPK_INPUT_SCALE, s);
+  if (!sb) return ofail(SPK_ERR_HIP, "op_stem7_eval: staging failed");
+  O_TRY(spk_launch_pack_weights(w, wp, 64, 7, 7, 3, CONV_MODE_STEM, DT_F16, split != 0, s), "pack_weights");
+  ConvArgs a;
+  memset(&a, 0, sizeof a);
+  a.cfg = a.dma = -1;
+  a.cls_ph = a.cls_pw = -1;
+  a.x = (const bf16_t*)x; a.w = wp; a.y = (bf16_t*)y; a.scale = sb; a.bias = sb + 64;
+  a.N = n; a.H = h; a.W = wst; a.Cin = 4; a.Ho = ho; a.Wo = wo; a.Cout = 64;
+  a.kh = a.kw = 7; a.stride = 2; a.pad = 3; a.M = n * ho * wo; a.K = kpad; a.relu = 1; a.dt = DT_F16; a.splitw = split != 0;
+  a.x_bytes = (unsigned)((size_t)n * h * wst * 4 * 2);
+  a.w_bytes = (unsigned)((size_t)64 * kpad * 2 * (split ? 2 : 1));
+  if (pool_y) {   // the max-pool layer that follows is computed by the stem kernel: only the pooled tensor is written
+    a.pool_y = (bf16_t*)pool_y;
+    a.pool_ho = (ho - 1) / 2 + 1;
+    a.pool_wo = (wo - 1) / 2 + 1;
+  }
+  O_CONV(spk_conv_launch(a, CONV_MODE_STEM, s, nullptr), "stem launch");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_stem7_eval: kernel failed");
+  return SPK_OK;
+}
+
+// What the launchers of the eval kernels above would choose for a problem (host only, no GPU): include/sykepic_hip.h
+extern "C" int spk_op_mbconv_eval_geometry(int kind, int a, int b, int c, int d, int out[8]) {
+  if (!out) return ofail(SPK_ERR_ARG, "op_mbconv_eval_geometry: bad arguments");
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  switch (kind) {
+    case 0: {   // squeeze-excitation gates: a = n, b = chunks, c = channels, d = hidden units
+      if (a < 1 || b < 1 || c < 8 || c % 8 || d < 1) return ofail(SPK_ERR_ARG, "op_mbconv_eval_geometry: bad arguments");
+      const int ipb = spk_se_ipb();
+      out[0] = spk_se_fc1_ch(b);                               // CH instantiation of se_fc1 (0: the run-time loop)
+      out[1] = out[0] ? 0 : (b + 3) / 4 * 4 - b;               // run-time loop: clamped surplus loads of its last step
+      out[2] = a - (a - 1) / ipb * ipb;                        // images of the last block (nim)
+      out[3] = (d + 3) / 4 * 4 - d;                            // hidden units the last fc1 block row leaves out
+      out[4] = (d * ipb + spk_se_fc2_stage() - 1) / spk_se_fc2_stage();   // staging passes of se_fc2
+      out[5] = (c + 255) / 256;                                // channel tiles of se_fc2 (blockIdx.y)
+      out[6] = c - (out[5] - 1) * 256;                         // channels of the last one
+      out[7] = (a + ipb - 1) / ipb;                            // image blocks
+      return SPK_OK;
+    }
+    case 1: {   // se_scale: a = n, b = hw, c = channels
+      if (a < 1 || b < 1 || c < 8 || c % 8) return ofail(SPK_ERR_ARG, "op_mbconv_eval_geometry: bad arguments");
+      const size_t per_img = (size_t)b * (c / 8);
+      out[0] = spk_se_scale_grid(a, per_img);
+      out[1] = (int)((per_img + 255) / 256);                   // blocks that would cover an image once
+      return SPK_OK;
+    }
+    case 2: {   // 3x3 stem: a = ho, b = wo, c = cout
+      if (a < 1 || b < 1 || c < 8 || c % 8) return ofail(SPK_ERR_ARG, "op_mbconv_eval_geometry: bad arguments");
+      out[0] = spk_stem3_gt(c);
+      return SPK_OK;
+    }
+    case 3: {   // padded / gated 1x1 conv: a = tile config, b = flavour, c = GEMM couts, d = split weights + 2 x gated
+      if (a < 0 || a > 6 || b < 0 || b > 6 || c < 64 || c % 64 || d < 0 || d > 3)
+        return ofail(SPK_ERR_ARG, "op_mbconv_eval_geometry: bad arguments");
+      out[0] = spk_conv_narrow_cfg(a, c, d & 1);
+      out[1] = spk_conv_padc_flavour(b, (d & 2) != 0);         // DMA template argument, or -3: not instantiated
+      return SPK_OK;
+    }
+  }
+  return ofail(SPK_ERR_ARG, "op_mbconv_eval_geometry: kind 0 ... 3");
+}
+
 // ---- the classifier head, the loss and the pooling layers (head.hip, pointwise.hip, train_kernels.hip), one layer at a
 // time through the launchers model.hip and train.hip call.  Arguments are checked before any HIP call. ----
 namespace {

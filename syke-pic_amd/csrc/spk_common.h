@@ -174,6 +174,11 @@ int spk_conv_launch(const ConvArgs& a, int mode, hipStream_t s, int* m_tiles_out
 void spk_conv_set_pin(int cfg, int dma, int wgrad_nbuf);
 int spk_conv_pinned_wgrad_nbuf();
 int spk_conv_m_tiles(int M, int Cout, int mode);
+// the tile config launch_with really runs for `cfg`: 256x256 -> 256x128 (Cout % 256, split weights) -> 128x64 (Cout % 128)
+int spk_conv_narrow_cfg(int cfg, int Cout, int splitw);
+// main-loop flavour `dma` on the padded-channel (cin_s / cout_s) or gated (spk_set_gate) fp16 path: the DMA template
+// argument of the instantiation that runs it (0, 2 or 4), or -3 when there is none
+int spk_conv_padc_flavour(int dma, bool gated);
 int spk_conv_stem_launch(const ConvArgs& a, hipStream_t s, int* m_tiles_out);  // conv_stem.hip
 const char* spk_conv_last_config();
 
@@ -316,6 +321,15 @@ int spk_launch_bn_fold(const float* g, const float* b, const float* mean, const 
 int spk_launch_pack_padded(const float* w, bf16_t* out, int cout, int taps, int cin, int cout_p, int cin_p, int dt,
                            int splitw, hipStream_t s);
 int spk_launch_pack_tapmajor(const float* w, float* out, int c, int rows, int c_p, hipStream_t s);
+// 3x3 RGB stem weights: master [cout][3][3][cin <= 3] fp32 (device) -> fp32 [9 taps][4][cout_p] (device), a host repack
+// that waits for `s` first (1.3k floats, once per load)
+int spk_pack_stem3(const float* w_dev, float* out_dev, int cout, int cin, int cout_p, hipStream_t s);
+// what the launchers of effnet.hip choose (host arithmetic; the launchers call these themselves):
+int spk_stem3_gt(int c);                          // GT of stem3x3_kernel: c / 8 when instantiated (4, 5, 6), else 0 = run-time
+int spk_se_fc1_ch(int chunks);                    // CH of se_fc1_kernel: 1, 2, 3, 4, 8, or 0 = the run-time loop
+int spk_se_ipb();                                 // images per block of se_fc1 / se_fc2
+int spk_se_fc2_stage();                           // hid values se_fc2 stages per pass of its loading loop
+int spk_se_scale_grid(int n, size_t per_img);     // blockIdx.x extent of se_scale_kernel (capped)
 int spk_launch_stem3x3(const bf16_t* x, const float* w, const float* scale, const float* bias, bf16_t* y, int n, int h,
                        int wid, int wstride, int ho, int wo, int c, int c_p, int act, int dt, hipStream_t s);
 int spk_dw_chunks(int n, int hw, int c_p);

@@ -124,6 +124,11 @@ SYMBOLS = {
     "spk_op_se_train_backward": (C.c_int, [_P] * 16 + [C.c_int] * 6 + [_P]),
     "spk_op_stem3_train": (C.c_int, [_P] * 5 + [C.c_int] * 6 + [_P]),
     "spk_op_mbconv_geometry": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)]),
+    "spk_op_conv1x1_padded": (C.c_int, [_P] * 7 + [C.c_int] * 7 + [_P]),
+    "spk_op_se_eval": (C.c_int, [_P, _P, C.c_int] + [_P] * 7 + [C.c_int] * 5 + [_P]),
+    "spk_op_stem3_eval": (C.c_int, [_P] * 5 + [C.c_int] * 5 + [_P]),
+    "spk_op_stem7_eval": (C.c_int, [_P] * 6 + [C.c_int] * 4 + [_P]),
+    "spk_op_mbconv_eval_geometry": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)]),
     "spk_op_linear": (C.c_int, [_P] * 4 + [C.c_int] * 3 + [_P]),
     "spk_op_linear_backward": (C.c_int, [_P] * 6 + [C.c_int] * 4 + [_P]),
     "spk_op_softmax": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, _P]),

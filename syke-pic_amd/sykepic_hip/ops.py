@@ -36,11 +36,11 @@ def _is_stem(cin, cout, k, stride, pad):
     return cin <= 4 and k == 7 and stride == 2 and pad == 3 and cout == 64
 
 
-def _stem_input(x):
+def _stem_input(x, dtype=torch.bfloat16):
     """[N,C<=4,H,W] -> NHWC with 4 stored channels and an even width (the layout spk_launch_to_nhwc4 produces)."""
     n, c, h, w = x.shape
     wp = (w + 1) & ~1
-    out = torch.zeros((n, h, wp, 4), dtype=torch.bfloat16, device=x.device)
+    out = torch.zeros((n, h, wp, 4), dtype=dtype, device=x.device)
     out[:, :, :w, :c] = x.permute(0, 2, 3, 1)
     return out
 
@@ -518,6 +518,138 @@ def stem3_train(x4, weight, c, dy=None, w_in=None):
         lib.check(so.spk_op_stem3_train(_p(_bf16c(x4)), _p(_f32c(weight)), _p(_bf16c(dy)) if dy is not None else None,
                                         _p(y), _p(dw), n, h, w, cin, cout, int(c), _stream(dev)))
     return {"y": y, "dw": dw}
+
+
+# ---- the MBConv eval kernels and the eval stems (csrc/conv_igemm.hip PADC / GATE, effnet.hip, conv_stem.hip), one layer
+# at a time.  Every output is NaN-poisoned and allocated with a sentinel tail of at least one more pixel row, which the
+# launches must leave alone (AssertionError otherwise).
+SENTINEL = -1234.0
+
+
+def _guarded(shape, dtype, dev, tail):
+    """(flat buffer of numel + tail elements, view of its first numel elements as `shape`): NaN, then the sentinel."""
+    numel = 1
+    for d in shape:
+        numel *= int(d)
+    buf = torch.full((numel + int(tail),), float("nan"), dtype=dtype, device=dev)
+    buf[numel:] = SENTINEL
+    return buf, buf[:numel].view(*shape)
+
+
+def _check_tail(buf, numel, what):
+    tail = buf[numel:]
+    if not bool((tail == SENTINEL).all()):
+        bad = int((tail != SENTINEL).nonzero()[0])
+        raise AssertionError(f"{what}: element {bad} behind the end of the output was written ({float(tail[bad])})")
+
+
+def mbconv_eval_geometry(kind, a=0, b=0, c=0, d=0):
+    """spk_op_mbconv_eval_geometry: what the launchers of the eval kernels below choose (no GPU needed).  Returns the 8
+    integers (see include/sykepic_hip.h)."""
+    so = lib.load()
+    out = (C.c_int * 8)()
+    lib.check(so.spk_op_mbconv_eval_geometry(int(kind), int(a), int(b), int(c), int(d), out))
+    return list(out)
+
+
+def conv1x1_padded(x, weight, bn_scale, bn_bias, act=0, res=None, gate=None, split=False):
+    """Eval-path 1x1 conv + folded BN (+ shortcut) + activation on channel counts that are multiples of 8 only
+    (spk_op_conv1x1_padded: spk_launch_pack_padded + the implicit GEMM with cin_s / cout_s).  x [N,Cin,H,W] float16,
+    weight [Cout,Cin], res [N,Cout,H,W] float16 or None, gate [N,Cin] float32 or None (the squeeze-excitation gates,
+    multiplied into the operand: spk_set_gate).  act: 0 none, 1 ReLU, 2 SiLU, 3 Hardswish.  Honours `pinned_conv`.
+    Returns [N,Cout,H,W] float16."""
+    so = lib.load()
+    dev = x.device
+    n, cin, h, w = x.shape
+    cout = weight.shape[0]
+    xh = x.half().permute(0, 2, 3, 1).contiguous()
+    rh = res.half().permute(0, 2, 3, 1).contiguous() if res is not None else None
+    gh = gate.float().contiguous() if gate is not None else None
+    # (a pixel row, and no less than the 64-channel GEMM tile that a missing column check would store)
+    buf, y = _guarded((n, h, w, cout), torch.float16, dev, max(w * cout, 64))
+    wk = weight.float().reshape(cout, cin).contiguous()
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_conv1x1_padded(_p(xh), _p(wk), _p(bn_scale.float().contiguous()),
+                                           _p(bn_bias.float().contiguous()), _p(rh), _p(gh), _p(buf), n, h, w, cin, cout,
+                                           int(act), int(bool(split)), _stream(dev)))
+    _check_tail(buf, y.numel(), "conv1x1_padded y")
+    return y.permute(0, 3, 1, 2)
+
+
+def se_eval(partial, w1, b1, w2, b2, hw, gate_kind=0, x=None):
+    """Eval squeeze-excitation (spk_op_se_eval: spk_launch_se) from the pool partials [N,chunks,C] float32 (sums over
+    the hw pixels).  w1 [S,C], b1 [S], w2 [C,S], b2 [C] float32; x [N,hw,C] float16 or None (the gates only).
+    Returns dict(hid [N,S], scale [N,C] float32, y [N,hw,C] float16 or None)."""
+    so = lib.load()
+    dev = partial.device
+    n, chunks, c = partial.shape
+    sq = w1.shape[0]
+    # one buffer: the gates, the hidden vector directly behind them (the layout of the model's scratch), the sentinel
+    buf = torch.full((n * c + n * sq + max(c, sq),), float("nan"), dtype=torch.float32, device=dev)
+    buf[n * c + n * sq:] = SENTINEL
+    scale, hid = buf[:n * c].view(n, c), buf[n * c:n * c + n * sq].view(n, sq)
+    ybuf = y = xh = None
+    if x is not None:
+        xh = x.half().contiguous()
+        assert xh.shape == (n, hw, c)
+        ybuf, y = _guarded((n, hw, c), torch.float16, dev, max(c, 8))
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_se_eval(_p(xh), _p(_f32c(partial)), chunks, _p(_f32c(w1)), _p(_f32c(b1)), _p(_f32c(w2)),
+                                    _p(_f32c(b2)), _p(hid), _p(scale), _p(ybuf), n, int(hw), c, sq, int(gate_kind),
+                                    _stream(dev)))
+    _check_tail(buf, n * c + n * sq, "se_eval scale / hid")
+    if y is not None:
+        _check_tail(ybuf, y.numel(), "se_eval y")
+    return {"hid": hid, "scale": scale, "y": y}
+
+
+def _stem_eval_input(x):
+    """Images [N,3,H,W] on the k / 255 grid in [0, 1] -> the fp16 NHWC4, even-width, x 255 tensor the model builds."""
+    k = torch.round(x.double() * 255.0)
+    assert float((x.double() * 255.0 - k).abs().max()) < 1e-3 and float(k.min()) >= 0 and float(k.max()) <= 255, \
+        "pixel values must be k / 255"
+    return _stem_input(k.to(torch.float16), torch.float16)
+
+
+def stem3_eval(x, weight, bn_scale, bn_bias, act=2):
+    """The 3x3/2 RGB stem of the eval path (spk_op_stem3_eval: pack_stem3 + spk_launch_stem3x3).  x [N,3,H,W] on the
+    k / 255 grid, weight [Cout,3,3,3] (OIHW), ordinary folded-BN scale / shift (1 / 255 is folded into the scale inside,
+    where the model does it).  Returns [N,Cout,Ho,Wo] float16."""
+    so = lib.load()
+    dev = x.device
+    n, _, h, w = x.shape
+    cout = weight.shape[0]
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    xh = _stem_eval_input(x)
+    wk = weight.float().permute(0, 2, 3, 1).contiguous()
+    # (a pixel row, and no less than the four outputs a thread of the kernel owns)
+    buf, y = _guarded((n, ho, wo, cout), torch.float16, dev, max(wo, 4) * cout)
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_stem3_eval(_p(xh), _p(wk), _p(bn_scale.float().contiguous()), _p(bn_bias.float().contiguous()),
+                                       _p(buf), n, h, w, cout, int(act), _stream(dev)))
+    _check_tail(buf, y.numel(), "stem3_eval y")
+    return y.permute(0, 3, 1, 2)
+
+
+def stem7_eval(x, weight, bn_scale, bn_bias, split=False, pool=False):
+    """The 7x7/2 ResNet stem + ReLU of the eval path (spk_op_stem7_eval: spk_launch_pack_weights(CONV_MODE_STEM) +
+    spk_conv_launch).  x [N,3,H,W] on the k / 255 grid, weight [64,3,7,7].  pool: the kernel variant with the fused 3x3/2
+    max-pool, which writes only the pooled tensor.  Returns [N,64,Ho,Wo] (pool: [N,64,(Ho-1)//2+1,(Wo-1)//2+1]) float16."""
+    so = lib.load()
+    dev = x.device
+    n, _, h, w = x.shape
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    if pool:
+        ho, wo = (ho - 1) // 2 + 1, (wo - 1) // 2 + 1
+    xh = _stem_eval_input(x)
+    wk = weight.float().permute(0, 2, 3, 1).contiguous()
+    buf, y = _guarded((n, ho, wo, 64), torch.float16, dev, wo * 64)
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_stem7_eval(_p(xh), _p(wk), _p(bn_scale.float().contiguous()), _p(bn_bias.float().contiguous()),
+                                       None if pool else _p(buf), _p(buf) if pool else None, n, h, w, int(bool(split)),
+                                       _stream(dev)))
+    _check_tail(buf, y.numel(), "stem7_eval y")
+    return y.permute(0, 3, 1, 2)
 
 
 # ---- the classifier head, the loss and the pooling layers (csrc/head.hip, pointwise.hip, train_kernels.hip) ----

@@ -62,6 +62,38 @@ def test_error_reporting_without_gpu_or_bad_args():
         ("spk_op_gavgpool", ARG, (p, p, 1, 4, 12, 0, None)),
         ("spk_op_gavgpool_backward", ARG, (None, p, 1, 4, 8, None)),
         ("spk_op_gavgpool_backward", ARG, (p, p, 1, 4, 12, None)),
+        # the MBConv eval / eval stem hooks: (x, w, scale, bias, res, gate, y, n, h, w, cin, cout, act, split, stream)
+        ("spk_op_conv1x1_padded", ARG, (None, p, p, p, None, None, p, 1, 2, 2, 8, 8, 0, 0, None)),
+        ("spk_op_conv1x1_padded", ARG, (p, None, p, p, None, None, p, 1, 2, 2, 8, 8, 0, 0, None)),
+        ("spk_op_conv1x1_padded", ARG, (p, p, p, p, None, None, None, 1, 2, 2, 8, 8, 0, 0, None)),
+        ("spk_op_conv1x1_padded", ARG, (p, p, p, p, None, None, p, 1, 2, 2, 12, 8, 0, 0, None)),     # cin % 8
+        ("spk_op_conv1x1_padded", ARG, (p, p, p, p, None, None, p, 1, 2, 2, 8, 12, 0, 0, None)),     # cout % 8
+        ("spk_op_conv1x1_padded", ARG, (p, p, p, p, None, None, p, 0, 2, 2, 8, 8, 0, 0, None)),      # n < 1
+        ("spk_op_conv1x1_padded", ARG, (p, p, p, p, None, None, p, 1, 2, 2, 8, 8, 4, 0, None)),      # act
+        # (x, partial, chunks, w1, b1, w2, b2, hid, scale, y, n, hw, c, sq, gate_kind, stream)
+        ("spk_op_se_eval", ARG, (None, None, 1, p, p, p, p, p, p, None, 1, 4, 8, 2, 0, None)),
+        ("spk_op_se_eval", ARG, (None, p, 1, p, p, p, p, None, p, None, 1, 4, 8, 2, 0, None)),
+        ("spk_op_se_eval", ARG, (None, p, 1, p, p, p, p, p, p, p, 1, 4, 8, 2, 0, None)),             # y without x
+        ("spk_op_se_eval", ARG, (None, p, 1, p, p, p, p, p, p, None, 1, 4, 12, 2, 0, None)),         # c % 8
+        ("spk_op_se_eval", ARG, (None, p, 1, p, p, p, p, p, p, None, 0, 4, 8, 2, 0, None)),          # n < 1
+        ("spk_op_se_eval", ARG, (None, p, 0, p, p, p, p, p, p, None, 1, 4, 8, 2, 0, None)),          # chunks < 1
+        ("spk_op_se_eval", ARG, (None, p, 1, p, p, p, p, p, p, None, 1, 4, 8, 2, 2, None)),          # gate_kind
+        ("spk_op_se_eval", ARG, (None, p, 1, p, p, p, p, p, p, None, 1, 4, 8, 2, 0, None)),          # hid not behind scale
+        # (x, w, scale, bias, y, n, h, w, cout, act, stream)
+        ("spk_op_stem3_eval", ARG, (None, p, p, p, p, 1, 4, 4, 8, 0, None)),
+        ("spk_op_stem3_eval", ARG, (p, p, p, p, None, 1, 4, 4, 8, 0, None)),
+        ("spk_op_stem3_eval", ARG, (p, p, p, p, p, 1, 4, 4, 12, 0, None)),                           # cout % 8
+        ("spk_op_stem3_eval", ARG, (p, p, p, p, p, 0, 4, 4, 8, 0, None)),                            # n < 1
+        ("spk_op_stem3_eval", ARG, (p, p, p, p, p, 1, 4, 4, 8, 7, None)),                            # act
+        ("spk_op_stem3_eval", UNSUPPORTED, (p, p, p, p, p, 1, 4, 4, 264, 0, None)),                  # cout > 256
+        # (x, w, scale, bias, y, pool_y, n, h, w, split, stream)
+        ("spk_op_stem7_eval", ARG, (None, p, p, p, p, None, 1, 8, 8, 0, None)),
+        ("spk_op_stem7_eval", ARG, (p, p, p, None, p, None, 1, 8, 8, 0, None)),
+        ("spk_op_stem7_eval", ARG, (p, p, p, p, None, None, 1, 8, 8, 0, None)),                      # neither output
+        ("spk_op_stem7_eval", ARG, (p, p, p, p, p, None, 0, 8, 8, 0, None)),                         # n < 1
+        ("spk_op_mbconv_eval_geometry", ARG, (0, 1, 1, 12, 2, ctypes.cast(buf, ctypes.POINTER(ctypes.c_int)))),   # c % 8
+        ("spk_op_mbconv_eval_geometry", ARG, (9, 1, 1, 8, 2, ctypes.cast(buf, ctypes.POINTER(ctypes.c_int)))),    # kind
+        ("spk_op_mbconv_eval_geometry", ARG, (3, 7, 0, 64, 0, ctypes.cast(buf, ctypes.POINTER(ctypes.c_int)))),   # tile config
     ]
     for name, want, args in bad:
         rc = getattr(so, name)(*args)

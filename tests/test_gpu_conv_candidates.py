@@ -26,8 +26,9 @@ exact).  Three things are asserted:
    its flavour is not instantiated for its (narrowed) tile - `instantiated` below mirrors the compile-time conditions
    of launch_hybrid / launch_bk32 - so no candidate the tuner can time for a problem is unsupported.
 
-Not covered (next gap): the padded-channel fp16 flavours of the EfficientNet path (`cin_s` / `cout_s`), which no
-single-operator hook reaches, and the dedicated stem kernel (conv_stem.hip), which has no tile choice.
+The padded-channel fp16 flavours of the EfficientNet path (`cin_s` / `cout_s`, with and without the squeeze-excitation
+gates in the operand) run under the same candidate grid in tests/test_gpu_mbconv_eval_ops.py, which also holds the
+operator tests of the dedicated stem kernel (conv_stem.hip; no tile choice) in its fp16 eval forms.
 """
 
 import collections
