@@ -241,6 +241,16 @@ int spk_eval_step(spk_model* m, const void* x_dev, int n, int h, int w, int layo
 int spk_train_forward_backward(spk_model* m, const void* x_dev, int n, int h, int w, int layout,
                                int dtype, const int64_t* y_dev, float* stats_dev,
                                float* logits_dev);
+/* The same step with the Mixup / CutMix criterion on a batch mixed by spk_mix_batch (not in the reference, whose loop
+ * is train.py:239-242): loss = lam CE(out, ya) + (1 - lam) CE(out, yb), CE the model's loss (spk_model_set_loss: its
+ * weights and smoothing; none and 0 for the default one), each term normalised by its own sum of weights, 1 - lam
+ * formed in float32.  stats[0] += n * loss; stats[1] and the per-class counters (kept exactly when the loss keeps
+ * them) count against the dominant label, ya when lam >= 0.5, else yb.  yb_dev == NULL or lam == 1:
+ * spk_train_forward_backward on ya, bit for bit, whatever the loss.  Checked before any HIP call: a null m / x_dev /
+ * ya_dev / stats_dev, n < 1, lam outside [0, 1] or not finite are SPK_ERR_ARG. */
+int spk_train_forward_backward_pair(spk_model* m, const void* x_dev, int n, int h, int w, int layout, int dtype,
+                                    const int64_t* ya_dev, const int64_t* yb_dev, float lam,
+                                    float* stats_dev, float* logits_dev);
 /* optimizer.step() — sykepic/train/train.py:243 */
 int spk_optim_step(spk_model* m, const spk_optim_desc* opt);
 
@@ -579,6 +589,15 @@ int spk_op_cross_entropy(const float* z_dev, const int64_t* labels_dev, int n, i
  * outside [0, 1]: SPK_ERR_ARG.  Equal inputs give equal bits. */
 int spk_op_cross_entropy_ex(const float* z_dev, const int64_t* labels_dev, int n, int c, const float* w_dev,
                             float label_smoothing, float* stats_dev, int* counts_dev, float* dz_dev, void* hip_stream);
+/* The Mixup / CutMix criterion of that loss on two label vectors, the kernel spk_train_forward_backward_pair runs:
+ * L = lam CE(z, ya; w, eps) + (1 - lam) CE(z, yb; w, eps), each CE normalised by its own sum of weights, 1 - lam formed
+ * in float32.  stats[0] += n * L; dz [n][c] (may be NULL) = lam dCE_a/dz + (1 - lam) dCE_b/dz; stats[1] and counts_dev
+ * (may be NULL) count against the dominant label: ya when lam >= 0.5, else yb.  yb_dev == NULL or lam == 1: the bits of
+ * spk_op_cross_entropy_ex on ya.  lam or label_smoothing outside [0, 1] or not finite: SPK_ERR_ARG.  Equal inputs give
+ * equal bits. */
+int spk_op_cross_entropy_pair(const float* z_dev, const int64_t* ya_dev, const int64_t* yb_dev, float lam, int n, int c,
+                              const float* w_dev, float label_smoothing, float* stats_dev, int* counts_dev, float* dz_dev,
+                              void* hip_stream);
 /* MaxPool2d(k, stride, pad): x [n,h,w,c] -> y [n,ho,wo,c].  idx == NULL: the eval path's kernel, dtype 0 bf16 / 1 fp16.
  * idx [n,ho,wo,c] bytes: the training step's kernel (bf16 only), which also saves the tap r * k + s of each maximum (the
  * first in that order among equal values).  c % 8 != 0: SPK_ERR_ARG; k * k > 255 or pad > k / 2: SPK_ERR_UNSUPPORTED. */
@@ -636,6 +655,19 @@ typedef struct {
 int spk_augment_batch(const unsigned char* in_dev, unsigned char* out_dev, unsigned char* tmp_dev, int n, int h,
                       int w, int c, const spk_aug_op* ops_dev, int n_ops, const unsigned char* border_dev,
                       void* stream);
+
+/* Mixup / CutMix (not in the reference; torchvision's reference recipe): every image of a batch mixed with the image
+ * `shift` places before it, out[i] = in[i] outside the box [y1,y2) x [x1,x2) and ca * in[i] + cb * in[(i - shift) mod n]
+ * inside it; one box and one coefficient pair for the batch.  Mixup is the full-image box with (ca, cb) =
+ * (lam, 1 - lam); CutMix is (0, 1), which copies the partner's elements bit for bit, without arithmetic.  Each product
+ * is rounded to float32, then the sum; float32 batches store that value, uint8 batches store it rounded to the nearest
+ * integer (ties to even) and clamped to 0..255.  Batches: SPK_LAYOUT_NHWC / SPK_DTYPE_U8 [n,h,w,c] or SPK_LAYOUT_NCHW /
+ * SPK_DTYPE_F32 [n,c,h,w], c 1 or 3, any n, h, w >= 1 and any pointer alignment the element type allows.  Out of
+ * place: in_dev and out_dev must not overlap.  An empty box is a plain copy.  Checked before any HIP call, each
+ * SPK_ERR_ARG: a null pointer, n / h / w < 1, c not 1 or 3, another layout / dtype pair, shift outside [0, n), ca or cb
+ * not finite, a box outside the image or inverted, overlapping buffers.  Asynchronous on hip_stream. */
+int spk_mix_batch(const void* in_dev, void* out_dev, int n, int h, int w, int c, int layout, int dtype,
+                  int shift, float ca, float cb, int y1, int x1, int y2, int x2, void* hip_stream);
 
 /* --- prediction from probabilities and thresholds ---
  * row_prediction of sykepic/compute/prediction.py:49-71 for n rows at once:

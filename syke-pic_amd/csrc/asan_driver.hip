@@ -185,6 +185,17 @@ int main(int argc, char** argv) {
     EXPECT(spk_op_cross_entropy_ex(f, labels, 1, 4, nullptr, 1.5f, f, nullptr, nullptr, nullptr) == SPK_ERR_ARG);
     EXPECT(spk_op_cross_entropy_ex(f, labels, 1, 4, nullptr, NAN, f, nullptr, nullptr, nullptr) == SPK_ERR_ARG);
     EXPECT(spk_op_cross_entropy_ex(f, nullptr, 1, 4, f, 0.1f, f, nullptr, nullptr, nullptr) == SPK_ERR_ARG);
+    // ... and the Mixup / CutMix entry points: lam, the box, the shift, the coefficients, overlapping buffers
+    unsigned char img_a[2 * 4 * 4 * 3] = {0}, img_b[2 * 4 * 4 * 3] = {0};
+    EXPECT(spk_op_cross_entropy_pair(f, labels, labels, 1.5f, 1, 4, nullptr, 0.f, f, nullptr, nullptr, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_op_cross_entropy_pair(f, labels, nullptr, NAN, 1, 4, nullptr, 0.f, f, nullptr, nullptr, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_op_cross_entropy_pair(f, nullptr, labels, 0.5f, 1, 4, nullptr, 0.f, f, nullptr, nullptr, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_train_forward_backward_pair(nullptr, f, 1, 4, 4, SPK_LAYOUT_NCHW, SPK_DTYPE_F32, labels, labels, 0.5f, f, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_mix_batch(img_a, img_b, 2, 4, 4, 3, SPK_LAYOUT_NHWC, SPK_DTYPE_U8, 2, 0.5f, 0.5f, 0, 0, 4, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_mix_batch(img_a, img_b, 2, 4, 4, 3, SPK_LAYOUT_NHWC, SPK_DTYPE_U8, 1, 0.5f, 0.5f, 0, 0, 5, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_mix_batch(img_a, img_b, 2, 4, 4, 3, SPK_LAYOUT_NHWC, SPK_DTYPE_U8, 1, NAN, 0.5f, 0, 0, 4, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_mix_batch(img_a, img_a + 8, 2, 4, 4, 3, SPK_LAYOUT_NHWC, SPK_DTYPE_U8, 1, 0.5f, 0.5f, 0, 0, 4, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_mix_batch(img_a, img_b, 2, 4, 4, 3, SPK_LAYOUT_NCHW, SPK_DTYPE_U8, 1, 0.5f, 0.5f, 0, 0, 4, 4, nullptr) == SPK_ERR_ARG);
   }
 
   // ---- a small bottleneck graph: stem, pool, 1x1 / 3x3 / 1x1 + shortcut, pool, head ----

@@ -323,6 +323,110 @@ __global__ __launch_bounds__(1024) void ce_ex_kernel(const float* __restrict__ z
   }
 }
 
+// The Mixup / CutMix criterion on two label vectors: L = lam CE(z, ya; w, eps) + (1 - lam) CE(z, yb; w, eps), each CE the
+// loss of ce_ex_kernel with its own W (W_a = sum_i w[ya_i], W_b = sum_i w[yb_i]), dz = lam dCE_a + (1 - lam) dCE_b.  The
+// same one block of a row per wave and the same fixed summation orders.  Per row the soft-max, lse and the smoothing sum
+// (term by term, w[j] (lse - z[j])) are computed once; the two row losses and the two gradients are then formed with
+// exactly the expressions of ce_ex_kernel, each with its own label and 1 / W, and only combined at the end:
+//   dz[i][j]  = lam g_a + (1 - lam) g_b,       stats[0] += lam (n CE_a) + (1 - lam) (n CE_b),    1 - lam formed in float32
+// so the extra roundings over ce_ex_kernel are the two products, 1 - lam and the sum (tests/test_gpu_loss_pair_ops.py);
+// no combined smoothing coefficient is formed.  stats[1] and the per-class counters go by the dominant label: ya when
+// lam >= 0.5, else yb.  The launcher sends lam == 1 (and yb == nullptr) to ce_ex_kernel itself.
+__global__ __launch_bounds__(1024) void ce_pair_kernel(const float* __restrict__ z, const int64_t* __restrict__ ya,
+                                                      const int64_t* __restrict__ yb, float lam, int n, int c,
+                                                      const float* __restrict__ w, float eps, float* __restrict__ stats,
+                                                      int* __restrict__ counts, float* __restrict__ dz) {
+  constexpr int WAVES = 16;
+  __shared__ float s_wa[WAVES];
+  __shared__ float s_wb[WAVES];
+  __shared__ float s_la[WAVES];
+  __shared__ float s_lb[WAVES];
+  __shared__ float s_corr[WAVES];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  // W_a, W_b: each as ce_ex_kernel forms W; every thread ends with the same bits
+  float Wa = (float)n, Wb = (float)n, Sw = (float)c;
+  if (w) {
+    float pa = 0.f, pb = 0.f;
+    for (int i = threadIdx.x; i < n; i += WAVES * 64) { pa += w[(int)ya[i]]; pb += w[(int)yb[i]]; }
+    pa = wave_sum(pa);
+    pb = wave_sum(pb);
+    if (lane == 0) { s_wa[wave] = pa; s_wb[wave] = pb; }
+    __syncthreads();
+    Wa = Wb = 0.f;
+    for (int q = 0; q < WAVES; ++q) { Wa += s_wa[q]; Wb += s_wb[q]; }
+    float sp = 0.f;
+    for (int j = lane; j < c; j += 64) sp += w[j];
+    Sw = wave_sum(sp);
+  }
+  const bool smooth = eps > 0.f;
+  const bool first = lam >= 0.5f;   // the dominant label
+  const float invWa = 1.0f / Wa, invWb = 1.0f / Wb;
+  const float a = 1.0f - eps, b = eps / (float)c;
+  const float cba = b * invWa, cbb = b * invWb;
+  const float lamb = 1.0f - lam;
+  float loss_a = 0.f, loss_b = 0.f, corr = 0.f;
+  for (int row = wave; row < n; row += WAVES) {
+    const float* zr = z + (size_t)row * c;
+    const int la = (int)ya[row], lb = (int)yb[row];
+    float mx = -INFINITY;
+    int arg = 0x7fffffff;
+    for (int j = lane; j < c; j += 64) {
+      const float v = zr[j];
+      if (v > mx) { mx = v; arg = j; }
+    }
+    // arg-max with torch's tie rule: lowest index among the maxima
+    for (int d = 32; d; d >>= 1) {
+      const float om = __shfl_xor(mx, d);
+      const int oa = __shfl_xor(arg, d);
+      if (om > mx || (om == mx && oa < arg)) { mx = om; arg = oa; }
+    }
+    float s = 0.f;
+    for (int j = lane; j < c; j += 64) s += expf(zr[j] - mx);
+    s = wave_sum(s);
+    const float lse = mx + logf(s);
+    float sm = 0.f;
+    if (smooth) {
+      for (int j = lane; j < c; j += 64) sm += (w ? w[j] : 1.f) * (lse - zr[j]);
+      sm = wave_sum(sm);
+    }
+    const float awa = a * (w ? w[la] : 1.f), awb = a * (w ? w[lb] : 1.f);
+    if (lane == 0) {
+      const int label = first ? la : lb;
+      const bool hit = arg == label;
+      loss_a += awa * (lse - zr[la]) + b * sm;
+      loss_b += awb * (lse - zr[lb]) + b * sm;
+      corr += hit ? 1.f : 0.f;
+      if (counts && (unsigned)label < (unsigned)c) {
+        atomicAdd(counts + 2 * label, 1);
+        if (hit) atomicAdd(counts + 2 * label + 1, 1);
+      }
+    }
+    if (dz) {
+      const float inv = 1.0f / s;
+      const float caa = awa * invWa, cab = awb * invWb;
+      for (int j = lane; j < c; j += 64) {
+        const float p = expf(zr[j] - mx) * inv;
+        float ga = caa * (p - (j == la ? 1.f : 0.f));
+        float gb = cab * (p - (j == lb ? 1.f : 0.f));
+        if (smooth) {
+          const float t = p * Sw - (w ? w[j] : 1.f);
+          ga += cba * t;
+          gb += cbb * t;
+        }
+        dz[(size_t)row * c + j] = lam * ga + lamb * gb;
+      }
+    }
+  }
+  if (lane == 0) { s_la[wave] = loss_a; s_lb[wave] = loss_b; s_corr[wave] = corr; }
+  __syncthreads();
+  if (threadIdx.x == 0) {   // fixed order
+    float ta = 0.f, tb = 0.f, tc = 0.f;
+    for (int q = 0; q < WAVES; ++q) { ta += s_la[q]; tb += s_lb[q]; tc += s_corr[q]; }
+    stats[0] += lam * (ta * invWa * (float)n) + lamb * (tb * invWb * (float)n);
+    stats[1] += tc;
+  }
+}
+
 // SURVEY.md §8f rank 2 — per-ROI prediction from probabilities and per-class
 // thresholds (reference sykepic/compute/prediction.py:49-71): the
 // highest-probability class that clears ITS OWN threshold wins (lowest index on
@@ -425,5 +529,14 @@ int spk_launch_ce(const float* z, const int64_t* y, int n, int c, float* stats, 
 int spk_launch_ce_ex(const float* z, const int64_t* y, int n, int c, const float* w, float label_smoothing, float* stats,
                      int* counts, float* dlogits, hipStream_t s) {
   hipLaunchKernelGGL(ce_ex_kernel, dim3(1), dim3(1024), 0, s, z, y, n, c, w, label_smoothing, stats, counts, dlogits);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// lam CE(z, ya) + (1 - lam) CE(z, yb); yb == nullptr or lam == 1: ce_ex_kernel on ya, bit for bit
+int spk_launch_ce_pair(const float* z, const int64_t* ya, const int64_t* yb, float lam, int n, int c, const float* w,
+                       float label_smoothing, float* stats, int* counts, float* dlogits, hipStream_t s) {
+  if (!yb || lam == 1.0f) return spk_launch_ce_ex(z, ya, n, c, w, label_smoothing, stats, counts, dlogits, s);
+  hipLaunchKernelGGL(ce_pair_kernel, dim3(1), dim3(1024), 0, s, z, ya, yb, lam, n, c, w, label_smoothing, stats, counts,
+                     dlogits);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

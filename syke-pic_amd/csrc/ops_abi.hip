@@ -5,7 +5,8 @@
 //   conv + train-mode BatchNorm forward   torch Conv2d + BatchNorm2d(+add)(+ReLU), sykepic/train/train.py:240
 //   BatchNorm / conv backward             what loss.backward() runs for that layer,  sykepic/train/train.py:242
 //   Linear / softmax / CrossEntropyLoss    spk_op_linear, spk_op_linear_backward, spk_op_softmax, spk_op_cross_entropy,
-//                                          spk_op_cross_entropy_ex (class weights, label smoothing, per-class counters)
+//                                          spk_op_cross_entropy_ex (class weights, label smoothing, per-class counters),
+//                                          spk_op_cross_entropy_pair (the Mixup / CutMix criterion on two label vectors)
 //   MaxPool2d / AdaptiveAvgPool2d(1)       spk_op_maxpool, spk_op_maxpool_backward, spk_op_gavgpool, spk_op_gavgpool_backward
 //                                          (head.hip, pointwise.hip, train_kernels.hip; exact integer and float64 references)
 // Scratch is allocated and freed inside the call (these are not on any hot path).
@@ -1028,6 +1029,20 @@ extern "C" int spk_op_cross_entropy_ex(const float* z, const int64_t* labels, in
   hipStream_t s = (hipStream_t)stream;
   O_TRY(spk_launch_ce_ex(z, labels, n, c, w, label_smoothing, stats, counts, dz, s), "cross-entropy");
   if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_cross_entropy_ex: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_cross_entropy_pair(const float* z, const int64_t* ya, const int64_t* yb, float lam, int n, int c,
+                                         const float* w, float label_smoothing, float* stats, int* counts, float* dz,
+                                         void* stream) {
+  if (!z || !ya || !stats || n < 1 || c < 1) return ofail(SPK_ERR_ARG, "op_cross_entropy_pair: bad arguments");
+  if (!(lam >= 0.f && lam <= 1.f)) return ofail(SPK_ERR_ARG, "op_cross_entropy_pair: lam must be in [0, 1]");
+  if (!(label_smoothing >= 0.f && label_smoothing <= 1.f))
+    return ofail(SPK_ERR_ARG, "op_cross_entropy_pair: label_smoothing must be in [0, 1]");
+  if (!below_2g(n, c)) return ofail(SPK_ERR_UNSUPPORTED, "op_cross_entropy_pair: a tensor of 2^31 elements or more");
+  hipStream_t s = (hipStream_t)stream;
+  O_TRY(spk_launch_ce_pair(z, ya, yb, lam, n, c, w, label_smoothing, stats, counts, dz, s), "cross-entropy");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_cross_entropy_pair: kernel failed");
   return SPK_OK;
 }
 

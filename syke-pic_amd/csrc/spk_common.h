@@ -384,6 +384,10 @@ int spk_launch_ce(const float* z, const int64_t* y, int n, int c, float* stats, 
 // gradient; counts [c][2] int32 (may be null) += per class (rows seen, rows correct)
 int spk_launch_ce_ex(const float* z, const int64_t* y, int n, int c, const float* w, float label_smoothing, float* stats,
                      int* counts, float* dlogits, hipStream_t s);
+// the Mixup / CutMix criterion lam CE(z, ya) + (1 - lam) CE(z, yb) of that loss, statistics by the dominant label
+// (ya when lam >= 0.5); yb == nullptr or lam == 1 launches the kernel of spk_launch_ce_ex on ya
+int spk_launch_ce_pair(const float* z, const int64_t* ya, const int64_t* yb, float lam, int n, int c, const float* w,
+                       float label_smoothing, float* stats, int* counts, float* dlogits, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // Training kernels (train_kernels.hip, conv_wgrad.hip)

@@ -977,8 +977,10 @@ static StepCtx step_begin(spk_model* m, int n, int w) {
   return c;
 }
 
-extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, int h, int w, int layout,
-                                          int dtype, const int64_t* y, float* stats, float* logits_out) {
+// The training step of both entry points.  y2 == nullptr: the loss on y, as ever; else the Mixup / CutMix criterion
+// lam CE(y) + (1 - lam) CE(y2) - the loss launch is all that differs.
+static int train_step(spk_model* m, const void* x, int n, int h, int w, int layout, int dtype, const int64_t* y,
+                      const int64_t* y2, float lam, float* stats, float* logits_out) {
   if (!m || !x || !y || !stats || n < 1) return tfail(SPK_ERR_ARG, "train step: bad arguments");
   if (dtype != SPK_DTYPE_F32 && dtype != SPK_DTYPE_U8) return tfail(SPK_ERR_ARG, "train step: dtype must be f32 or u8");
   HIP_TRY(hipSetDevice(m->device));
@@ -1047,7 +1049,10 @@ extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, in
 
   // ------------------------- loss + dlogits -------------------------
   const float* logits = (const float*)m->T(last);
-  if (m->loss_ex())
+  if (y2)   // the model's weights and smoothing (none and 0 for the default loss); counters when they are kept
+    K_TRY(spk_launch_ce_pair(logits, y, y2, lam, n, m->num_classes, m->loss_w, m->loss_eps, stats, m->class_counts,
+                             (float*)t->G(last), s), "cross-entropy");
+  else if (m->loss_ex())
     K_TRY(spk_launch_ce_ex(logits, y, n, m->num_classes, m->loss_w, m->loss_eps, stats, m->class_counts,
                            (float*)t->G(last), s), "cross-entropy");
   else
@@ -1128,6 +1133,20 @@ extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, in
     }
   }
   return SPK_OK;
+}
+
+extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, int h, int w, int layout,
+                                          int dtype, const int64_t* y, float* stats, float* logits_out) {
+  return train_step(m, x, n, h, w, layout, dtype, y, nullptr, 1.f, stats, logits_out);
+}
+
+extern "C" int spk_train_forward_backward_pair(spk_model* m, const void* x, int n, int h, int w, int layout, int dtype,
+                                               const int64_t* ya, const int64_t* yb, float lam, float* stats,
+                                               float* logits_out) {
+  if (!m || !x || !ya || !stats || n < 1) return tfail(SPK_ERR_ARG, "train_forward_backward_pair: bad arguments");
+  if (!(lam >= 0.f && lam <= 1.f)) return tfail(SPK_ERR_ARG, "train_forward_backward_pair: lam must be in [0, 1]");
+  // one label vector, or all the weight on the first: the step of spk_train_forward_backward, plain kernel included
+  return train_step(m, x, n, h, w, layout, dtype, ya, lam == 1.f ? nullptr : yb, lam, stats, logits_out);
 }
 
 // Makes the model's stream wait for whatever the last training step left running on the side stream (the deferred tail

@@ -55,6 +55,35 @@ def _checkpoint_on(s):
     return v
 
 
+def _alpha(key):
+    """``mixup_alpha`` / ``cutmix_alpha``: the Beta(alpha, alpha) parameter of the mix, 0 (or empty) = off."""
+    def parse(s):
+        v = float(s) if s.strip() else 0.0
+        if not (v >= 0.0 and v != float("inf")):
+            raise ValueError(f"{key} must be a finite number >= 0.0. Got: {v}")
+        return v
+    return parse
+
+
+def _probability(key, default):
+    def parse(s):
+        v = float(s) if s.strip() else default
+        if not 0.0 <= v <= 1.0:
+            raise ValueError(f"{key} must be between 0.0 and 1.0. Got: {v}")
+        return v
+    return parse
+
+
+def get_batch_mix(config, seed=0):
+    """The `mix.BatchMix` of ``[train] mixup_alpha / cutmix_alpha / mix_prob / mix_switch_prob``, or None when both
+    alphas are 0 (the default): no object, no draw, the training step of a run without the keys."""
+    tr = Settings(config).train
+    if tr.mixup_alpha == 0.0 and tr.cutmix_alpha == 0.0:
+        return None
+    from .mix import BatchMix
+    return BatchMix(tr.mixup_alpha, tr.cutmix_alpha, tr.mix_prob, tr.mix_switch_prob, seed=seed)
+
+
 def _index_prob_pairs(s):
     """``dropout = 1,0.5;2,0.3`` -> [(1, 0.5), (2, 0.3)] (list index in the head, probability)."""
     return [(int(i), float(p)) for i, p in (pair.split(",") for pair in s.split(";"))] if s else []
@@ -88,6 +117,9 @@ KEYS = {
         # loss (loss.py) and which validation figure selects best_state.pth; the defaults are the reference's behaviour
         "label_smoothing": (_smoothing, "0"), "class_weights": (_class_weights, "none"),
         "checkpoint_on": (_checkpoint_on, "accuracy"),
+        # Mixup / CutMix of every training batch on the GPU (mix.py); both alphas 0: off, the run of a file without the keys
+        "mixup_alpha": (_alpha("mixup_alpha"), "0"), "cutmix_alpha": (_alpha("cutmix_alpha"), "0"),
+        "mix_prob": (_probability("mix_prob", 1.0), "1"), "mix_switch_prob": (_probability("mix_switch_prob", 0.5), "0.5"),
     },
     "lr_warmup": {
         "use": (_flag, REQUIRED), "factor_1": (float, REQUIRED), "factor_2": (float, REQUIRED), "step_1": (int, REQUIRED),

@@ -92,6 +92,8 @@ SYMBOLS = {
     "spk_eval_step": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "spk_train_forward_backward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                              _P, _P, _P]),
+    "spk_train_forward_backward_pair": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  _P, _P, C.c_float, _P, _P]),
     "spk_optim_step": (C.c_int, [_P, C.POINTER(OptimDesc)]),
     "spk_model_grad_buffer": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),
     "spk_model_set_grad_ready_callback": (C.c_int, [_P, _P, _P, _P, C.c_int]),
@@ -134,6 +136,7 @@ SYMBOLS = {
     "spk_op_softmax": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, _P]),
     "spk_op_cross_entropy": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "spk_op_cross_entropy_ex": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_float, _P, _P, _P, _P]),
+    "spk_op_cross_entropy_pair": (C.c_int, [_P, _P, _P, C.c_float, C.c_int, C.c_int, _P, C.c_float, _P, _P, _P, _P]),
     "spk_op_maxpool": (C.c_int, [_P] * 3 + [C.c_int] * 8 + [_P]),
     "spk_op_maxpool_backward": (C.c_int, [_P] * 3 + [C.c_int] * 8 + [_P]),
     "spk_op_gavgpool": (C.c_int, [_P, _P] + [C.c_int] * 4 + [_P]),
@@ -146,6 +149,7 @@ SYMBOLS = {
     "spk_preprocess_rois": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "spk_predict_rows": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_float, _P, _P, _P]),
     "spk_augment_batch": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
+    "spk_mix_batch": (C.c_int, [_P, _P] + [C.c_int] * 7 + [C.c_float, C.c_float] + [C.c_int] * 4 + [_P]),
     "spk_model_profile_infer": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.POINTER(LayerTime), C.c_int]),
     "spk_model_profile_train": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,

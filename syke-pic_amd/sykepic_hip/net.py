@@ -537,18 +537,26 @@ class HipNet:
                 C.c_void_p(logits.data_ptr()) if want_logits else None))
         return logits
 
-    def forward_backward(self, x, y, want_logits=False):
+    def forward_backward(self, x, y, want_logits=False, y2=None, lam=1.0):
         """zero_grad + train-mode forward + CrossEntropyLoss + backward
-        (reference sykepic/train/train.py:239-242) in one library call."""
+        (reference sykepic/train/train.py:239-242) in one library call.
+        y2, lam: the Mixup / CutMix criterion ``lam * CE(out, y) + (1 - lam) * CE(out, y2)`` on a batch mixed by
+        `mix.BatchMix` (spk_train_forward_backward_pair); accuracy and the per-class counters then count against the
+        dominant label (y when lam >= 0.5, else y2).  y2 None or lam == 1: the step on y alone, bit for bit."""
         self._ensure_init()
         x, n, h, w, layout, dtype = self._prep(x)
         y = y.to(self.device, dtype=torch.int64).contiguous()
+        if y2 is not None:
+            y2 = y2.to(self.device, dtype=torch.int64).contiguous()
+            if y2.numel() != y.numel():
+                raise ValueError(f"y2 has {y2.numel()} labels, y has {y.numel()}")
         logits = torch.empty((n, self.num_classes), dtype=torch.float32, device=self.device) if want_logits else None
         with torch.cuda.device(self.device):
             lib.check(self._lib.spk_model_set_stream(self._h, self._stream()))
             try:
-                lib.check(self._lib.spk_train_forward_backward(
+                lib.check(self._lib.spk_train_forward_backward_pair(
                     self._h, C.c_void_p(x.data_ptr()), n, h, w, layout, dtype, C.c_void_p(y.data_ptr()),
+                    C.c_void_p(y2.data_ptr()) if y2 is not None else None, float(lam),
                     C.c_void_p(self._stats_buf().data_ptr()),
                     C.c_void_p(logits.data_ptr()) if want_logits else None))
             except RuntimeError as e:

@@ -721,6 +721,52 @@ def cross_entropy_ex(z, labels, stats, weight=None, label_smoothing=0.0, counts=
                                              _p(_f32c(stats)), _p(counts), _p(_f32c(dz)), _stream(dev)))
 
 
+def cross_entropy_pair(z, ya, yb, lam, stats, weight=None, label_smoothing=0.0, counts=None, dz=None):
+    """spk_op_cross_entropy_pair: the Mixup / CutMix criterion lam * CE(z, ya) + (1 - lam) * CE(z, yb) of
+    CrossEntropyLoss(weight, label_smoothing).  Adds (n * loss, rows whose arg-max is the dominant label - ya when
+    lam >= 0.5, else yb) to stats [2] float32 and per class (rows, correct rows) of the dominant label to counts [c, 2]
+    int32 (None: no counters); writes dz [N,c] (the caller's buffer; None: no gradient).  yb None (or lam == 1): the bits
+    of `cross_entropy_ex` on ya."""
+    so = lib.load()
+    dev = z.device
+    n, c = z.shape
+    for y in (ya, yb):
+        assert y is None or (y.dtype == torch.int64 and y.is_contiguous() and y.is_cuda and y.numel() == n)
+    assert weight is None or weight.numel() == c
+    assert counts is None or (counts.dtype == torch.int32 and counts.is_contiguous() and counts.is_cuda
+                              and counts.numel() == 2 * c)
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_cross_entropy_pair(_p(_f32c(z)), _p(ya), _p(yb), float(lam), n, c, _p(_f32c(weight)),
+                                               float(label_smoothing), _p(_f32c(stats)), _p(counts), _p(_f32c(dz)),
+                                               _stream(dev)))
+
+
+def mix_batch(x, ca, cb, box, shift=1, out=None):
+    """spk_mix_batch: x mixed with itself rolled by `shift` images along the batch.  x: a contiguous device batch, uint8
+    [N,H,W,C] or float32 [N,C,H,W], C 1 or 3.  Inside box = (y1, x1, y2, x2) the result is ca * x[i] + cb * x[(i - shift)
+    % N] (each product and the sum rounded to float32; uint8 rounds that to nearest-even and clamps), outside it x[i];
+    (ca, cb) = (0, 1) copies the partner's pixels.  out: the caller's buffer of x's shape and dtype (it must not overlap
+    x), else a new tensor.  Returns out; the work is enqueued on the current stream."""
+    so = lib.load()
+    dev = x.device
+    assert x.is_cuda and x.is_contiguous() and x.dim() == 4 and x.dtype in (torch.uint8, torch.float32), \
+        "contiguous uint8 [N,H,W,C] or float32 [N,C,H,W] device batch expected"
+    if x.dtype == torch.uint8:
+        n, h, w, c = x.shape
+        layout, dtype = lib.LAYOUT_NHWC, lib.DTYPE_U8
+    else:
+        n, c, h, w = x.shape
+        layout, dtype = lib.LAYOUT_NCHW, lib.DTYPE_F32
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.is_cuda and out.is_contiguous() and out.shape == x.shape and out.dtype == x.dtype
+    y1, x1, y2, x2 = (int(v) for v in box)
+    with torch.cuda.device(dev):
+        lib.check(so.spk_mix_batch(_p(x), _p(out), n, h, w, c, layout, dtype, int(shift), float(ca), float(cb), y1, x1, y2,
+                                   x2, _stream(dev)))
+    return out
+
+
 def maxpool(x, k, stride, pad, want_idx=False):
     """MaxPool2d on x [N,H,W,C] bf16 / fp16 (spk_op_maxpool).  want_idx: the training kernel, which also returns the
     saved taps [N,Ho,Wo,C] uint8; else the eval kernel.  Returns (y, idx or None)."""

@@ -25,7 +25,7 @@ import torch
 
 from . import arch, data, schedule
 from . import loss as loss_mod
-from .config import Settings, get_network, get_transforms
+from .config import Settings, get_batch_mix, get_network, get_transforms
 from . import dp
 from .dp import GradSync
 from .optim import HipOptimizer
@@ -104,6 +104,9 @@ def main(args):
     loss_fn = loss_mod.CrossEntropyLoss(loss_mod.resolve_class_weights(tr.class_weights, classes, train_labels),
                                         tr.label_smoothing)
     checkpoint_on = tr.checkpoint_on
+    # Mixup / CutMix (mix.py): None unless `mixup_alpha` or `cutmix_alpha` is set; its own generator, seeded per rank by
+    # the rule of the Dropout seed below
+    batch_mix = get_batch_mix(config, seed=seed * world + rank)
     external_test = ds.external_test
     if external_test:
         extra_loader = data.extra_eval_dataloader(external_test, model_data, exclude=["Unclassified"])
@@ -116,7 +119,8 @@ def main(args):
         model_dir = Path(resume)
         state = load_train_state(model_dir)
         check_train_state(state, network=mo.network, classes=classes, img_shape=img_shape, optimizer=tr.optimizer,
-                          world=world, loss=loss_fn.describe(), checkpoint_on=checkpoint_on)
+                          world=world, loss=loss_fn.describe(), checkpoint_on=checkpoint_on,
+                          mix=batch_mix.describe() if batch_mix is not None else None)
     else:
         # model directory <path>/<network>[_<id>]; id "auto" = next free number, picked by rank 0 for the whole job
         # (another rank could already see the directory rank 0 has just made)
@@ -164,6 +168,8 @@ def main(args):
 
     run_info = {"network": mo.network, "classes": classes, "img_shape": [int(v) for v in img_shape],
                 "optimizer": tr.optimizer, "world": world, "loss": loss_fn.describe(), "checkpoint_on": checkpoint_on}
+    if batch_mix is not None:        # (no key without mixing: the file of a run that never heard of it)
+        run_info["mix"] = batch_mix.describe()
     if state is not None and (state["early_stopped"] or state["epoch"] >= tr.max_epochs):
         # nothing left to train (raise `max_epochs` to extend a run that reached it): the reports of the best model
         if chief:
@@ -173,7 +179,7 @@ def main(args):
         best_state = train_net(net, model_data.train_loader, model_data.val_loader, optimizer, loss_fn, tr.max_epochs,
                                tr.early_stop_patience, model_dir, device, lr_scheduler, lr_warmup, dist=dist,
                                run_info=run_info if tr.save_train_state else None, resume=state,
-                               checkpoint_on=checkpoint_on)
+                               checkpoint_on=checkpoint_on, batch_mix=batch_mix)
     if dist is not None:
         dist.barrier()
     net.load_state_dict(torch.load(best_state, map_location="cpu"))
@@ -225,10 +231,19 @@ def load_train_state(model_dir):
     return torch.load(path, map_location="cpu", weights_only=True)
 
 
-def check_train_state(state, network, classes, img_shape, optimizer, world, loss=None, checkpoint_on="accuracy"):
+def _same_mix(a, b):
+    """Two `BatchMix.describe()` dicts (None: no mixing) name the same mixing."""
+    if not a or not b:
+        return not a and not b
+    keys = ("mixup_alpha", "cutmix_alpha", "prob", "switch_prob")
+    return all(float(a.get(k, -1.0)) == float(b.get(k, -1.0)) for k in keys)
+
+
+def check_train_state(state, network, classes, img_shape, optimizer, world, loss=None, checkpoint_on="accuracy", mix=None):
     """A resumed run must be the run that wrote the file: one line naming the first thing that differs.
     loss: `CrossEntropyLoss.describe()` of the config (None: the defaults); a file without the key - every file written
-    before the loss had options - was trained with the defaults, and likewise for `checkpoint_on`."""
+    before the loss had options - was trained with the defaults, and likewise for `checkpoint_on`.
+    mix: `BatchMix.describe()` of the config (None: no mixing); a file without the key was written without mixing."""
     if state.get("format") != TRAIN_STATE_FORMAT:
         raise ValueError(f"cannot resume: train_state.pth has format number {state.get('format')}, this version reads "
                          f"{TRAIN_STATE_FORMAT}")
@@ -252,14 +267,23 @@ def check_train_state(state, network, classes, img_shape, optimizer, world, loss
     if state.get("checkpoint_on", "accuracy") != checkpoint_on:
         raise ValueError(f"cannot resume: checkpoint_on differs, train_state.pth has {state.get('checkpoint_on', 'accuracy')}, "
                          f"the config gives {checkpoint_on}")
+    if not _same_mix(state.get("mix"), mix):
+        def show_mix(d):
+            return "off" if not d else ", ".join(f"{k} {float(v):g}" for k, v in sorted(d.items()))
+        raise ValueError(f"cannot resume: mix differs, train_state.pth has {show_mix(state.get('mix'))}, the config gives "
+                         f"{show_mix(mix)}")
 
 
-def _rank_state(net):
+def _rank_state(net, batch_mix=None):
     """What differs from rank to rank: the positions of the generators the shuffle (torch) and the augmentation draws
     (Python's `random`) come from, and the model's mask seed and step counter.  numpy's global generator is not
-    saved: nothing on the training path draws from it."""
+    saved: nothing on the training path draws from it.  With mixing on, the position of the `BatchMix` generator too
+    (`mix_rng`; no such key without it)."""
     import random
-    return {"torch_rng": torch.get_rng_state(), "python_rng": random.getstate(), "model": net.train_counters()}
+    out = {"torch_rng": torch.get_rng_state(), "python_rng": random.getstate(), "model": net.train_counters()}
+    if batch_mix is not None:
+        out["mix_rng"] = batch_mix.getstate()
+    return out
 
 
 def _sampler_of(loader):
@@ -283,7 +307,7 @@ def collect_train_state(run_info, epoch, ended, early_stopped, net, optimizer, l
     }
 
 
-def restore_train_state(state, net, optimizer, lr_scheduler, rank, train_loader):
+def restore_train_state(state, net, optimizer, lr_scheduler, rank, train_loader, batch_mix=None):
     """Inverse of `collect_train_state`; returns the book-keeping of the epoch loop."""
     import random
     net.load_state_dict(state["net"])
@@ -303,12 +327,14 @@ def restore_train_state(state, net, optimizer, lr_scheduler, rank, train_loader)
     net.set_train_counters(mine["model"])
     torch.set_rng_state(mine["torch_rng"])
     random.setstate(mine["python_rng"])
+    if batch_mix is not None and "mix_rng" in mine:
+        batch_mix.setstate(mine["mix_rng"])
     return state["book"]
 
 
 def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epochs, early_stop_patience,
               model_dir, device, lr_scheduler=None, lr_warmup=None, dist=None, run_info=None, resume=None,
-              checkpoint_on="accuracy"):
+              checkpoint_on="accuracy", batch_mix=None):
     """loss_fn: None (nn.CrossEntropyLoss() as the reference constructs it), a `loss.CrossEntropyLoss` or a
     `torch.nn.CrossEntropyLoss`: its `weight` and `label_smoothing` go to the loss kernel fused into the training and
     validation steps (`HipNet.set_loss`); another reduction than "mean" is a ValueError.
@@ -320,7 +346,10 @@ def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epo
     Data parallelism: every rank normalises its loss by the weights of ITS batch (W = sum_i w[y_i]) and the gradients
     are averaged over the ranks, as DistributedDataParallel does - not the mean of one global batch.
     run_info (network, classes, img_shape, optimizer, world): write `train_state.pth` at the end of every epoch;
-    resume: the loaded file of an earlier run to continue behind its last finished epoch."""
+    resume: the loaded file of an earlier run to continue behind its last finished epoch.
+    batch_mix: a `mix.BatchMix` (or None): called once per TRAINING batch, on the device batch, and the step then runs
+    the two-label criterion lam * CE(out, y) + (1 - lam) * CE(out, y.roll(1)); the `[STAT] Train Acc` line counts
+    against the dominant label of each batch.  Validation and test batches are never mixed."""
     loss = loss_mod.from_loss_fn(loss_fn)
     if checkpoint_on not in ("accuracy", "balanced_accuracy"):
         raise ValueError(f"checkpoint_on must be accuracy or balanced_accuracy. Got: {checkpoint_on}")
@@ -339,7 +368,8 @@ def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epo
     best_state = Path(model_dir) / "best_state.pth"
     first_epoch = 1
     if resume is not None:
-        book = restore_train_state(resume, net, optimizer, lr_scheduler, dp.rank_world(dist)[0], train_dataloader)
+        book = restore_train_state(resume, net, optimizer, lr_scheduler, dp.rank_world(dist)[0], train_dataloader,
+                                   batch_mix)
         max_val_acc, min_val_loss, no_improvement = book["max_val_acc"], book["min_val_loss"], book["no_improvement"]
         train_accs, train_losses = list(book["train_accs"]), list(book["train_losses"])
         val_accs, val_losses = list(book["val_accs"]), list(book["val_losses"])
@@ -363,7 +393,11 @@ def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epo
             for batch in (tqdm(train_dataloader) if chief else train_dataloader):
                 x, y = batch[0], batch[1]
                 optimizer.zero_grad()
-                net.forward_backward(x, y)
+                if batch_mix is None:
+                    net.forward_backward(x, y)
+                else:       # on the device batch: a CPU batch of the host loader is transferred first
+                    xm, ya, yb, lam = batch_mix(x.to(device, non_blocking=True), torch.as_tensor(y).to(device))
+                    net.forward_backward(xm, ya, y2=yb, lam=lam)
                 sync.all_reduce(optimizer)
                 optimizer.step()
                 seen += len(y)
@@ -429,7 +463,7 @@ def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epo
             if run_info is not None:
                 # after every decision of this epoch; the generators stand where the loaders left them (their batch
                 # thread has ended with the epoch's last batch), the ranks' positions are gathered into the one file
-                ranks = dp.gather_object(_rank_state(net), dist)
+                ranks = dp.gather_object(_rank_state(net, batch_mix), dist)
                 if chief:
                     book = {"max_val_acc": max_val_acc, "min_val_loss": min_val_loss, "no_improvement": no_improvement,
                             "train_accs": train_accs, "train_losses": train_losses, "val_accs": val_accs,
