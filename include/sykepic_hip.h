@@ -414,6 +414,15 @@ int spk_op_conv3x3(const void* x_dev, const float* w_dev, const float* bn_scale_
                    const void* res_dev, void* y_dev, int n, int h, int w, int cin, int cout, int relu, int split, int cfg,
                    void* hip_stream);
 int spk_op_conv3x3_num_configs(void);
+/* The direct 3x3 kernel of the 64 -> 64 channel convs (csrc/conv_d3.hip: weights resident in LDS, activation fragments
+ * loaded straight into registers) on caller-provided DEVICE buffers: x [n,h,w,cin] fp16, w [cout][3][3][cin] fp32, pad 1.
+ * cfg >= 0: that configuration - SPK_ERR_UNSUPPORTED ("does not fit") unless cin = cout = 64, stride 1 and split == 0;
+ * cfg < 0: the implicit-GEMM kernel on the same problem (bit-identical where both run).  iters > 0 with ms_out: the
+ * launch is repeated iters times and *ms_out is the mean time of one in milliseconds. */
+int spk_op_conv3x3_direct(const void* x_dev, const float* w_dev, const float* bn_scale_dev, const float* bn_bias_dev,
+                          const void* res_dev, void* y_dev, int n, int h, int w, int cin, int cout, int stride, int relu,
+                          int split, int cfg, int iters, float* ms_out, void* stream);
+int spk_op_conv3x3_direct_num_configs(void);
 /* A whole identity bottleneck block of the eval path (torchvision Bottleneck.forward without downsample, reached through
  * `net(x)`: /root/reference/sykepic/compute/probability.py:189): y = ReLU(BN3(W3 . ReLU(BN2(W2 * ReLU(BN1(W1 . x))))) + x).
  * x, y: [n,h,w,4 cm] fp16 device tensors (y != x); fp32 device weights w1 [cm][4 cm], w2 [cm][3][3][cm], w3 [4 cm][cm];

@@ -2,7 +2,7 @@
 // library has ~9 k lines of it).  Built by `build.sh asan` with -fsanitize=address,undefined on the HOST pass of every
 // translation unit and run on the CPU (tests/test_abi.py): it walks the host logic that does not need a GPU - handle
 // creation and its error paths, the parameter table, spk_last_error, and the tuner table (tune_table.h: one parser for
-// the seven tags of the tune-cache file, the nearest-batch rule, the appended lines) - so that heap overflows,
+// the tags of the tune-cache file, the nearest-batch rule, the appended lines) - so that heap overflows,
 // use-after-free and undefined behaviour there abort the run.  With no GPU every HIP call fails and the error paths
 // are what runs; on a GPU box the same binary works on real (small) buffers.  argv[1]: the shipped tuning seed
 // (default: the source tree's).
@@ -143,15 +143,20 @@ static void tuner_table_checks(const std::string& tmp, const std::string& seed_p
       {2, 9, 9, 64, 64, 5, 13}, {9, 9, 64, 0, 64, 5, 0}, {9, 64, 5, 2}, {81, 64, 64, 3, 1, 0, 1, 64064, 1}};
   for (int t = 0; t < (int)fresh.size(); ++t) spk_tune_store((TuneTag)t, fresh[t].data(), fresh[t].data() + kTuneSchemas[t].n_key, true);
   spk_tune_store(TUNE_DW, dk, &one, true);
-  EXPECT(read_tune_lines(tmp).size() == lines.size() + fresh.size());   // (nothing for the depthwise choice)
+  const int d3_fresh[] = {9, 9, 1, 5, kD3NumCfgs - 1};                  // the tag behind the depthwise one: not in `fresh`
+  spk_tune_store(TUNE_D3, d3_fresh, d3_fresh + kTuneSchemas[TUNE_D3].n_key, true);
+  EXPECT(read_tune_lines(tmp).size() == lines.size() + fresh.size() + 1);   // (nothing for the depthwise choice)
   use_cache(tmp.c_str());
+  EXPECT(look(TUNE_D3, {9, 9, 1, 5}) == kD3NumCfgs - 1);
+  EXPECT(look(TUNE_D3, {9, 9, 1, 8}) == kD3NumCfgs - 1);                // the nearest-batch rule holds for it too
+  EXPECT(look(TUNE_D3, {9, 9, 0, 5}) == -1000);
   for (int t = 0; t < (int)fresh.size(); ++t) {
     int v[2] = {-1000, -1000};
     EXPECT(spk_tune_find((TuneTag)t, fresh[t].data(), v));
     for (int i = 0; i < kTuneSchemas[t].n_val; ++i) EXPECT(v[i] == fresh[t][kTuneSchemas[t].n_key + i]);
   }
   EXPECT(look(TUNE_DW, {0, 64, 28, 28, 240, 5, 1}) == -1000);
-  EXPECT(spk_tune_detail::table().map.size() == lines.size() + fresh.size());
+  EXPECT(spk_tune_detail::table().map.size() == lines.size() + fresh.size() + 1);
   remove(tmp.c_str());
 }
 
@@ -258,6 +263,8 @@ int main(int argc, char** argv) {
     fprintf(f, "chain 14 14 256 0 256 64 0\n");
     fprintf(f, "bneck 14 256 8 1\n");
     fprintf(f, "wgrad 6272 256 256 3 1 0 13 128128 1\n");
+    fprintf(f, "d3 56 56 0 128 -1\n");
+    fprintf(f, "d3 56 56 1 128 %d\n", kD3NumCfgs);                 // (out of range)
     fprintf(f, "pw1x1 2 14 14 256 2048 1 1 1 256 99999\n");       // values out of range: ignored
     fprintf(f, "pw1x1 2 14 14 256 2048 1 1 1 256 -2\n");
     fprintf(f, "pw2 1 14 14 256 28 28 512 2048 1 2 256 %d\n", kPwNumCfgs);
@@ -291,13 +298,15 @@ int main(int argc, char** argv) {
   EXPECT(look(TUNE_BNECK, {14, 256, 8}) == 1);
   EXPECT(look(TUNE_WGRAD, {6272, 256, 256, 3, 1, 0, 13, 128128}) == 1);
   EXPECT(look(TUNE_C3, {2, 7, 7, 512, 512, 128}) == 13);
+  EXPECT(look(TUNE_D3, {56, 56, 0, 128}) == -1);
+  EXPECT(look(TUNE_D3, {56, 56, 1, 128}) == -1000);
   EXPECT(look(TUNE_PW1, {2, 14, 14, 256, 2048, 1, 1, 1, 256}) == -1000);
   EXPECT(look(TUNE_PW2, {1, 14, 14, 256, 28, 28, 512, 2048, 1, 2, 256}) == -1000);
   EXPECT(look(TUNE_C3, {1, 14, 14, 256, 512, 256}) == -1000);
   EXPECT(look(TUNE_CHAIN, {14, 14, 256, 0, 512, 64}) == -1000);
   EXPECT(look(TUNE_BNECK, {28, 128, 8}) == -1000);
   EXPECT(look(TUNE_WGRAD, {6272, 256, 512, 3, 1, 0, 13, 128128}) == -1000);
-  EXPECT(spk_tune_detail::table().map.size() == 8);
+  EXPECT(spk_tune_detail::table().map.size() == 9);
   setenv("SPK_AUTOTUNE", "0", 1);
   // a problem that is NOT in the file (channels 128), on real buffers when there is a GPU
   const int n = 1, h = 8, wd = 8, cin = 128, cout = 128, M = n * h * wd;

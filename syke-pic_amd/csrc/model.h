@@ -41,6 +41,8 @@ struct Layer {
   size_t wpw_off = 0;             // fragment-ordered image of a 1x1 conv's weights (conv_pw.hip), when pw_ok
   bool pw_ok = false;             // 1x1, stride 1 or 2, no padding anywhere, channels multiples of 64
   bool c3_ok = false;             // 3x3 stride 1 pad 1, cin % 64 == 0, cout % 256 == 0: conv_c3.hip (image at wpw_off)
+  bool d3_ok = false;             // 3x3 stride 1 pad 1, cin = cout = 64: conv_d3.hip (image at wd3_off)
+  size_t wd3_off = 0;             // its [cout][9 cin] weights in conv_pw.hip's fragment order
   // eval: a block-closing 1x1 conv and the 1x1 shortcut (downsample) conv of its block as ONE K-concatenated GEMM
   // (conv_pw.hip, PwConvArgs::x2): the shortcut tensor is neither written nor re-read
   int dual_src = -1;              // block-closing conv: index of the shortcut conv it absorbs, or -1

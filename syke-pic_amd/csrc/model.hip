@@ -331,6 +331,13 @@ extern "C" int spk_model_create_grouped(const spk_layer_desc* layers, const int3
         L.wpw_off = wpack;
         wpack += (size_t)2 * L.d.cout * 9 * L.d.cin;
       }
+      // the 64 -> 64 3x3 convs (stage 1): a third image, the K = 9 * 64 GEMM panel in the 1x1 kernel's fragment order
+      L.d3_ok = L.mode == CONV_MODE_GENERIC && L.d.k == 3 && L.d.stride == 1 && L.d.pad == 1 && L.cin_p == L.d.cin &&
+                L.cout_p == L.d.cout && L.d.cin == 64 && L.d.cout == 64 && L.kpad == 9 * L.d.cin && L.d.relu != SPK_ACT_HSWISH;
+      if (L.d3_ok) {
+        L.wd3_off = wpack;
+        wpack += (size_t)L.d.cout * 9 * L.d.cin;
+      }
     } else {
       continue;
     }
@@ -701,6 +708,10 @@ int spk_commit(spk_model* m) {
     if ((L.c3_ok || (L.bn_head >= 0 && L.d.k == 3)) && m->infer_dt == DT_F16 &&
         spk_launch_pack_c3(wsrc, m->wpack + L.wpw_off, L.d.cout, L.d.cin, layer_split(m, L) ? 2 : 1, m->stream))
       return fail(SPK_ERR_HIP, "pack_c3 launch failed");
+    // (from the same rounded values as the implicit GEMM's image above: master layout [cout][kh][kw][cin] = [cout][K])
+    if (L.d3_ok && m->infer_dt == DT_F16 && !layer_split(m, L) &&
+        spk_launch_pack_pw(wsrc, nullptr, m->wpack + L.wd3_off, L.d.cout, 9 * L.d.cin, DT_F16, 1, m->stream))
+      return fail(SPK_ERR_HIP, "pack_pw (3x3 panel) launch failed");
   }
   // fused (block-closing + shortcut) convs: K-concatenated weights with both eval-BN scales folded in, normalised per
   // cout by a power of two (exact in the fp32 epilogue), in fragment order
@@ -1356,6 +1367,16 @@ static int run_conv_eval(spk_model* m, Layer& L, int nb) {
     const int r = spk_conv3x3_launch(q, m->stream);
     if (r == 0) return SPK_OK;
     if (r != -3) return fail(SPK_ERR_HIP, std::string("3x3 conv launch failed for ") + L.d.name);
+  }
+  if (L.d3_ok && a.dt == DT_F16 && !a.splitw && !a.res_lo && !a.y_lo && !a.cin_s && !a.cout_s && !a.pool_y) {
+    C3Args q;
+    memset(&q, 0, sizeof q);
+    q.x = a.x; q.wp = m->wpack + L.wd3_off; q.y = a.y; q.scale = a.scale; q.shift = a.bias; q.res = a.res;
+    q.N = nb; q.H = in.h; q.W = in.w; q.Cin = a.Cin; q.Cout = a.Cout; q.M = a.M; q.relu = a.relu; q.dt = DT_F16; q.nb = 1;
+    q.x_bytes = a.x_bytes; q.y_bytes = (unsigned)((size_t)a.M * a.Cout * 2);
+    if (spk_conv3x3_d3_launch(a, q, m->stream))
+      return fail(SPK_ERR_HIP, std::string("3x3 conv launch failed for ") + L.d.name);
+    return SPK_OK;
   }
   if (spk_conv_launch(a, L.mode, m->stream, nullptr))
     return fail(SPK_ERR_HIP, std::string("conv launch failed for ") + L.d.name);

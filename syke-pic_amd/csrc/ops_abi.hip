@@ -12,6 +12,7 @@
 // Scratch is allocated and freed inside the call (these are not on any hot path).
 #include "model.h"
 #include "train_effnet.h"
+#include "tune_table.h"
 
 #include <algorithm>
 #include <cstring>
@@ -432,6 +433,56 @@ extern "C" int spk_op_conv3x3(const void* x, const float* w_ohwi, const float* b
   return SPK_OK;
 }
 extern "C" int spk_op_conv3x3_num_configs(void) { return spk_c3_num_configs(); }
+
+// The direct 64 -> 64 3x3 kernel (conv_d3.hip) on caller-provided buffers: x [n,h,wd,cin] fp16, w [cout][3][3][cin] fp32.
+// cfg >= 0: that configuration, SPK_ERR_UNSUPPORTED ("does not fit") for a problem the kernel does not take (cin or cout
+// not 64, stride not 1, split weights) or a configuration it does not have; cfg < 0: the implicit GEMM on the same problem.
+// iters > 0: the launch is then repeated iters times between two events and *ms_out is the mean time of one.
+extern "C" int spk_op_conv3x3_direct(const void* x, const float* w_ohwi, const float* bn_scale, const float* bn_bias,
+                                     const void* res, void* y, int n, int h, int wd, int cin, int cout, int stride, int relu,
+                                     int split, int cfg, int iters, float* ms_out, void* stream) {
+  if (!x || !w_ohwi || !bn_scale || !bn_bias || !y || n < 1 || h < 1 || wd < 1 || (stride != 1 && stride != 2) || iters < 0)
+    return ofail(SPK_ERR_ARG, "op_conv3x3_direct: bad arguments");
+  if (cin % 64 || cout % 64) return ofail(SPK_ERR_UNSUPPORTED, "channels must be multiples of 64");
+  if (cfg >= 0 && (cin != 64 || cout != 64 || stride != 1 || split))
+    return ofail(SPK_ERR_UNSUPPORTED, "this configuration does not fit the problem");
+  hipStream_t s = (hipStream_t)stream;
+  const int ho = (h - 1) / stride + 1, wo = (wd - 1) / stride + 1, M = n * ho * wo;
+  if ((size_t)n * h * wd * cin * 2 >= 0x80000000ull || (size_t)M * cout * 2 >= 0x80000000ull)
+    return ofail(SPK_ERR_UNSUPPORTED, "op_conv3x3_direct: an operand of 2 GiB or more (split the batch)");
+  Scratch sc;
+  bf16_t* wp = sc.get<bf16_t>((size_t)2 * cout * 9 * cin);
+  if (!wp) return ofail(SPK_ERR_HIP, "hipMalloc failed");
+  ConvArgs a;
+  memset(&a, 0, sizeof a);
+  a.cfg = a.dma = -1;
+  a.cls_ph = a.cls_pw = -1;
+  a.x = (const bf16_t*)x; a.w = wp; a.y = (bf16_t*)y; a.scale = bn_scale; a.bias = bn_bias; a.res = (const bf16_t*)res;
+  a.N = n; a.H = h; a.W = wd; a.Cin = cin; a.Ho = ho; a.Wo = wo; a.Cout = cout;
+  a.kh = a.kw = 3; a.stride = stride; a.pad = 1; a.M = M; a.K = 9 * cin; a.relu = relu; a.dt = DT_F16; a.splitw = split != 0;
+  a.x_bytes = (unsigned)((size_t)n * h * wd * cin * 2);
+  a.w_bytes = (unsigned)((size_t)cout * 9 * cin * 2 * (split ? 2 : 1));
+  C3Args q;
+  memset(&q, 0, sizeof q);
+  q.x = a.x; q.wp = wp; q.y = a.y; q.scale = bn_scale; q.shift = bn_bias; q.res = a.res;
+  q.N = n; q.H = h; q.W = wd; q.Cin = cin; q.Cout = cout; q.M = M; q.relu = relu; q.dt = DT_F16; q.nb = 1;
+  q.x_bytes = a.x_bytes; q.y_bytes = (unsigned)((size_t)M * cout * 2);
+  if (cfg < 0) O_TRY(spk_launch_pack_weights(w_ohwi, wp, cout, 3, 3, cin, CONV_MODE_GENERIC, DT_F16, split != 0, s), "pack_weights");
+  else O_TRY(spk_launch_pack_pw(w_ohwi, nullptr, wp, cout, 9 * cin, DT_F16, 1, s), "pack_pw");
+  auto run = [&]() { return cfg < 0 ? spk_conv_launch(a, CONV_MODE_GENERIC, s, nullptr) : spk_d3_launch(q, cfg, s); };
+  const int r = run();
+  if (r == -3) return ofail(SPK_ERR_UNSUPPORTED, "this configuration does not fit the problem");
+  if (r) return ofail(SPK_ERR_HIP, "conv3x3_direct launch failed");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "conv3x3_direct kernel failed");
+  if (iters > 0 && ms_out) {
+    SpkLaunchTimer timer;
+    float ms = 0.f;
+    if (!timer.ok || !timer.time(s, iters, run, &ms)) return ofail(SPK_ERR_HIP, "conv3x3_direct timing failed");
+    *ms_out = ms / (float)iters;
+  }
+  return SPK_OK;
+}
+extern "C" int spk_op_conv3x3_direct_num_configs(void) { return spk_d3_num_configs(); }
 
 // A whole identity bottleneck block of the eval path on caller-provided buffers: x, y [n,h,w,4 cm] fp16; fp32 weights
 // w1 [cm][4 cm], w2 [cm][3][3][cm], w3 [4 cm][cm]; folded BatchNorm scale / shift per conv.  fused != 0: the one-kernel

@@ -259,6 +259,16 @@ int spk_launch_pack_c3(const float* w_ohwi, bf16_t* out, int cout, int cin, int 
 int spk_conv3x3_launch(const C3Args& a, hipStream_t s);
 
 // ---------------------------------------------------------------------------
+// Direct 3x3 stride-1 pad-1 convolution for Cin = Cout = 64: the whole weight panel resident in LDS, activation
+// fragments loaded straight into VGPRs (conv_d3.hip).  C3Args with wp = the [Cout][kh][kw][Cin] image packed by
+// spk_launch_pack_pw (K = 9 * Cin, nb = 1); wp_bytes is not used.  Bit-identical to the implicit GEMM.
+// ---------------------------------------------------------------------------
+int spk_d3_num_configs();
+int spk_d3_launch(const C3Args& a, int cfg, hipStream_t s);   // -3: this kernel / configuration does not fit the problem
+// eval path: the implicit GEMM (a) or the fastest configuration of conv_d3.hip (q), timed once per problem and cached
+int spk_conv3x3_d3_launch(const ConvArgs& a, const C3Args& q, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // A whole identity bottleneck block (1x1 -> 3x3 -> 1x1 + shortcut, ReLU after each BatchNorm) as one kernel: the two mid
 // tensors stay in LDS (conv_bneck.hip).  fp16, single weight images.
 // ---------------------------------------------------------------------------

@@ -23,11 +23,12 @@
 
 constexpr int kPwNumCfgs = 18;   // configurations of spk_pw_launch (conv_pw.hip)
 constexpr int kC3NumCfgs = 14;   // configurations of spk_c3_launch (conv_c3.hip)
+constexpr int kD3NumCfgs = 6;    // configurations of spk_d3_launch (conv_d3.hip)
 
 // One line of the file is "<tag> <n_key ints> <n_val ints>".  n_pos is the position of the batch size N among the key
 // fields (-1: the key has none and matches exactly only); values outside [val_min, val_max] are dropped on load.
 struct TuneSchema { const char* tag; int n_key, n_pos, n_val, val_min, val_max; };
-enum TuneTag { TUNE_CONV, TUNE_PW1, TUNE_PW2, TUNE_C3, TUNE_CHAIN, TUNE_BNECK, TUNE_WGRAD, TUNE_DW, TUNE_NTAGS };
+enum TuneTag { TUNE_CONV, TUNE_PW1, TUNE_PW2, TUNE_C3, TUNE_CHAIN, TUNE_BNECK, TUNE_WGRAD, TUNE_DW, TUNE_D3, TUNE_NTAGS };
 constexpr TuneSchema kTuneSchemas[TUNE_NTAGS] = {
     // mode dt splitw N H W Cin Cout k stride pad_cls stats operands -> tile config, main-loop flavour
     {"conv", 13, 3, 2, INT_MIN, INT_MAX},
@@ -38,6 +39,7 @@ constexpr TuneSchema kTuneSchemas[TUNE_NTAGS] = {
     {"bneck", 3, 2, 1, 0, 2},                 // H CM N -> 0 three launches, 1 / 2 whole-block kernel (14- / 7-row blocks)
     {"wgrad", 8, -1, 1, INT_MIN, INT_MAX},    // M Cin Cout k stride stem splits tile -> pipeline stages
     {nullptr, 7, -1, 1, 0, 1},                // depthwise (never in the file): et N H W C k stride -> 0 gather, 1 LDS ring
+    {"d3", 4, 3, 1, -1, kD3NumCfgs - 1},      // H W res N -> -1 implicit GEMM, else configuration of the direct 64 -> 64 3x3 kernel
 };
 
 // nullptr: no file (SPK_TUNE_CACHE unset, empty or "off")

@@ -293,6 +293,34 @@ def conv3x3(x, weight, bn_scale, bn_bias, relu=True, split=False, cfg=0, res=Non
     return y.permute(0, 3, 1, 2)
 
 
+def conv3x3_direct_num_configs():
+    return int(lib.load().spk_op_conv3x3_direct_num_configs())
+
+
+def conv3x3_direct(x, weight, bn_scale, bn_bias, relu=True, split=False, cfg=0, res=None, stride=1, iters=0):
+    """Eval-path 3x3 pad-1 conv + folded BN (+ shortcut) (+ ReLU) by the direct 64 -> 64 kernel (spk_op_conv3x3_direct,
+    csrc/conv_d3.hip).  x [N,Cin,H,W] float16, weight [Cout,Cin,3,3], res [N,Cout,Ho,Wo] or None.  cfg >= 0: that
+    configuration, RuntimeError "does not fit" for a problem the kernel does not take; cfg < 0: the implicit GEMM on the
+    same problem.  iters > 0: returns (y, mean milliseconds of one launch over iters back-to-back launches)."""
+    import ctypes as C
+    so = lib.load()
+    dev = x.device
+    n, cin, h, w = x.shape
+    cout = weight.shape[0]
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    xh = x.half().permute(0, 2, 3, 1).contiguous()
+    y = torch.full((n, ho, wo, cout), float("nan"), dtype=torch.float16, device=dev)
+    wk = weight.float().permute(0, 2, 3, 1).contiguous()   # OIHW -> O,kh,kw,I
+    rh = res.half().permute(0, 2, 3, 1).contiguous() if res is not None else None
+    ms = C.c_float(0.0)
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_conv3x3_direct(_p(xh), _p(wk), _p(bn_scale.float().contiguous()), _p(bn_bias.float().contiguous()),
+                                           _p(rh) if rh is not None else None, _p(y), n, h, w, cin, cout, int(stride),
+                                           int(bool(relu)), int(bool(split)), int(cfg), int(iters), C.byref(ms), _stream(dev)))
+    y = y.permute(0, 3, 1, 2)
+    return (y, float(ms.value)) if iters > 0 else y
+
+
 def bottleneck(x, w1, w2, w3, bn1, bn2, bn3, fused=True, iters=0, stamps=None, wz=None, bnz=None):
     """Eval-path identity bottleneck block (spk_op_bottleneck): x [N,4cm,H,W] float16, w1 [cm,4cm,1,1], w2 [cm,cm,3,3],
     w3 [4cm,cm,1,1], bn* = (scale, shift) of the folded eval BatchNorms.  fused: the one-kernel form (csrc/conv_bneck.hip),
