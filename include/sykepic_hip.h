@@ -314,6 +314,45 @@ int spk_model_set_loss(spk_model* m, const float* class_weights_host, float labe
  * one (no counters are kept).  Synchronous. */
 int spk_model_class_counts_read(spk_model* m, int64_t* host, int reset);
 
+/* --- Exponential moving average (EMA) of the weights (not in the reference; the usual fine-tuning recipe) ---
+ * A second flat float32 buffer in the layout of the model's own: every parameter and every float buffer (BatchNorm
+ * running mean / variance).  num_batches_tracked (int64) is not averaged: the model's own value serves both states.
+ * Every argument and state check happens before any HIP call.
+ *
+ * spk_model_ema_enable(m, on != 0): allocate the buffer (4 bytes per flat element) and copy the model's tensors into
+ *   it - the average STARTS as a copy; enabled already: copy again.  SPK_ERR_STATE while swapped in.  on == 0: free it; an
+ *   average that is swapped in is swapped out first, so the model keeps its own weights.  spk_model_destroy frees it.
+ *   Synchronous.
+ * spk_model_ema_update(m, w): avg[i] = fma(w, model[i] - avg[i], avg[i]) over the whole buffer - one fused multiply-add
+ *   of the float32-rounded difference, torch.lerp's formula for w < 0.5, used here for every w; w = 1 - decay.  Where
+ *   model[i] == avg[i] the average keeps its bits (a frozen tensor's average stays the tensor), except that -0 becomes
+ *   +0.  One launch on the model's stream, behind everything the last training and optimizer step left running.
+ *   w not finite or outside (0, 1): SPK_ERR_ARG; not enabled, or swapped in: SPK_ERR_STATE.
+ * spk_model_ema_swap(m): exchange the CONTENTS of the two buffers (one launch on the model's stream; pointers and
+ *   offsets stay) and toggle the `swapped` state; every packed weight image is rebuilt from what the model's buffer
+ *   now holds.  While swapped in, spk_eval_step, spk_forward_infer, spk_model_read_param and spk_model_load_param work
+ *   on the average, spk_train_forward_backward*, spk_optim_step and spk_model_ema_update return SPK_ERR_STATE ("the
+ *   moving average is swapped in"), and spk_model_ema_read / _load address the model's own tensors.  Not enabled:
+ *   SPK_ERR_STATE.
+ * spk_model_load_param on a model that is NOT swapped in changes the model alone: the average keeps its values
+ *   (spk_model_ema_load, or spk_model_ema_enable again, sets them).
+ * spk_model_ema_read / spk_model_ema_load: one float tensor of the other buffer, float32 in state_dict layout like
+ *   spk_model_read_param.  Synchronous.  A null argument, an int64 key or a size mismatch: SPK_ERR_ARG; unknown key:
+ *   SPK_ERR_KEY; not enabled: SPK_ERR_STATE.
+ * spk_model_ema_state: the two flags. */
+int spk_model_ema_enable(spk_model* m, int on);
+int spk_model_ema_update(spk_model* m, float w);
+int spk_model_ema_swap(spk_model* m);
+int spk_model_ema_read(spk_model* m, const char* key, float* host, int64_t numel);
+int spk_model_ema_load(spk_model* m, const char* key, const float* host, int64_t numel);
+int spk_model_ema_state(spk_model* m, int* enabled, int* swapped);
+/* Test hooks: the launches of spk_model_ema_update / spk_model_ema_swap on caller buffers, n floats each at any 4-byte
+ * aligned device address (16-byte accesses on the aligned body, element accesses on the head and the tail).
+ * Synchronous.  SPK_ERR_ARG, before any HIP call: a null pointer, n < 1, a misaligned pointer, overlapping ranges, w not
+ * finite or outside (0, 1). */
+int spk_op_ema_lerp(float* e_dev, const float* p_dev, int64_t n, float w, void* hip_stream);
+int spk_op_swap_f32(float* a_dev, float* b_dev, int64_t n, void* hip_stream);
+
 /* Test hook: copy activation `tensor_id` (spk_layer_desc.dst numbering) of the
  * most recent forward to the host as float32 NCHW ([n,c,h,w]; [n,c] for the
  * head).  The stem input (id 0) is not readable.  Synchronous. */

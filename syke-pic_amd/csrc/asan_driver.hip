@@ -201,6 +201,24 @@ int main(int argc, char** argv) {
     EXPECT(spk_mix_batch(img_a, img_b, 2, 4, 4, 3, SPK_LAYOUT_NHWC, SPK_DTYPE_U8, 1, NAN, 0.5f, 0, 0, 4, 4, nullptr) == SPK_ERR_ARG);
     EXPECT(spk_mix_batch(img_a, img_a + 8, 2, 4, 4, 3, SPK_LAYOUT_NHWC, SPK_DTYPE_U8, 1, 0.5f, 0.5f, 0, 0, 4, 4, nullptr) == SPK_ERR_ARG);
     EXPECT(spk_mix_batch(img_a, img_b, 2, 4, 4, 3, SPK_LAYOUT_NCHW, SPK_DTYPE_U8, 1, 0.5f, 0.5f, 0, 0, 4, 4, nullptr) == SPK_ERR_ARG);
+    // ... and the moving average's: a null handle, the weight, null / overlapping / misaligned buffers, the count
+    float ea[8] = {0}, eb[8] = {0};
+    int en = 0, sw = 0;
+    EXPECT(spk_model_ema_enable(nullptr, 1) == SPK_ERR_ARG);
+    EXPECT(spk_model_ema_update(nullptr, 0.1f) == SPK_ERR_ARG);
+    EXPECT(spk_model_ema_swap(nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_model_ema_read(nullptr, "head.0.weight", f, 4) == SPK_ERR_ARG);
+    EXPECT(spk_model_ema_load(nullptr, "head.0.weight", f, 4) == SPK_ERR_ARG);
+    EXPECT(spk_model_ema_state(nullptr, &en, &sw) == SPK_ERR_ARG);
+    EXPECT(spk_op_ema_lerp(ea, eb, 8, 0.f, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_op_ema_lerp(ea, eb, 8, 1.f, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_op_ema_lerp(ea, eb, 8, NAN, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_op_ema_lerp(ea, eb, 0, 0.1f, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_op_ema_lerp(ea, nullptr, 8, 0.1f, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_op_ema_lerp(ea, ea + 4, 8, 0.1f, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_op_swap_f32(ea, ea + 7, 8, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_op_swap_f32(ea, (float*)((char*)eb + 2), 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_op_swap_f32(nullptr, eb, 8, nullptr) == SPK_ERR_ARG);
   }
 
   // ---- a small bottleneck graph: stem, pool, 1x1 / 3x3 / 1x1 + shortcut, pool, head ----

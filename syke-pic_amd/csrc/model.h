@@ -97,6 +97,9 @@ struct spk_model {
 
   float* pbuf = nullptr;       // flat fp32 master parameters + buffers
   size_t n_flat = 0, n_train = 0;
+  // exponential moving average of pbuf (spk_model_ema_*): a second flat buffer in pbuf's layout, null while off
+  float* ema = nullptr;
+  bool ema_swapped = false;    // the CONTENTS of pbuf and ema are exchanged: pbuf holds the average, no training step runs
   bf16_t* wpack = nullptr;     // bf16 conv weights, [Cout][K] per layer
   float* scale_bias = nullptr; // eval-BN folded scale/bias per conv
   float* dwpack = nullptr;     // fp32 tap-major weights of depthwise / 3x3-stem layers (EfficientNet)

@@ -431,6 +431,7 @@ extern "C" void spk_model_destroy(spk_model* m) {
   hipDeviceSynchronize();
   free_acts(m);
   if (m->pbuf) hipFree(m->pbuf);
+  if (m->ema) hipFree(m->ema);
   if (m->wpack) hipFree(m->wpack);
   if (m->scale_bias) hipFree(m->scale_bias);
   if (m->dwpack) hipFree(m->dwpack);
@@ -542,6 +543,97 @@ int spk_read_flat(spk_model* m, const float* flat, const Param& p, float* host) 
         for (int64_t w = 0; w < W; ++w)
           host[(size_t)(((o * I + i) * H + h) * W + w)] = tmp[(size_t)(((o * H + h) * W + w) * I + i)];
   return SPK_OK;
+}
+
+// ---------------------------------------------------------------------------
+// exponential moving average of the weights (include/sykepic_hip.h): a second flat buffer in pbuf's layout
+// ---------------------------------------------------------------------------
+static bool ema_weight_ok(float w) { return w > 0.f && w < 1.f; }   // (false for NaN; nothing infinite is below 1)
+
+// exchanges the CONTENTS of pbuf and the average on the model's stream: every packed image is rebuilt from pbuf at its
+// next use; offsets into pbuf that other code holds stay valid
+static int ema_exchange(spk_model* m) {
+  SPK_TRY(spk_train_join(m));
+  if (spk_launch_swap_f32(m->pbuf, m->ema, m->n_flat, m->stream) != 0) return fail(SPK_ERR_HIP, "model_ema_swap: launch failed");
+  m->ema_swapped = !m->ema_swapped;
+  m->dirty = true;
+  spk_train_mark_dirty(m);
+  return SPK_OK;
+}
+
+extern "C" int spk_model_ema_enable(spk_model* m, int on) {
+  if (!m) return fail(SPK_ERR_ARG, "model_ema_enable: null model");
+  if (on && m->ema_swapped)
+    return fail(SPK_ERR_STATE, "model_ema_enable: the moving average is swapped in (swap back before starting it again)");
+  if (!on && !m->ema) return SPK_OK;
+  HIP_TRY(hipSetDevice(m->device));
+  if (!on) {
+    if (m->ema_swapped) SPK_TRY(ema_exchange(m));   // the model keeps its own weights
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    HIP_TRY(hipFree(m->ema));
+    m->ema = nullptr;
+    return SPK_OK;
+  }
+  SPK_TRY(spk_train_join(m));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  if (!m->ema) HIP_TRY(hipMalloc((void**)&m->ema, m->n_flat * sizeof(float)));
+  HIP_TRY(hipMemcpy(m->ema, m->pbuf, m->n_flat * sizeof(float), hipMemcpyDeviceToDevice));
+  return SPK_OK;
+}
+
+extern "C" int spk_model_ema_state(spk_model* m, int* enabled, int* swapped) {
+  if (!m || !enabled || !swapped) return fail(SPK_ERR_ARG, "model_ema_state: null argument");
+  *enabled = m->ema != nullptr;
+  *swapped = m->ema_swapped;
+  return SPK_OK;
+}
+
+extern "C" int spk_model_ema_update(spk_model* m, float w) {
+  if (!m) return fail(SPK_ERR_ARG, "model_ema_update: null model");
+  if (!ema_weight_ok(w)) return fail(SPK_ERR_ARG, "model_ema_update: w must be finite and inside (0, 1)");
+  if (!m->ema) return fail(SPK_ERR_STATE, "model_ema_update: the moving average is not enabled");
+  if (m->ema_swapped) return fail(SPK_ERR_STATE, "model_ema_update: the moving average is swapped in");
+  HIP_TRY(hipSetDevice(m->device));
+  SPK_TRY(spk_train_join(m));
+  if (spk_launch_ema_lerp(m->ema, m->pbuf, m->n_flat, w, m->stream) != 0)
+    return fail(SPK_ERR_HIP, "model_ema_update: launch failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_model_ema_swap(spk_model* m) {
+  if (!m) return fail(SPK_ERR_ARG, "model_ema_swap: null model");
+  if (!m->ema) return fail(SPK_ERR_STATE, "model_ema_swap: the moving average is not enabled");
+  HIP_TRY(hipSetDevice(m->device));
+  return ema_exchange(m);
+}
+
+// the float tensor `key` of the average: argument checks of spk_model_ema_read / spk_model_ema_load
+static int ema_param(spk_model* m, const char* key, const void* host, int64_t numel, const char* fn, const Param** out) {
+  if (!m || !key || !host) return fail(SPK_ERR_ARG, std::string(fn) + ": null argument");
+  if (!m->ema) return fail(SPK_ERR_STATE, std::string(fn) + ": the moving average is not enabled");
+  const Param* p = find_param(m, key);
+  if (!p) return fail(SPK_ERR_KEY, std::string(fn) + ": unknown state_dict key: " + key);
+  if (p->dtype == SPK_DTYPE_I64)
+    return fail(SPK_ERR_ARG, std::string(fn) + ": " + key + " is an int64 counter: it is not averaged, the model's own serves");
+  if (numel != p->numel) return fail(SPK_ERR_ARG, std::string(fn) + ": size mismatch for " + key);
+  *out = p;
+  return SPK_OK;
+}
+
+extern "C" int spk_model_ema_read(spk_model* m, const char* key, float* host, int64_t numel) {
+  const Param* p = nullptr;
+  SPK_TRY(ema_param(m, key, host, numel, "model_ema_read", &p));
+  HIP_TRY(hipSetDevice(m->device));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  return spk_read_flat(m, m->ema, *p, host);
+}
+
+extern "C" int spk_model_ema_load(spk_model* m, const char* key, const float* host, int64_t numel) {
+  const Param* p = nullptr;
+  SPK_TRY(ema_param(m, key, host, numel, "model_ema_load", &p));
+  HIP_TRY(hipSetDevice(m->device));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  return spk_load_flat(m, m->ema, *p, host);
 }
 
 extern "C" int spk_model_set_requires_grad(spk_model* m, const char* key, int flag) {

@@ -1166,3 +1166,34 @@ extern "C" int spk_op_gavgpool_backward(const float* gy, void* gx, int n, int hw
   if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_gavgpool_backward: kernel failed");
   return SPK_OK;
 }
+
+// ---- the two kernels of the weights' moving average (train_kernels.hip) on caller buffers: the launches
+// spk_model_ema_update / spk_model_ema_swap make on the model's flat buffers ----
+namespace {
+// shared argument rules: two disjoint ranges of n >= 1 floats at 4-byte aligned addresses
+int stream_pair_args(const char* who, const void* a, const void* b, int64_t n) {
+  if (!a || !b) return ofail(SPK_ERR_ARG, std::string(who) + ": null pointer");
+  if (n < 1) return ofail(SPK_ERR_ARG, std::string(who) + ": n < 1");
+  const size_t ua = (size_t)a, ub = (size_t)b, bytes = (size_t)n * 4;
+  if ((ua | ub) & 3) return ofail(SPK_ERR_ARG, std::string(who) + ": buffers not 4-byte aligned");
+  if (ua < ub + bytes && ub < ua + bytes) return ofail(SPK_ERR_ARG, std::string(who) + ": the two ranges overlap");
+  return SPK_OK;
+}
+}  // namespace
+
+extern "C" int spk_op_ema_lerp(float* e, const float* p, int64_t n, float w, void* stream) {
+  if (const int r = stream_pair_args("op_ema_lerp", e, p, n)) return r;
+  if (!(w > 0.f && w < 1.f)) return ofail(SPK_ERR_ARG, "op_ema_lerp: w must be finite and inside (0, 1)");
+  hipStream_t s = (hipStream_t)stream;
+  O_TRY(spk_launch_ema_lerp(e, p, (size_t)n, w, s), "ema lerp");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_ema_lerp: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_swap_f32(float* a, float* b, int64_t n, void* stream) {
+  if (const int r = stream_pair_args("op_swap_f32", a, b, n)) return r;
+  hipStream_t s = (hipStream_t)stream;
+  O_TRY(spk_launch_swap_f32(a, b, (size_t)n, s), "swap");
+  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_swap_f32: kernel failed");
+  return SPK_OK;
+}

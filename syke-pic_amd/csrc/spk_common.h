@@ -460,6 +460,10 @@ int spk_launch_pack_dgrad(const float* w, bf16_t* out, int cout, int taps, int c
 int spk_launch_opt_multi(int kind, float* p, const float* g, float* m, float* v, const OptTable& t,
                          float b1, float b2, float eps, float wd, float momentum, float gscale, float alpha,
                          hipStream_t s);
+// moving average of the weights (train_kernels.hip): e[i] = fma(w, p[i] - e[i], e[i]), and the exchange of two arrays.
+// n floats at any 4-byte aligned addresses; the two arrays must not overlap.
+int spk_launch_ema_lerp(float* e, const float* p, size_t n, float w, hipStream_t s);
+int spk_launch_swap_f32(float* a, float* b, size_t n, hipStream_t s);
 void spk_wgrad_plan(int M, int Cout, int Ktot, int* splits, int* pix_per_split);
 int spk_wgrad_launch(const bf16_t* x, const bf16_t* dy, float* slabs, int N, int H, int W, int Cin,
                      int Ho, int Wo, int Cout, int k, int stride, int pad, int stem, int splits,

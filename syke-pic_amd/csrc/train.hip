@@ -983,6 +983,8 @@ static int train_step(spk_model* m, const void* x, int n, int h, int w, int layo
                       const int64_t* y2, float lam, float* stats, float* logits_out) {
   if (!m || !x || !y || !stats || n < 1) return tfail(SPK_ERR_ARG, "train step: bad arguments");
   if (dtype != SPK_DTYPE_F32 && dtype != SPK_DTYPE_U8) return tfail(SPK_ERR_ARG, "train step: dtype must be f32 or u8");
+  // pbuf holds the average (spk_model_ema_swap): a step would train it, and update running statistics that are not the model's
+  if (m->ema_swapped) return tfail(SPK_ERR_STATE, "train step: the moving average is swapped in (spk_model_ema_swap back first)");
   HIP_TRY(hipSetDevice(m->device));
   SPK_TRY(ensure_state(m));
   SPK_TRY(plan_train(m, n, h, w));
@@ -1214,6 +1216,7 @@ extern "C" int spk_optim_step(spk_model* m, const spk_optim_desc* opt) {
     return tfail(SPK_ERR_UNSUPPORTED,
                  "optimizer kind not supported (SGD, Adam, AdamW, RMSprop, Adagrad, Adamax, NAdam, RAdam, Adadelta, ASGD, Rprop)");
   if (!m->train) return tfail(SPK_ERR_STATE, "optim_step before any training step");
+  if (m->ema_swapped) return tfail(SPK_ERR_STATE, "optim_step: the moving average is swapped in (spk_model_ema_swap back first)");
   HIP_TRY(hipSetDevice(m->device));
   TrainState* t = m->train;
   const float gscale = opt->grad_scale == 0.f ? 1.f : opt->grad_scale;

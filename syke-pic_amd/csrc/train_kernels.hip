@@ -681,6 +681,122 @@ inline int grid_for(size_t total, int block) {
   return (int)g;
 }
 
+// ---- Exponential moving average of the flat parameter buffer (spk_model_ema_update / spk_model_ema_swap) ----
+// Both kernels are one pass over float32 arrays and HBM-bound.  The array that is WRITTEN (e; both of swap's) sets the
+// geometry: `head` scalars up to its first 16-byte boundary, then `body` 16-byte chunks, then `tail` scalars, so every
+// chunk is stored with one aligned 16-byte store whatever the pointers and n are.  The other array is read 16 bytes at a
+// time where its chunk is aligned too (always, for the model's own buffers) and element by element otherwise - one
+// decision per launch (VEC).  Every thread has four chunks in flight per round of the grid-stride loop; the grid is
+// sized to the device (spk_stream_grid), never to n.
+struct StreamGeom {
+  int head, tail;
+  long long body;
+};
+
+template <bool VEC>
+__device__ __forceinline__ f32x4_t stream_load4(const float* p) {
+  if (VEC) return *(const f32x4_t*)p;
+  f32x4_t v;
+  v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3];
+  return v;
+}
+template <bool VEC>
+__device__ __forceinline__ void stream_store4(float* p, const f32x4_t v) {
+  if (VEC) { *(f32x4_t*)p = v; return; }
+  p[0] = v[0]; p[1] = v[1]; p[2] = v[2]; p[3] = v[3];
+}
+
+// e + w (p - e) as ONE fused multiply-add of the rounded difference: torch.lerp's formula for w < 0.5, used for every
+// w.  Written with the intrinsics so that contraction flags cannot change it (there is nothing left to contract: the
+// difference is an operand of the product).  p == e gives e back bit for bit, except that e = -0 becomes +0.
+__device__ __forceinline__ float ema_lerp1(float e, float p, float w) { return __fmaf_rn(w, __fsub_rn(p, e), e); }
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void ema_lerp_kernel(float* __restrict__ e, const float* __restrict__ p,
+                                                       StreamGeom g, float w) {
+  const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)gridDim.x * 256;
+  if (tid < g.head) e[tid] = ema_lerp1(e[tid], p[tid], w);
+  float* eb = e + g.head;
+  const float* pb = p + g.head;
+  if (tid < g.tail) {
+    const long long i = g.body * 4 + tid;
+    eb[i] = ema_lerp1(eb[i], pb[i], w);
+  }
+  for (long long q = tid; q < g.body; q += 4 * nth) {
+    f32x4_t ev[4], pv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (q + k * nth < g.body) {
+        ev[k] = *(const f32x4_t*)(eb + 4 * (q + k * nth));
+        pv[k] = stream_load4<VEC>(pb + 4 * (q + k * nth));
+      }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (q + k * nth < g.body) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ev[k][j] = ema_lerp1(ev[k][j], pv[k][j], w);
+        *(f32x4_t*)(eb + 4 * (q + k * nth)) = ev[k];
+      }
+  }
+}
+
+// exchanges the contents of two disjoint arrays (geometry from a; VEC: b's chunks are 16-byte aligned too)
+template <bool VEC>
+__global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, StreamGeom g) {
+  const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)gridDim.x * 256;
+  if (tid < g.head) { const float t = a[tid]; a[tid] = b[tid]; b[tid] = t; }
+  float* ab = a + g.head;
+  float* bb = b + g.head;
+  if (tid < g.tail) {
+    const long long i = g.body * 4 + tid;
+    const float t = ab[i]; ab[i] = bb[i]; bb[i] = t;
+  }
+  for (long long q = tid; q < g.body; q += 4 * nth) {
+    f32x4_t av[4], bv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (q + k * nth < g.body) {
+        av[k] = *(const f32x4_t*)(ab + 4 * (q + k * nth));
+        bv[k] = stream_load4<VEC>(bb + 4 * (q + k * nth));
+      }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (q + k * nth < g.body) {
+        *(f32x4_t*)(ab + 4 * (q + k * nth)) = bv[k];
+        stream_store4<VEC>(bb + 4 * (q + k * nth), av[k]);
+      }
+  }
+}
+
+// head / body / tail of n floats at `written`, and whether `other` is 16-byte aligned where the body starts
+inline StreamGeom stream_geom(const void* written, const void* other, size_t n, bool* vec) {
+  StreamGeom g;
+  const size_t head = (4 - (((size_t)written >> 2) & 3)) & 3;
+  g.head = (int)(head < n ? head : n);
+  g.body = (long long)((n - g.head) / 4);
+  g.tail = (int)(n - g.head - (size_t)g.body * 4);
+  *vec = (((size_t)other + (size_t)g.head * 4) & 15) == 0;
+  return g;
+}
+
+// blocks of 256 threads for a streaming pass: eight per compute unit of the current device (asked once), fewer when the
+// array has fewer chunks than that many threads would take in one round
+inline int spk_stream_grid(long long chunks) {
+  static int cus = 0;
+  if (cus <= 0) {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) == hipSuccess &&
+        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
+      cus = v;
+    else
+      cus = 256;
+  }
+  long long want = (chunks + 256 * 4 - 1) / (256 * 4);
+  if (want < 1) want = 1;
+  const long long cap = (long long)cus * 8;
+  return (int)(want < cap ? want : cap);
+}
+
 }  // namespace
 
 #define LAUNCH_OK() (hipGetLastError() == hipSuccess ? 0 : -1)
@@ -840,5 +956,29 @@ int spk_launch_adam(float* p, const float* g, float* m, float* v, size_t n, floa
                     float eps, float wd, float gscale, float bc1, float bc2_sqrt, hipStream_t s) {
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps,
                      wd, gscale, bc1, bc2_sqrt);
+  return LAUNCH_OK();
+}
+
+// e[i] = fma(w, p[i] - e[i], e[i]) over n floats; e and p disjoint, 4-byte aligned (the callers check)
+int spk_launch_ema_lerp(float* e, const float* p, size_t n, float w, hipStream_t s) {
+  bool vec;
+  const StreamGeom g = stream_geom(e, p, n, &vec);
+  const dim3 grid(spk_stream_grid(g.body));
+  if (vec)
+    hipLaunchKernelGGL(ema_lerp_kernel<true>, grid, dim3(256), 0, s, e, p, g, w);
+  else
+    hipLaunchKernelGGL(ema_lerp_kernel<false>, grid, dim3(256), 0, s, e, p, g, w);
+  return LAUNCH_OK();
+}
+
+// a <-> b over n floats; disjoint, 4-byte aligned
+int spk_launch_swap_f32(float* a, float* b, size_t n, hipStream_t s) {
+  bool vec;
+  const StreamGeom g = stream_geom(a, b, n, &vec);
+  const dim3 grid(spk_stream_grid(g.body));
+  if (vec)
+    hipLaunchKernelGGL(swap_f32_kernel<true>, grid, dim3(256), 0, s, a, b, g);
+  else
+    hipLaunchKernelGGL(swap_f32_kernel<false>, grid, dim3(256), 0, s, a, b, g);
   return LAUNCH_OK();
 }

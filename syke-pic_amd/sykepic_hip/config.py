@@ -84,6 +84,24 @@ def get_batch_mix(config, seed=0):
     return BatchMix(tr.mixup_alpha, tr.cutmix_alpha, tr.mix_prob, tr.mix_switch_prob, seed=seed)
 
 
+def _ema_decay(s):
+    """``ema_decay``: the decay of the weights' moving average (ema.py), 0 (or empty) = off."""
+    v = float(s) if s.strip() else 0.0
+    if not 0.0 <= v < 1.0:
+        raise ValueError(f"ema_decay must be at least 0.0 and below 1.0. Got: {v}")
+    return v
+
+
+def get_model_ema(config, net):
+    """The `ema.ModelEma` of ``[train] ema_decay / ema_warmup`` over `net`, or None when the decay is 0 (the default):
+    no object, no second buffer, no launch - the run of a file without the keys."""
+    tr = Settings(config).train
+    if tr.ema_decay == 0.0:
+        return None
+    from .ema import ModelEma
+    return ModelEma(net, tr.ema_decay, tr.ema_warmup)
+
+
 def _index_prob_pairs(s):
     """``dropout = 1,0.5;2,0.3`` -> [(1, 0.5), (2, 0.3)] (list index in the head, probability)."""
     return [(int(i), float(p)) for i, p in (pair.split(",") for pair in s.split(";"))] if s else []
@@ -120,6 +138,9 @@ KEYS = {
         # Mixup / CutMix of every training batch on the GPU (mix.py); both alphas 0: off, the run of a file without the keys
         "mixup_alpha": (_alpha("mixup_alpha"), "0"), "cutmix_alpha": (_alpha("cutmix_alpha"), "0"),
         "mix_prob": (_probability("mix_prob", 1.0), "1"), "mix_switch_prob": (_probability("mix_switch_prob", 0.5), "0.5"),
+        # exponential moving average of the weights (ema.py): validated, checkpointed and shipped as best_state.pth while the
+        # raw weights keep training; decay 0: off, the run of a file without the keys
+        "ema_decay": (_ema_decay, "0"), "ema_warmup": (_flag, "yes"),
     },
     "lr_warmup": {
         "use": (_flag, REQUIRED), "factor_1": (float, REQUIRED), "factor_2": (float, REQUIRED), "step_1": (int, REQUIRED),

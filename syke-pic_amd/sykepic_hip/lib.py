@@ -106,6 +106,14 @@ SYMBOLS = {
     "spk_model_train_counters_set": (C.c_int, [_P, C.c_uint64, C.c_uint64]),
     "spk_model_set_loss": (C.c_int, [_P, _P, C.c_float]),
     "spk_model_class_counts_read": (C.c_int, [_P, _P, C.c_int]),
+    "spk_model_ema_enable": (C.c_int, [_P, C.c_int]),
+    "spk_model_ema_update": (C.c_int, [_P, C.c_float]),
+    "spk_model_ema_swap": (C.c_int, [_P]),
+    "spk_model_ema_read": (C.c_int, [_P, C.c_char_p, _P, C.c_int64]),
+    "spk_model_ema_load": (C.c_int, [_P, C.c_char_p, _P, C.c_int64]),
+    "spk_model_ema_state": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "spk_op_ema_lerp": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P]),
+    "spk_op_swap_f32": (C.c_int, [_P, _P, C.c_int64, _P]),
     "spk_model_read_activation": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64]),
     "spk_model_read_activation_grad": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64]),
     "spk_op_conv_bn_train_forward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P] + [C.c_int] * 9 + [_P]),

@@ -681,6 +681,67 @@ class HipNet:
                                                      int(a.size)))
         return self
 
+    # ---- exponential moving average of the weights (spk_model_ema_*; ema.ModelEma drives it) ----
+    def ema_enable(self, on=True):
+        """Start the average as a copy of the model's tensors as they are NOW (again: copy again), or drop it."""
+        self._ensure_init()
+        with torch.cuda.device(self.device):
+            lib.check(self._lib.spk_model_set_stream(self._h, self._stream()))
+            lib.check(self._lib.spk_model_ema_enable(self._h, int(bool(on))))
+        return self
+
+    def ema_update(self, w):
+        """avg += w * (model - avg) over every parameter and float buffer, one kernel; w = 1 - decay, inside (0, 1)."""
+        with torch.cuda.device(self.device):
+            lib.check(self._lib.spk_model_set_stream(self._h, self._stream()))
+            lib.check(self._lib.spk_model_ema_update(self._h, float(w)))
+
+    def ema_swap(self):
+        """Exchange model and average: while swapped in, `eval_step`, `forward`, `state_dict` and `load_state_dict`
+        work on the average, and training steps are refused."""
+        with torch.cuda.device(self.device):
+            lib.check(self._lib.spk_model_set_stream(self._h, self._stream()))
+            lib.check(self._lib.spk_model_ema_swap(self._h))
+        return self
+
+    def ema_state(self):
+        """{"enabled": bool, "swapped": bool}"""
+        en, sw = C.c_int(), C.c_int()
+        lib.check(self._lib.spk_model_ema_state(self._h, C.byref(en), C.byref(sw)))
+        return {"enabled": bool(en.value), "swapped": bool(sw.value)}
+
+    def _ema_specs(self):
+        """The averaged tensors: every key of `state_dict()` but the int64 `num_batches_tracked` counters, in its order."""
+        return [(k, shape) for k, shape, kind in self._specs if kind != "bn_nbt"]
+
+    def ema_state_dict(self):
+        """The average as CPU float32 tensors in `state_dict()` layout and order, float keys only (the model's own
+        `num_batches_tracked` serves both).  While swapped in this is the model the average displaced."""
+        sd = OrderedDict()
+        for key, shape in self._ema_specs():
+            buf = np.empty(shape, dtype=np.float32)
+            lib.check(self._lib.spk_model_ema_read(self._h, key.encode(), C.c_void_p(buf.ctypes.data), int(buf.size)))
+            sd[key] = torch.from_numpy(buf)
+        return sd
+
+    def load_ema_state_dict(self, state):
+        """Inverse of `ema_state_dict`: exactly its keys, each with the tensor's shape."""
+        want = OrderedDict(self._ema_specs())
+        missing = [k for k in want if k not in state]
+        unexpected = [k for k in state if k not in want]
+        if missing or unexpected:
+            raise RuntimeError(f"Error(s) in loading the moving average of HipNet: missing keys {missing}, unexpected keys "
+                               f"{unexpected} (float tensors only: num_batches_tracked is not averaged)")
+        for k, shape in want.items():
+            v = state[k]
+            t = v.detach().cpu() if isinstance(v, torch.Tensor) else torch.as_tensor(v)
+            if tuple(t.shape) != tuple(shape):
+                raise RuntimeError(f"size mismatch for {k}: the average in the file has shape {tuple(t.shape)}, "
+                                   f"the shape in current model is {tuple(shape)}")
+            a = np.ascontiguousarray(t.numpy().astype(np.float32))
+            lib.check(self._lib.spk_model_ema_load(self._h, k.encode(), C.c_void_p(a.ctypes.data), int(a.size)))
+        return self
+
     def read_activation(self, tensor_id, n, shape):
         """Test hook: activation `tensor_id` of the last forward as a CPU
         float32 tensor of `shape` ([n,c,h,w] or [n,c])."""

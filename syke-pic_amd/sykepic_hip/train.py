@@ -16,6 +16,7 @@ GPU) every rank trains on its shard, gradients are all-reduced over RCCL and
 rank 0 alone prints, checkpoints and writes reports.
 """
 
+import contextlib
 import os
 import shutil
 from configparser import ConfigParser
@@ -24,8 +25,9 @@ from pathlib import Path
 import torch
 
 from . import arch, data, schedule
+from . import ema as ema_mod
 from . import loss as loss_mod
-from .config import Settings, get_batch_mix, get_network, get_transforms
+from .config import Settings, get_batch_mix, get_model_ema, get_network, get_transforms
 from . import dp
 from .dp import GradSync
 from .optim import HipOptimizer
@@ -107,6 +109,8 @@ def main(args):
     # Mixup / CutMix (mix.py): None unless `mixup_alpha` or `cutmix_alpha` is set; its own generator, seeded per rank by
     # the rule of the Dropout seed below
     batch_mix = get_batch_mix(config, seed=seed * world + rank)
+    # moving average of the weights (ema.py): its settings now, for the resume check; the object once the network exists
+    ema_info = ema_mod.describe(tr.ema_decay, tr.ema_warmup)
     external_test = ds.external_test
     if external_test:
         extra_loader = data.extra_eval_dataloader(external_test, model_data, exclude=["Unclassified"])
@@ -120,7 +124,7 @@ def main(args):
         state = load_train_state(model_dir)
         check_train_state(state, network=mo.network, classes=classes, img_shape=img_shape, optimizer=tr.optimizer,
                           world=world, loss=loss_fn.describe(), checkpoint_on=checkpoint_on,
-                          mix=batch_mix.describe() if batch_mix is not None else None)
+                          mix=batch_mix.describe() if batch_mix is not None else None, ema=ema_info)
     else:
         # model directory <path>/<network>[_<id>]; id "auto" = next free number, picked by rank 0 for the whole job
         # (another rank could already see the directory rank 0 has just made)
@@ -170,16 +174,20 @@ def main(args):
                 "optimizer": tr.optimizer, "world": world, "loss": loss_fn.describe(), "checkpoint_on": checkpoint_on}
     if batch_mix is not None:        # (no key without mixing: the file of a run that never heard of it)
         run_info["mix"] = batch_mix.describe()
+    if ema_info is not None:         # (likewise)
+        run_info["ema"] = ema_info
     if state is not None and (state["early_stopped"] or state["epoch"] >= tr.max_epochs):
         # nothing left to train (raise `max_epochs` to extend a run that reached it): the reports of the best model
         if chief:
             print(f"[INFO] {model_dir}: training ended after epoch {state['epoch']}, nothing to resume")
         best_state = Path(model_dir) / "best_state.pth"
     else:
+        # the average starts as a copy of the tensors every replica holds now (a resumed run loads its own over it)
+        model_ema = get_model_ema(config, net)
         best_state = train_net(net, model_data.train_loader, model_data.val_loader, optimizer, loss_fn, tr.max_epochs,
                                tr.early_stop_patience, model_dir, device, lr_scheduler, lr_warmup, dist=dist,
                                run_info=run_info if tr.save_train_state else None, resume=state,
-                               checkpoint_on=checkpoint_on, batch_mix=batch_mix)
+                               checkpoint_on=checkpoint_on, batch_mix=batch_mix, model_ema=model_ema)
     if dist is not None:
         dist.barrier()
     net.load_state_dict(torch.load(best_state, map_location="cpu"))
@@ -239,11 +247,13 @@ def _same_mix(a, b):
     return all(float(a.get(k, -1.0)) == float(b.get(k, -1.0)) for k in keys)
 
 
-def check_train_state(state, network, classes, img_shape, optimizer, world, loss=None, checkpoint_on="accuracy", mix=None):
+def check_train_state(state, network, classes, img_shape, optimizer, world, loss=None, checkpoint_on="accuracy", mix=None,
+                      ema=None):
     """A resumed run must be the run that wrote the file: one line naming the first thing that differs.
     loss: `CrossEntropyLoss.describe()` of the config (None: the defaults); a file without the key - every file written
     before the loss had options - was trained with the defaults, and likewise for `checkpoint_on`.
-    mix: `BatchMix.describe()` of the config (None: no mixing); a file without the key was written without mixing."""
+    mix: `BatchMix.describe()` of the config (None: no mixing); a file without the key was written without mixing.
+    ema: `ModelEma.describe()` of the config (None: no moving average); a file without the key was written without one."""
     if state.get("format") != TRAIN_STATE_FORMAT:
         raise ValueError(f"cannot resume: train_state.pth has format number {state.get('format')}, this version reads "
                          f"{TRAIN_STATE_FORMAT}")
@@ -272,6 +282,9 @@ def check_train_state(state, network, classes, img_shape, optimizer, world, loss
             return "off" if not d else ", ".join(f"{k} {float(v):g}" for k, v in sorted(d.items()))
         raise ValueError(f"cannot resume: mix differs, train_state.pth has {show_mix(state.get('mix'))}, the config gives "
                          f"{show_mix(mix)}")
+    if not ema_mod.same_settings(state.get("ema"), ema):
+        raise ValueError(f"cannot resume: ema differs, train_state.pth has {ema_mod.show_settings(state.get('ema'))}, "
+                         f"the config gives {ema_mod.show_settings(ema)}")
 
 
 def _rank_state(net, batch_mix=None):
@@ -291,10 +304,12 @@ def _sampler_of(loader):
     return s if hasattr(s, "set_epoch") and hasattr(s, "epoch") else None
 
 
-def collect_train_state(run_info, epoch, ended, early_stopped, net, optimizer, lr_scheduler, book, ranks, train_loader):
-    """Everything `train_net` needs to go on with epoch `epoch + 1` as if it had never stopped."""
+def collect_train_state(run_info, epoch, ended, early_stopped, net, optimizer, lr_scheduler, book, ranks, train_loader,
+                        model_ema=None):
+    """Everything `train_net` needs to go on with epoch `epoch + 1` as if it had never stopped.  With a moving average
+    the `ema` entry holds its settings, its `tensors` and its count of `updates`; no such key without."""
     sampler = _sampler_of(train_loader)
-    return {
+    out = {
         "format": TRAIN_STATE_FORMAT, **run_info,
         "epoch": int(epoch), "ended": bool(ended), "early_stopped": bool(early_stopped),
         "net": dict(net.state_dict()),
@@ -305,12 +320,17 @@ def collect_train_state(run_info, epoch, ended, early_stopped, net, optimizer, l
         "sampler_epoch": int(sampler.epoch) if sampler is not None else None,
         "book": book, "ranks": ranks,
     }
+    if model_ema is not None:
+        out["ema"] = {**model_ema.describe(), **model_ema.state_dict()}
+    return out
 
 
-def restore_train_state(state, net, optimizer, lr_scheduler, rank, train_loader, batch_mix=None):
+def restore_train_state(state, net, optimizer, lr_scheduler, rank, train_loader, batch_mix=None, model_ema=None):
     """Inverse of `collect_train_state`; returns the book-keeping of the epoch loop."""
     import random
-    net.load_state_dict(state["net"])
+    net.load_state_dict(state["net"])       # (the model alone: the average is loaded next)
+    if model_ema is not None:
+        model_ema.load_state_dict(state["ema"])
     params = dict(net.named_parameters())
     for key, flag in state["requires_grad"].items():
         params[key].requires_grad = flag
@@ -334,7 +354,7 @@ def restore_train_state(state, net, optimizer, lr_scheduler, rank, train_loader,
 
 def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epochs, early_stop_patience,
               model_dir, device, lr_scheduler=None, lr_warmup=None, dist=None, run_info=None, resume=None,
-              checkpoint_on="accuracy", batch_mix=None):
+              checkpoint_on="accuracy", batch_mix=None, model_ema=None):
     """loss_fn: None (nn.CrossEntropyLoss() as the reference constructs it), a `loss.CrossEntropyLoss` or a
     `torch.nn.CrossEntropyLoss`: its `weight` and `label_smoothing` go to the loss kernel fused into the training and
     validation steps (`HipNet.set_loss`); another reduction than "mean" is a ValueError.
@@ -349,7 +369,13 @@ def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epo
     resume: the loaded file of an earlier run to continue behind its last finished epoch.
     batch_mix: a `mix.BatchMix` (or None): called once per TRAINING batch, on the device batch, and the step then runs
     the two-label criterion lam * CE(out, y) + (1 - lam) * CE(out, y.roll(1)); the `[STAT] Train Acc` line counts
-    against the dominant label of each batch.  Validation and test batches are never mixed."""
+    against the dominant label of each batch.  Validation and test batches are never mixed.
+    model_ema: an `ema.ModelEma` over `net` (or None): updated after every `optimizer.step()`; at the end of an epoch the
+    average is swapped in for the validation pass and the `best_state.pth` save, so the `[STAT] Val` lines, the
+    checkpoint rule, early stopping and the plateau scheduler see the averaged model, while the `[STAT] Train` lines stay
+    those of the raw training forward.  Every rank keeps its own average: the parameters are equal on all ranks by
+    construction, the averaged running statistics are averaged over the ranks in front of the validation pass, as the
+    raw ones are.  `train_state.pth` is written after swapping back and carries both."""
     loss = loss_mod.from_loss_fn(loss_fn)
     if checkpoint_on not in ("accuracy", "balanced_accuracy"):
         raise ValueError(f"checkpoint_on must be accuracy or balanced_accuracy. Got: {checkpoint_on}")
@@ -369,13 +395,16 @@ def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epo
     first_epoch = 1
     if resume is not None:
         book = restore_train_state(resume, net, optimizer, lr_scheduler, dp.rank_world(dist)[0], train_dataloader,
-                                   batch_mix)
+                                   batch_mix, model_ema)
         max_val_acc, min_val_loss, no_improvement = book["max_val_acc"], book["min_val_loss"], book["no_improvement"]
         train_accs, train_losses = list(book["train_accs"]), list(book["train_losses"])
         val_accs, val_losses = list(book["val_accs"]), list(book["val_losses"])
         first_epoch = resume["epoch"] + 1
         if chief:
             print(f"[INFO] Resuming after epoch {resume['epoch']}")
+    if model_ema is not None and chief:
+        print(f"[INFO] Validation, the checkpoint rule and best_state.pth use the moving average of the weights "
+              f"({ema_mod.show_settings(model_ema.describe())}); the Train figures are those of the raw weights")
     try:
         from tqdm import tqdm
     except ImportError:  # pragma: no cover
@@ -400,6 +429,8 @@ def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epo
                     net.forward_backward(xm, ya, y2=yb, lam=lam)
                 sync.all_reduce(optimizer)
                 optimizer.step()
+                if model_ema is not None:
+                    model_ema.update()
                 seen += len(y)
             loss_sum, correct = net.read_stats()          # one device sync per epoch
             loss_sum, correct, seen = sync.reduce_stats(loss_sum, correct, seen)
@@ -413,40 +444,45 @@ def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epo
             # the validation set, and the counters are summed: checkpoint, early-stop and learning-rate decisions
             # below are then identical on every rank by construction
             dp.sync_buffers(net, dist)
-            net.eval()
-            net.reset_stats()
-            if extended:
-                net.read_class_counts(reset=True)      # drop the training pass's counts
-            seen = 0
-            for batch in val_dataloader:
-                net.eval_step(batch[0], batch[1])
-                seen += len(batch[1])
-            loss_sum, correct = net.read_stats()
-            loss_sum, correct, seen = sync.reduce_stats(loss_sum, correct, seen)
-            val_acc, val_loss = correct / seen, loss_sum / seen
-            val_accs.append(val_acc)
-            val_losses.append(val_loss)
-            criterion = val_acc
-            if extended:
-                counts = sync.reduce_class_counts(net.read_class_counts(reset=True))
-                val_bal = loss_mod.balanced_accuracy(counts.tolist())
-                if checkpoint_on == "balanced_accuracy":
-                    criterion = val_bal
-            if chief:
+            # with a moving average: the average stands in for the model from here to the checkpoint (and its running
+            # statistics are averaged over the ranks as the raw ones were, one line up); the raw weights come back after
+            with (model_ema.applied() if model_ema is not None else contextlib.nullcontext()):
+                if model_ema is not None:
+                    dp.sync_buffers(net, dist)
+                net.eval()
+                net.reset_stats()
                 if extended:
-                    print(f"[STAT] Val Acc: {val_acc:.3f}, Val Loss: {val_loss:.3f}, Val Balanced Acc: {val_bal:.3f}")
-                else:
-                    print(f"[STAT] Val Acc: {val_acc:.3f}, Val Loss: {val_loss:.3f}")
-                _plot(train_accs, train_losses, val_accs, val_losses, Path(model_dir), epoch)
-            if criterion > max_val_acc:
-                max_val_acc = criterion
+                    net.read_class_counts(reset=True)      # drop the training pass's counts
+                seen = 0
+                for batch in val_dataloader:
+                    net.eval_step(batch[0], batch[1])
+                    seen += len(batch[1])
+                loss_sum, correct = net.read_stats()
+                loss_sum, correct, seen = sync.reduce_stats(loss_sum, correct, seen)
+                val_acc, val_loss = correct / seen, loss_sum / seen
+                val_accs.append(val_acc)
+                val_losses.append(val_loss)
+                criterion = val_acc
+                if extended:
+                    counts = sync.reduce_class_counts(net.read_class_counts(reset=True))
+                    val_bal = loss_mod.balanced_accuracy(counts.tolist())
+                    if checkpoint_on == "balanced_accuracy":
+                        criterion = val_bal
                 if chief:
-                    print("[INFO] Increased balanced accuracy, saving model state"
-                          if checkpoint_on == "balanced_accuracy" else "[INFO] Increased accuracy, saving model state")
-                    try:
-                        save_atomically(net.state_dict(), best_state)
-                    except Exception as e:  # noqa: BLE001 - the previous best model is still there, the run goes on
-                        print(f"[INFO] Could not write {best_state.name} ({e}); the previous one stays")
+                    if extended:
+                        print(f"[STAT] Val Acc: {val_acc:.3f}, Val Loss: {val_loss:.3f}, Val Balanced Acc: {val_bal:.3f}")
+                    else:
+                        print(f"[STAT] Val Acc: {val_acc:.3f}, Val Loss: {val_loss:.3f}")
+                    _plot(train_accs, train_losses, val_accs, val_losses, Path(model_dir), epoch)
+                if criterion > max_val_acc:
+                    max_val_acc = criterion
+                    if chief:
+                        print("[INFO] Increased balanced accuracy, saving model state"
+                              if checkpoint_on == "balanced_accuracy" else "[INFO] Increased accuracy, saving model state")
+                        try:
+                            save_atomically(net.state_dict(), best_state)
+                        except Exception as e:  # noqa: BLE001 - the previous best model is still there, the run goes on
+                            print(f"[INFO] Could not write {best_state.name} ({e}); the previous one stays")
             if val_loss < min_val_loss or epoch == 1:
                 no_improvement = 0
                 min_val_loss = val_loss
@@ -470,7 +506,8 @@ def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epo
                             "val_losses": val_losses}
                     try:
                         save_atomically(collect_train_state(run_info, epoch, stop or epoch == max_epochs, stop, net,
-                                                            optimizer, lr_scheduler, book, ranks, train_dataloader),
+                                                            optimizer, lr_scheduler, book, ranks, train_dataloader,
+                                                            model_ema),
                                         Path(model_dir) / TRAIN_STATE_FILE)
                     except Exception as e:  # noqa: BLE001 - a recovery file, never a reason to lose the run
                         print(f"[INFO] Could not write {TRAIN_STATE_FILE} ({e}); the previous one stays")
