@@ -160,10 +160,107 @@ static void tuner_table_checks(const std::string& tmp, const std::string& seed_p
   remove(tmp.c_str());
 }
 
+// ---- the graph analysis (spk_graph_build, model_graph.hip): no HIP call, so it runs here whatever the host ----
+static spk_layer_desc op(int kind, const char* name, int cin, int cout, int k, int s, int p, int src, int dst, int relu, int child) {
+  spk_layer_desc d = conv(name, name, cin, cout, k, s, p, src, dst, -1, relu, child);
+  d.kind = kind;
+  return d;
+}
+
+static void graph_checks() {
+  // the ResNet stem + max-pool, a stage-1-shaped stage (a downsample block and two identity blocks, 256-channel trunk, cm 64)
+  // and the first (downsample) block of the next stage
+  std::vector<spk_layer_desc> g;
+  g.push_back(conv("base.0", "base.1", 3, 64, 7, 2, 3, 0, 1, -1, 1, 0));                                     // 0
+  g.push_back(op(SPK_OP_MAXPOOL, "base.3", 64, 64, 3, 2, 1, 1, 2, 0, 3));                                    // 1
+  g.push_back(conv("base.4.0.conv1", "base.4.0.bn1", 64, 64, 1, 1, 0, 2, 3, -1, 1, 4));                      // 2
+  g.push_back(conv("base.4.0.conv2", "base.4.0.bn2", 64, 64, 3, 1, 1, 3, 4, -1, 1, 4));                      // 3
+  g.push_back(conv("base.4.0.downsample.0", "base.4.0.downsample.1", 64, 256, 1, 1, 0, 2, 5, -1, 0, 4));     // 4
+  g.push_back(conv("base.4.0.conv3", "base.4.0.bn3", 64, 256, 1, 1, 0, 4, 6, 5, 1, 4));                      // 5
+  g.push_back(conv("base.4.1.conv1", "base.4.1.bn1", 256, 64, 1, 1, 0, 6, 7, -1, 1, 4));                     // 6
+  g.push_back(conv("base.4.1.conv2", "base.4.1.bn2", 64, 64, 3, 1, 1, 7, 8, -1, 1, 4));                      // 7
+  g.push_back(conv("base.4.1.conv3", "base.4.1.bn3", 64, 256, 1, 1, 0, 8, 9, 6, 1, 4));                      // 8
+  g.push_back(conv("base.4.2.conv1", "base.4.2.bn1", 256, 64, 1, 1, 0, 9, 10, -1, 1, 4));                    // 9
+  g.push_back(conv("base.4.2.conv2", "base.4.2.bn2", 64, 64, 3, 1, 1, 10, 11, -1, 1, 4));                    // 10
+  g.push_back(conv("base.4.2.conv3", "base.4.2.bn3", 64, 256, 1, 1, 0, 11, 12, 9, 1, 4));                    // 11
+  g.push_back(conv("base.5.0.conv1", "base.5.0.bn1", 256, 128, 1, 1, 0, 12, 13, -1, 1, 5));                  // 12
+  g.push_back(conv("base.5.0.conv2", "base.5.0.bn2", 128, 128, 3, 2, 1, 13, 14, -1, 1, 5));                  // 13
+  g.push_back(conv("base.5.0.downsample.0", "base.5.0.downsample.1", 256, 512, 1, 2, 0, 12, 15, -1, 0, 5));  // 14
+  g.push_back(conv("base.5.0.conv3", "base.5.0.bn3", 128, 512, 1, 1, 0, 14, 16, 15, 1, 5));                  // 15
+  g.push_back(op(SPK_OP_GAVGPOOL, "base.8", 512, 512, 1, 1, 0, 16, 17, 0, 8));                               // 16
+  g.push_back(op(SPK_OP_LINEAR, "head.0", 512, 10, 1, 1, 0, 17, 18, 0, -1));                                 // 17
+  {
+    spk_model m;
+    EXPECT(spk_graph_build(&m, g.data(), nullptr, (int)g.size()) == SPK_OK);
+    const std::vector<Layer>& L = m.layers;
+    const int nl = (int)L.size();
+    EXPECT(nl == 18 && m.n_tensors == 19 && !m.effnet);
+    EXPECT(L[0].fuse_pool == 1 && L[1].pooled_by_stem);
+    for (int c : {5, 15}) {   // block-closing conv + shortcut conv, the second with a stride-2 shortcut
+      EXPECT(L[c].dual_src == c - 1 && L[c - 1].fused_into == c && L[c - 1].side_branch);
+    }
+    for (int c : {5, 8, 11}) {   // block-closing conv -> the next block's conv1; the last one crosses the stage (256 -> 128)
+      EXPECT(L[c].chain_next == c + 1 && L[c + 1].chained_by == c);
+    }
+    EXPECT(L[15].chain_next == -1);
+    for (int h : {6, 9}) {   // the two identity blocks
+      EXPECT(L[h].bn_c2 == h + 1 && L[h].bn_c3 == h + 2 && L[h + 1].bn_head == h && L[h + 2].bn_head == h);
+    }
+    for (int h : {2, 3, 4, 5, 12, 13, 14, 15}) EXPECT(L[h].bn_c2 == -1 && L[h].bn_c3 == -1 && L[h].bn_head == -1);
+    for (int c : {3, 7, 10}) EXPECT(L[c].d3_ok && L[c].inner3x3);
+    EXPECT(!L[13].d3_ok);
+    size_t pairs = 0;
+    for (int i = 0; i < nl; ++i) {   // every index in range, every pair closed
+      const Layer& Q = L[i];
+      for (int idx : {Q.dual_src, Q.fused_into, Q.chain_next, Q.chained_by, Q.bn_c2, Q.bn_c3, Q.bn_head, Q.gate_conv, Q.gate_from,
+                      Q.se_dw, Q.src_se, Q.exp_next, Q.fuse_pool})
+        EXPECT(idx >= -1 && idx < nl);
+      for (int pi : {Q.p_w, Q.p_g, Q.p_b, Q.p_mean, Q.p_var, Q.p_nbt, Q.p_w2, Q.p_b2}) EXPECT(pi >= -1 && pi < (int)m.params.size());
+      if (Q.dual_src >= 0) { EXPECT(L[Q.dual_src].fused_into == i); ++pairs; }
+      if (Q.chain_next >= 0) { EXPECT(L[Q.chain_next].chained_by == i); ++pairs; }
+      EXPECT(Q.gate_conv == -1 && Q.gate_from == -1 && Q.se_dw == -1 && Q.src_se == -1);
+    }
+    EXPECT(pairs == 5);
+    EXPECT(m.n_wpack > 0 && m.n_sb > 0 && m.n_wdual == (size_t)2 * (256 * (64 + 64) + 512 * (128 + 256)) && m.n_sdual == 2 * (256 + 512));
+    EXPECT(m.n_flat >= m.n_train && m.n_train > 0 && m.n_means > 0);
+    for (const Param& p : m.params) EXPECT(p.dtype != SPK_DTYPE_F32 || p.off + (size_t)p.numel <= m.n_flat);
+    // state_dict order: a block's downsample conv is registered behind its conv3
+    EXPECT(m.index.at("base.4.0.conv3.weight") < m.index.at("base.4.0.downsample.0.weight"));
+  }
+  // one MBConv block behind a 3x3 stem: expand 1x1, depthwise, squeeze-excitation, project (+ the trunk)
+  std::vector<spk_layer_desc> e;
+  e.push_back(conv("base.0.0", "base.0.1", 3, 32, 3, 2, 1, 0, 1, -1, SPK_ACT_SILU, 0));                       // 0
+  e.push_back(conv("base.1.0.expand", "base.1.0.bn0", 32, 128, 1, 1, 0, 1, 2, -1, SPK_ACT_SILU, 1));          // 1
+  e.push_back(conv("base.1.0.dw", "base.1.0.bn1", 128, 128, 3, 1, 1, 2, 3, -1, SPK_ACT_SILU, 1));             // 2
+  e.back().kind = SPK_OP_DWCONV;
+  e.push_back(op(SPK_OP_SE, "base.1.0.se", 128, 128, 8, 1, 0, 3, 4, SPK_ACT_NONE, 1));                        // 3
+  e.push_back(conv("base.1.0.project", "base.1.0.bn2", 128, 32, 1, 1, 0, 4, 5, 1, SPK_ACT_NONE, 1));          // 4
+  e.push_back(conv("base.2.0.expand", "base.2.0.bn0", 32, 128, 1, 1, 0, 5, 6, -1, SPK_ACT_SILU, 2));          // 5: the next block's
+  e.push_back(op(SPK_OP_GAVGPOOL, "base.8", 128, 128, 1, 1, 0, 6, 7, 0, 8));                                  // 6
+  e.push_back(op(SPK_OP_LINEAR, "head.0", 128, 10, 1, 1, 0, 7, 8, 0, -1));                                    // 7
+  {
+    spk_model m;
+    EXPECT(spk_graph_build(&m, e.data(), nullptr, (int)e.size()) == SPK_OK);
+    const std::vector<Layer>& L = m.layers;
+    EXPECT(L.size() == 8 && m.effnet && !m.mobilenet);
+    EXPECT(L[3].gate_conv == 4 && L[4].gate_from == 3);
+    EXPECT(L[3].se_dw == 2 && L[4].src_se == 3);
+    // the expand conv behind a conv (what the fp8 project conv leaves its e4m3 copy for); none behind an expand conv itself
+    EXPECT(L[0].exp_next == 1 && L[4].exp_next == 5 && L[1].exp_next == -1 && L[5].exp_next == -1);
+    for (const Layer& Q : L) EXPECT(Q.dual_src == -1 && Q.chain_next == -1 && Q.bn_c2 == -1 && Q.bn_head == -1 && Q.fuse_pool == -1);
+    EXPECT(m.n_dwp > 0 && L[3].p_w2 >= 0 && L[3].p_b2 >= 0);
+    // a squeeze-excitation layer must not be wider than 1024 hidden units: the error path leaves nothing behind
+    e[3].k = 2000;
+    spk_model bad;
+    EXPECT(spk_graph_build(&bad, e.data(), nullptr, (int)e.size()) == SPK_ERR_UNSUPPORTED && strlen(spk_last_error()) > 0);
+  }
+}
+
 int main(int argc, char** argv) {
   int ndev = 0;
   const bool gpu = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
   printf("asan_driver: %d GPU(s)\n", gpu ? ndev : 0);
+  graph_checks();
 
   // ---- argument errors ----
   spk_model* m = nullptr;

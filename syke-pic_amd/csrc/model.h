@@ -54,19 +54,20 @@ struct Layer {
   // output, as one kernel (conv_pw.hip, PwConvArgs::wpz): the trunk is written but not re-read by that conv
   int chain_next = -1;            // block-closing conv: index of the conv it can also compute, or -1
   int chained_by = -1;            // that conv: index of the block-closing conv
-  bool chained_now_h[2] = {false, false};   // set by the block-closing conv's launch of the current forward, per half-batch
-                                  // chain (index = spk_model::half): chain_next is done for THAT half
   // eval, single-weight modes: a whole identity bottleneck block - conv1 1x1 -> conv2 3x3 -> conv3 1x1 + shortcut, ReLU behind
-  // each BatchNorm - as ONE kernel (conv_bneck.hip): the two mid tensors are never written
+  // each BatchNorm - as ONE kernel (conv_bneck.hip): the two mid tensors are never written.  (Or conv2's launch also
+  // computes conv3 + shortcut (+ the chained conv): conv_btail_kernel.)  Which form ran: spk_model::ran
   int bn_c2 = -1, bn_c3 = -1;     // the block's conv1: indices of its conv2 / conv3, or -1
   int bn_head = -1;               // conv2 / conv3 of such a block: index of its conv1
-  bool bneck_now_h[2] = {false, false};   // conv1: the one-kernel form ran for this half-batch chain of the current forward
-  bool btail_now_h[2] = {false, false};   // conv2: its launch also computed conv3 + shortcut (+ the chained conv): conv_btail_kernel
   size_t mu_off = 0;              // generic convs: offset of this layer's cin input-channel means in spk_model::act_mean
   // fp16 eval of an MBConv block: the squeeze-excitation layer computes its gates only and the project 1x1 conv that is
   // the sole reader of its output multiplies them into its activation operand (conv_igemm.hip, spk_set_gate)
   int gate_conv = -1;             // squeeze-excitation layer: index of that conv, or -1
   int gate_from = -1;             // that conv: index of the squeeze-excitation layer
+  // producers and readers the executor needs at a launch (resolved once, spk_graph_build; -1: none)
+  int se_dw = -1;                 // squeeze-excitation layer: the depthwise conv that writes its input (and leaves the pool partials)
+  int src_se = -1;                // conv: the squeeze-excitation layer that writes its input
+  int exp_next = -1;              // conv: the first expand-shaped 1x1 conv that reads its output (fp8: gets the trunk's e4m3 shadow)
   int64_t nbt = 0;  // num_batches_tracked (host copy; exact int64)
   bool trunk_writer = false;  // output is (or is added to) the residual trunk: stem, block-closing conv, downsample
   bool inner3x3 = false;      // 3x3 conv in the middle of a bottleneck block (reads a 1x1 conv's output)
@@ -79,6 +80,17 @@ struct Layer {
   int fuse_pool = -1;         // stem conv: index of the 3x3/2 max-pool layer its eval kernel can absorb (conv_stem.hip), or -1
   bool pooled_by_stem = false;  // that max-pool layer
 };
+
+// What the eval forward did with one layer (spk_model::ran) - the ONE place that says which launch computed a layer and
+// whether its output tensor is in the arena; the cases, one by one: DESIGN.md section 1.  form: EF_OWN plus what else its
+// launch did, or EF_INSIDE the launch of layer `by` (EF_NONE: has not run in this forward); wrote: the output tensor was
+// written.  A layer that finds itself EF_INSIDE when its turn comes has nothing left to do.
+enum EvalForm : uint8_t { EF_NONE = 0, EF_OWN = 1, EF_POOL = 2, EF_DUAL = 4, EF_CHAIN = 8, EF_BNECK = 16, EF_BTAIL = 32, EF_GATES = 64, EF_INSIDE = 128 };
+struct EvalRan { uint8_t form = EF_NONE; bool wrote = false; int by = -1; };
+// The fusions a call of the executor may use, and whether the call is the forward itself.  The tuners time their "two
+// kernels" / "three launches" alternatives with the fusion under test (and EVAL_FORWARD) taken out, a read-back recomputes
+// with 0: only the forward consults and writes spk_model::ran.
+enum : unsigned { FUSE_POOL = 1, FUSE_DUAL = 2, FUSE_CHAIN = 4, FUSE_BNECK = 8, FUSE_BTAIL = 16, FUSE_GATE = 32, FUSE_ALL = 63, EVAL_FORWARD = 64 };
 
 struct TrainState;
 
@@ -97,6 +109,7 @@ struct spk_model {
 
   float* pbuf = nullptr;       // flat fp32 master parameters + buffers
   size_t n_flat = 0, n_train = 0;
+  size_t n_wpack = 0, n_sb = 0, n_dwp = 0, n_wdual = 0, n_sdual = 0;   // elements of the packed images below (spk_graph_build)
   // exponential moving average of pbuf (spk_model_ema_*): a second flat buffer in pbuf's layout, null while off
   float* ema = nullptr;
   bool ema_swapped = false;    // the CONTENTS of pbuf and ema are exchanged: pbuf holds the average, no training step runs
@@ -108,14 +121,13 @@ struct spk_model {
   bool fuse_ds = true;         // SPK_FUSE_DS=0 turns the fusion off
   bool fuse_se = true;         // fp16 eval: squeeze-excitation scaling inside the project conv (SPK_SE_FUSE=0: its own pass)
   int chain = 1;               // conv3 -> next conv1 chaining: 1 where it is faster (timed once per problem), SPK_CHAIN=0 never, 2 always
-  bool no_chain_now = false;   // the chain tuner is timing the two-kernel alternative
   int bneck = 1;               // whole-bottleneck kernel: 1 where it is faster (rule + timing: bneck_choice), SPK_BNECK=0 never, 2 always
                                // (14-row blocks), 3 always (7-row blocks)
   bool two_streams_now = false;   // the executor is enqueueing the two halves of a batch on two streams
-  bool no_bneck_now = false;   // its tuner is timing the three-launch alternative
   int btail = 0;               // conv2 + conv3 (+ chained conv) kernel on the stage the whole-block kernel does not take: off - it is
                                // bit-identical but no faster than the launches it replaces; SPK_BTAIL=1
-  std::vector<char> stale;     // per tensor: the last eval forward did not write it (a fused-away shortcut tensor)
+  std::vector<EvalRan> ran[2]; // per layer: what the last eval forward did with it, for each of the two half-batch chains
+                               // (index = spk_model::half; a single-stream forward leaves chain 1 at EF_NONE).  Cleared by spk_eval_begin
   bool effnet = false;         // EfficientNet graph (widths that are not multiples of 64, depthwise / SE / SiLU ops): its
                                // TRAINING plan pads every activation tensor to a multiple of 64 channels (train_effnet.hip)
   bool mobilenet = false;      // MobileNetV3 arithmetic (a Hardswish layer or a ReLU / Hardsigmoid squeeze-excitation gate):
@@ -163,6 +175,7 @@ struct spk_model {
   size_t fp8_shadow_bytes = 0;
   size_t fp8_shadow_img = 0;            // bytes per image of the shadow: the largest h * w * stride of any shadowed tensor; a chunk
                                         // [img0, ...) starts at img0 * fp8_shadow_img in every block (disjoint slices per half-batch)
+                                        // (0: this forward leaves no copy)
   // state one layer leaves for the next, per half-batch chain of the two-stream forward (index = spk_model::half)
   int half = 0;                      // which of the two chains the executor is enqueueing (0: the caller's stream)
   int dw_chunks_h[2] = {0, 0};       // pool-partial rows per image the depthwise layer that ran last wrote
@@ -193,9 +206,7 @@ struct spk_model {
 
   int img0 = 0;                 // first image of the chunk the eval executor is working on (prefix micro-batching)
   bool fuse_stem_pool = true;   // eval: stem conv + max-pool in one kernel (SPK_FUSE_STEM_POOL=0 turns it off)
-  int stale_stem_t = -1;        // tensor id of the stem output the last eval forward did NOT write (fused), or -1
-  bool force_unfused = false;   // read_activation is recomputing the stem output
-  int last_eval_nb = 0;         // images of the last eval micro-batch (read_activation recomputes a stale tensor)
+  int last_eval_nb = 0;         // images of the last eval micro-batch (read_activation recomputes a tensor it did not write)
   float* P(int pi) const { return pbuf + params[pi].off; }
   void* T(int t) const { return (char*)arena + toff[t]; }
   // tensor t from image img0 on
@@ -214,10 +225,66 @@ struct spk_model {
 };
 
 void spk_set_error(const std::string& s);
+#define SPK_LOCAL __attribute__((visibility("hidden")))   // shared between the model_*.hip files, not a symbol of the library
+// the one error helper of the host code: records msg for spk_last_error and returns code
+SPK_LOCAL int spk_fail(int code, const std::string& msg);
+#define HIP_TRY(expr)                                                                                      \
+  do {                                                                                                     \
+    hipError_t e_ = (expr);                                                                                \
+    if (e_ != hipSuccess) return spk_fail(SPK_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+#define SPK_TRY(expr) do { int r_ = (expr); if (r_ != SPK_OK) return r_; } while (0)
+
+// model_graph.hip: the graph analysis.  No HIP call: fills m->layers (modes, roles, every fusion-candidate index), the
+// parameter table with its flat offsets (n_flat, n_train, n_means) and the offsets into the packed images with their sizes
+// (spk_model::n_wpack ...)
+SPK_LOCAL int spk_graph_build(spk_model* m, const spk_layer_desc* layers, const int32_t* groups, int n);
+// tensor t: n_src layers take it as their input, n_res convs add it as their shortcut operand (last: the last of them); producer writes it
+struct Readers { int n_src = 0, n_res = 0, last = -1, producer = -1; int total() const { return n_src + n_res; } };
+SPK_LOCAL Readers spk_readers_of(const spk_model* m, int t);
+// what the fp8 roles ask of an MBConv block's first conv (model_pack.hip; spk_graph_build resolves Layer::exp_next with it)
+static inline bool spk_expand_shaped(const spk_layer_desc& d) {
+  return d.kind == SPK_OP_CONV && d.k == 1 && d.stride == 1 && d.res < 0 && d.cout % 16 == 0 && d.src != 0;
+}
+SPK_LOCAL void spk_free_acts(spk_model* m);
+// model_pack.hip
 int spk_commit(spk_model* m);
+// does this conv run with hi/lo split weights in the eval path?  (inline: the executor asks several times per launch)
+static inline int layer_split(const spk_model* m, const Layer& L) {
+  if (m->infer_dt != DT_F16 || m->splitw == 0) return 0;
+  if (m->splitw == 4) return m->split_mask[&L - m->layers.data()] ? 1 : 0;
+  // 5: no conv at all - every fp16 weight image is zero-sum rounded instead (the 7x7 stem as whole rows against the
+  // image's channel means: raw pixels on a near-constant background are almost all mean)
+  if (m->splitw == 5) return 0;
+  // 3: every conv except the 3x3 conv in the middle of a BOTTLENECK block, i.e. a 3x3 conv that neither writes the
+  // trunk nor reads it (tests/archive/diagnostics/split_rules.py: its weight rounding adds the least logit error per MFMA
+  // cycle a lo-product costs).  The first 3x3 conv of a basic block (ResNet-18/34) reads the trunk and stays split:
+  // un-split it costs 1.1e-3 of probability on the class-standardised golden fixture (tests/archive/diagnostics/diverse_prec.py)
+  // (Round 3 tried splitting the last stage's inner 3x3 convs as well, tests/archive/diagnostics/split_rules.py "all-but-
+  // inner3x3(stages1-3)": +0.29 ms per forward and no gain on the class-standardised golden fixture.)
+  // EfficientNets: none.  Their error is the fp16 rounding of every stored activation, amplified layer by layer through 16-32
+  // SiLU blocks (tests/archive/diagnostics/effnet_prec.py); the weight rounding does not show beside it - goldens 1.2e-4 with
+  // hi + lo on every 1x1 conv, 2.4e-4 without, fresh images the same medians and maxima either way
+  // (tests/archive/diagnostics/effnet_calibrated.py) - while the lo products cost 7 % of the B4 forward (26.2 -> 28.2 k img/s).
+  // MobileNetV3 (Hardswish / Hardsigmoid graphs): every conv.  On a trained MobileNetV3-Large the weight rounding does show:
+  // 7.1e-4 ... 1.06e-3 worst of 256 images without the lo products, 3.4e-4 ... 5.8e-4 with them (tests/test_gpu_mobilenet.py).
+  if (m->splitw == 3 && m->effnet && !m->mobilenet) return 0;
+  if (m->splitw == 3) return L.trunk_writer || L.d.k != 3 || !L.inner3x3 ? 1 : 0;
+  return m->splitw == 1 || L.trunk_writer ? 1 : 0;
+}
+static inline float spk_fp8_scale_of(float amax) {
+  // value = byte * scale; 2x headroom over the calibration batch (e4m3 keeps its 3 mantissa bits over 15 binades,
+  // so headroom costs no precision); conversion saturates at +-448
+  return amax > 0.f ? 2.f * amax / 448.f : 1.f;
+}
+SPK_LOCAL int spk_fp8_pack(spk_model* m);
 int spk_train_join(spk_model* m);   // train.hip: the model's stream waits for the last step's deferred side-stream work
+// model.hip: the activation plan and the eval executor
 int spk_plan(spk_model* m, int n, int h, int w, bool pad = false);
-int spk_run_layer_eval(spk_model* m, Layer& L, int nb);
+SPK_LOCAL int spk_micro_batch(spk_model* m, int n);
+static inline size_t spk_image_stride_bytes(int c, int h, int w, int dtype) { return (size_t)c * h * w * (dtype == SPK_DTYPE_U8 ? 1 : 4); }
+SPK_LOCAL void spk_eval_begin(spk_model* m, int nb);   // a forward of nb images starts: nothing has run, no e4m3 shadow is valid
+int spk_run_layer_eval(spk_model* m, Layer& L, int nb, unsigned allow);   // allow: FUSE_* | EVAL_FORWARD
 int spk_forward_eval_logits(spk_model* m, const void* x, int n, int h, int w, int layout, int dtype,
                             float* logits_dev);
 int spk_read_flat(spk_model* m, const float* flat, const Param& p, float* host);

@@ -854,8 +854,8 @@ extern "C" int spk_op_mbconv_geometry(int kind, int M, int C, int HW, int S, int
   return ofail(SPK_ERR_ARG, "op_mbconv_geometry: kind 0 ... 4");
 }
 
-// ---- the MBConv EVAL kernels and the eval stems, one layer at a time: the pack and launch calls spk_commit and
-// run_conv_eval / spk_run_layer_eval (model.hip) make for a padded-channel 1x1 conv (with or without the squeeze-
+// ---- the MBConv EVAL kernels and the eval stems, one layer at a time: the pack and launch calls spk_commit
+// (model_pack.hip) and run_conv_eval / spk_run_layer_eval (model.hip) make for a padded-channel 1x1 conv (with or without the squeeze-
 // excitation gates in its operand), a squeeze-excitation layer, the 3x3/2 RGB stem and the 7x7/2 ResNet stem (with or
 // without the fused max-pool), on caller-provided fp16 buffers.  Arguments are checked before any HIP call. ----
 namespace {

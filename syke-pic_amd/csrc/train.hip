@@ -14,23 +14,9 @@
 #include <cstdlib>
 #include <cstring>
 
-static int tfail(int code, const std::string& msg) {
-  spk_set_error(msg);
-  return code;
-}
-#define HIP_TRY(expr)                                                          \
-  do {                                                                         \
-    hipError_t e_ = (expr);                                                    \
-    if (e_ != hipSuccess) return tfail(SPK_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-#define SPK_TRY(expr)            \
-  do {                           \
-    int r_ = (expr);             \
-    if (r_ != SPK_OK) return r_; \
-  } while (0)
 #define K_TRY(expr, what)                                            \
   do {                                                               \
-    if ((expr) != 0) return tfail(SPK_ERR_HIP, std::string(what) + " launch failed"); \
+    if ((expr) != 0) return spk_fail(SPK_ERR_HIP, std::string(what) + " launch failed"); \
   } while (0)
 
 struct ConvTrain {
@@ -225,7 +211,7 @@ static int plan_train(spk_model* m, int n, int h, int w) {
     const TDim& d = m->tdims[id];
     const size_t bytes = (size_t)n * d.h * d.w * d.c * (d.bf16 ? 2 : 4);
     if (bytes >= ((size_t)1 << 31))
-      return tfail(SPK_ERR_UNSUPPORTED, "training batch too large: an activation exceeds 2 GiB");
+      return spk_fail(SPK_ERR_UNSUPPORTED, "training batch too large: an activation exceeds 2 GiB");
     t->goff[id] = total;
     total += al256(bytes);
   }
@@ -396,8 +382,8 @@ static void fill_conv(ConvArgs& a, const bf16_t* x, const bf16_t* w, bf16_t* y, 
 // ---------------------------------------------------------------------------
 // -3 from spk_conv_launch: the candidate pinned by spk_op_conv_pin is not instantiated for this problem
 static int dgrad_rc(int r, const char* what) {
-  if (r == -3) return tfail(SPK_ERR_UNSUPPORTED, std::string(what) + ": the pinned candidate does not fit this problem");
-  if (r) return tfail(SPK_ERR_HIP, std::string(what) + " launch failed");
+  if (r == -3) return spk_fail(SPK_ERR_UNSUPPORTED, std::string(what) + ": the pinned candidate does not fit this problem");
+  if (r) return spk_fail(SPK_ERR_HIP, std::string(what) + " launch failed");
   return SPK_OK;
 }
 
@@ -414,8 +400,8 @@ int spk_conv_dgrad_all(const bf16_t* dy, const bf16_t* wdg, bf16_t* dx, bool acc
     }
     return dgrad_rc(spk_conv_launch(a, CONV_MODE_DGRAD, s, fuse ? &fuse->tiles : nullptr), "conv dgrad");
   }
-  if (fuse) return tfail(SPK_ERR_ARG, "the fused BatchNorm reduction needs a single-launch (stride 1) data gradient");
-  if (stride != 2) return tfail(SPK_ERR_UNSUPPORTED, "conv stride must be 1 or 2 on the training path");
+  if (fuse) return spk_fail(SPK_ERR_ARG, "the fused BatchNorm reduction needs a single-launch (stride 1) data gradient");
+  if (stride != 2) return spk_fail(SPK_ERR_UNSUPPORTED, "conv stride must be 1 or 2 on the training path");
   // one launch per output parity class; a class that no tap can reach (1x1 stride 2: three of four) is all zeros
   bool need_zero = false;
   for (int cl = 0; cl < 4; ++cl) {
@@ -804,7 +790,7 @@ static int group_backward(StepCtx& c, int i, const bf16_t* dy, int slot) {
   const Param& pw = m->params[L.p_w];
   if (c.needs[L.d.src]) {
     if (c.deferred[L.d.src] >= 0)
-      return tfail(SPK_ERR_STATE, std::string("deferred shortcut gradient cannot land in grouped conv ") + L.d.name);
+      return spk_fail(SPK_ERR_STATE, std::string("deferred shortcut gradient cannot land in grouped conv ") + L.d.name);
     K_TRY(spk_launch_group_dgrad(dy, m->P(L.p_w), (bf16_t*)t->G(L.d.src), c.has_grad[L.d.src] != 0, n, in.h, in.w, C,
                                  L.groups, L.d.stride, DT_BF16, s), "grouped conv dgrad");
     mark(m, PH_CONV_DGRAD);
@@ -833,7 +819,7 @@ static int conv_dgrad(StepCtx& c, int i, const bf16_t* dy) {
   const int pi = fuse_target(c, i);
   const int dsrc = c.deferred[L.d.src];
   if (dsrc >= 0 && pi < 0)
-    return tfail(SPK_ERR_STATE, std::string("deferred shortcut gradient of ") + m->layers[dsrc].d.name + " has no fused data gradient to land in");
+    return spk_fail(SPK_ERR_STATE, std::string("deferred shortcut gradient of ") + m->layers[dsrc].d.name + " has no fused data gradient to land in");
   BnbFuse fz;
   fz.res_src = nullptr;
   fz.res_bits = nullptr;
@@ -940,7 +926,7 @@ static int check_bn_counts(const spk_model* m, int n) {
   for (const Layer& L : m->layers) {
     const TDim& o = m->tdims[L.d.dst];
     if ((L.d.kind == SPK_OP_CONV || L.d.kind == SPK_OP_DWCONV) && (long)n * o.h * o.w < 2)
-      return tfail(SPK_ERR_ARG, std::string("Expected more than 1 value per channel when training, got input size [") +
+      return spk_fail(SPK_ERR_ARG, std::string("Expected more than 1 value per channel when training, got input size [") +
                                     std::to_string(n) + ", " + std::to_string(L.d.cout) + ", " + std::to_string(o.h) +
                                     ", " + std::to_string(o.w) + "] at " + L.d.bn);
   }
@@ -981,10 +967,10 @@ static StepCtx step_begin(spk_model* m, int n, int w) {
 // lam CE(y) + (1 - lam) CE(y2) - the loss launch is all that differs.
 static int train_step(spk_model* m, const void* x, int n, int h, int w, int layout, int dtype, const int64_t* y,
                       const int64_t* y2, float lam, float* stats, float* logits_out) {
-  if (!m || !x || !y || !stats || n < 1) return tfail(SPK_ERR_ARG, "train step: bad arguments");
-  if (dtype != SPK_DTYPE_F32 && dtype != SPK_DTYPE_U8) return tfail(SPK_ERR_ARG, "train step: dtype must be f32 or u8");
+  if (!m || !x || !y || !stats || n < 1) return spk_fail(SPK_ERR_ARG, "train step: bad arguments");
+  if (dtype != SPK_DTYPE_F32 && dtype != SPK_DTYPE_U8) return spk_fail(SPK_ERR_ARG, "train step: dtype must be f32 or u8");
   // pbuf holds the average (spk_model_ema_swap): a step would train it, and update running statistics that are not the model's
-  if (m->ema_swapped) return tfail(SPK_ERR_STATE, "train step: the moving average is swapped in (spk_model_ema_swap back first)");
+  if (m->ema_swapped) return spk_fail(SPK_ERR_STATE, "train step: the moving average is swapped in (spk_model_ema_swap back first)");
   HIP_TRY(hipSetDevice(m->device));
   SPK_TRY(ensure_state(m));
   SPK_TRY(plan_train(m, n, h, w));
@@ -1145,8 +1131,8 @@ extern "C" int spk_train_forward_backward(spk_model* m, const void* x, int n, in
 extern "C" int spk_train_forward_backward_pair(spk_model* m, const void* x, int n, int h, int w, int layout, int dtype,
                                                const int64_t* ya, const int64_t* yb, float lam, float* stats,
                                                float* logits_out) {
-  if (!m || !x || !ya || !stats || n < 1) return tfail(SPK_ERR_ARG, "train_forward_backward_pair: bad arguments");
-  if (!(lam >= 0.f && lam <= 1.f)) return tfail(SPK_ERR_ARG, "train_forward_backward_pair: lam must be in [0, 1]");
+  if (!m || !x || !ya || !stats || n < 1) return spk_fail(SPK_ERR_ARG, "train_forward_backward_pair: bad arguments");
+  if (!(lam >= 0.f && lam <= 1.f)) return spk_fail(SPK_ERR_ARG, "train_forward_backward_pair: lam must be in [0, 1]");
   // one label vector, or all the weight on the first: the step of spk_train_forward_backward, plain kernel included
   return train_step(m, x, n, h, w, layout, dtype, ya, lam == 1.f ? nullptr : yb, lam, stats, logits_out);
 }
@@ -1164,7 +1150,7 @@ int spk_train_join(spk_model* m) {
 
 extern "C" int spk_model_set_grad_ready_callback(spk_model* m, spk_grad_ready_fn cb, void* user, void* comm_stream,
                                                  int n_buckets) {
-  if (!m || (cb && (n_buckets < 1 || n_buckets > 3))) return tfail(SPK_ERR_ARG, "set_grad_ready_callback: bad arguments");
+  if (!m || (cb && (n_buckets < 1 || n_buckets > 3))) return spk_fail(SPK_ERR_ARG, "set_grad_ready_callback: bad arguments");
   HIP_TRY(hipSetDevice(m->device));
   m->grad_cb = cb;
   m->grad_cb_user = user;
@@ -1211,12 +1197,12 @@ static int grad_bucket_done(spk_model* m, int b) {
 }
 
 extern "C" int spk_optim_step(spk_model* m, const spk_optim_desc* opt) {
-  if (!m || !opt) return tfail(SPK_ERR_ARG, "optim_step: bad arguments");
+  if (!m || !opt) return spk_fail(SPK_ERR_ARG, "optim_step: bad arguments");
   if (opt->kind < SPK_OPT_SGD || opt->kind > SPK_OPT_RPROP)
-    return tfail(SPK_ERR_UNSUPPORTED,
+    return spk_fail(SPK_ERR_UNSUPPORTED,
                  "optimizer kind not supported (SGD, Adam, AdamW, RMSprop, Adagrad, Adamax, NAdam, RAdam, Adadelta, ASGD, Rprop)");
-  if (!m->train) return tfail(SPK_ERR_STATE, "optim_step before any training step");
-  if (m->ema_swapped) return tfail(SPK_ERR_STATE, "optim_step: the moving average is swapped in (spk_model_ema_swap back first)");
+  if (!m->train) return spk_fail(SPK_ERR_STATE, "optim_step before any training step");
+  if (m->ema_swapped) return spk_fail(SPK_ERR_STATE, "optim_step: the moving average is swapped in (spk_model_ema_swap back first)");
   HIP_TRY(hipSetDevice(m->device));
   TrainState* t = m->train;
   const float gscale = opt->grad_scale == 0.f ? 1.f : opt->grad_scale;
@@ -1286,7 +1272,7 @@ extern "C" int spk_optim_step(spk_model* m, const spk_optim_desc* opt) {
 }
 
 extern "C" int spk_model_grad_buffer(spk_model* m, void** dev_ptr, int64_t* numel) {
-  if (!m || !dev_ptr || !numel) return tfail(SPK_ERR_ARG, "grad_buffer: bad arguments");
+  if (!m || !dev_ptr || !numel) return spk_fail(SPK_ERR_ARG, "grad_buffer: bad arguments");
   HIP_TRY(hipSetDevice(m->device));
   SPK_TRY(ensure_state(m));
   SPK_TRY(spk_train_join(m));
@@ -1297,12 +1283,12 @@ extern "C" int spk_model_grad_buffer(spk_model* m, void** dev_ptr, int64_t* nume
 }
 
 extern "C" int spk_model_read_grad(spk_model* m, const char* key, void* host, int64_t numel) {
-  if (!m || !key || !host) return tfail(SPK_ERR_ARG, "read_grad: bad arguments");
+  if (!m || !key || !host) return spk_fail(SPK_ERR_ARG, "read_grad: bad arguments");
   auto it = m->index.find(key);
-  if (it == m->index.end()) return tfail(SPK_ERR_KEY, std::string("unknown state_dict key: ") + key);
+  if (it == m->index.end()) return spk_fail(SPK_ERR_KEY, std::string("unknown state_dict key: ") + key);
   const Param& p = m->params[it->second];
-  if (!p.trainable || p.numel != numel) return tfail(SPK_ERR_ARG, std::string("no gradient / size mismatch for ") + key);
-  if (!m->train) return tfail(SPK_ERR_STATE, "read_grad before any training step");
+  if (!p.trainable || p.numel != numel) return spk_fail(SPK_ERR_ARG, std::string("no gradient / size mismatch for ") + key);
+  if (!m->train) return spk_fail(SPK_ERR_STATE, "read_grad before any training step");
   HIP_TRY(hipSetDevice(m->device));
   SPK_TRY(spk_train_join(m));
   HIP_TRY(hipStreamSynchronize(m->stream));
@@ -1312,12 +1298,12 @@ extern "C" int spk_model_read_grad(spk_model* m, const char* key, void* host, in
 // ---- checkpointing of what a training step leaves behind beside the parameters (include/sykepic_hip.h) ----
 static int optim_state_param(spk_model* m, const char* key, int slot, const void* host, int64_t numel, const char* fn,
                              const Param** out) {
-  if (!m || !key || !host || slot < 0 || slot > 1) return tfail(SPK_ERR_ARG, std::string(fn) + ": bad arguments");
+  if (!m || !key || !host || slot < 0 || slot > 1) return spk_fail(SPK_ERR_ARG, std::string(fn) + ": bad arguments");
   auto it = m->index.find(key);
-  if (it == m->index.end()) return tfail(SPK_ERR_KEY, std::string(fn) + ": unknown state_dict key: " + key);
+  if (it == m->index.end()) return spk_fail(SPK_ERR_KEY, std::string(fn) + ": unknown state_dict key: " + key);
   const Param& p = m->params[it->second];
   if (!p.trainable || p.numel != numel)
-    return tfail(SPK_ERR_ARG, std::string(fn) + ": no gradient / size mismatch for " + key);
+    return spk_fail(SPK_ERR_ARG, std::string(fn) + ": no gradient / size mismatch for " + key);
   *out = &p;
   return SPK_OK;
 }
@@ -1346,36 +1332,36 @@ extern "C" int spk_model_optim_state_load(spk_model* m, const char* key, int slo
 }
 
 extern "C" int spk_model_param_counters_get(spk_model* m, const char* key, int64_t* step, double* mu_product) {
-  if (!m || !key || !step || !mu_product) return tfail(SPK_ERR_ARG, "model_param_counters_get: bad arguments");
+  if (!m || !key || !step || !mu_product) return spk_fail(SPK_ERR_ARG, "model_param_counters_get: bad arguments");
   auto it = m->index.find(key);
-  if (it == m->index.end()) return tfail(SPK_ERR_KEY, std::string("model_param_counters_get: unknown state_dict key: ") + key);
+  if (it == m->index.end()) return spk_fail(SPK_ERR_KEY, std::string("model_param_counters_get: unknown state_dict key: ") + key);
   const Param& p = m->params[it->second];
-  if (!p.trainable) return tfail(SPK_ERR_ARG, std::string("model_param_counters_get: ") + key + " is a buffer, not a parameter");
+  if (!p.trainable) return spk_fail(SPK_ERR_ARG, std::string("model_param_counters_get: ") + key + " is a buffer, not a parameter");
   *step = (int64_t)p.step;
   *mu_product = p.mu_product;
   return SPK_OK;
 }
 
 extern "C" int spk_model_param_counters_set(spk_model* m, const char* key, int64_t step, double mu_product) {
-  if (!m || !key || step < 0) return tfail(SPK_ERR_ARG, "model_param_counters_set: bad arguments");
+  if (!m || !key || step < 0) return spk_fail(SPK_ERR_ARG, "model_param_counters_set: bad arguments");
   auto it = m->index.find(key);
-  if (it == m->index.end()) return tfail(SPK_ERR_KEY, std::string("model_param_counters_set: unknown state_dict key: ") + key);
+  if (it == m->index.end()) return spk_fail(SPK_ERR_KEY, std::string("model_param_counters_set: unknown state_dict key: ") + key);
   Param& p = m->params[it->second];
-  if (!p.trainable) return tfail(SPK_ERR_ARG, std::string("model_param_counters_set: ") + key + " is a buffer, not a parameter");
+  if (!p.trainable) return spk_fail(SPK_ERR_ARG, std::string("model_param_counters_set: ") + key + " is a buffer, not a parameter");
   p.step = (long)step;
   p.mu_product = mu_product;
   return SPK_OK;
 }
 
 extern "C" int spk_model_train_counters_get(spk_model* m, uint64_t* steps, uint64_t* seed) {
-  if (!m || !steps || !seed) return tfail(SPK_ERR_ARG, "model_train_counters_get: bad arguments");
+  if (!m || !steps || !seed) return spk_fail(SPK_ERR_ARG, "model_train_counters_get: bad arguments");
   *steps = m->train ? (uint64_t)m->train->steps : 0;
   *seed = m->seed;
   return SPK_OK;
 }
 
 extern "C" int spk_model_train_counters_set(spk_model* m, uint64_t steps, uint64_t seed) {
-  if (!m) return tfail(SPK_ERR_ARG, "model_train_counters_set: bad arguments");
+  if (!m) return spk_fail(SPK_ERR_ARG, "model_train_counters_set: bad arguments");
   HIP_TRY(hipSetDevice(m->device));
   SPK_TRY(ensure_state(m));
   m->train->steps = (unsigned long long)steps;
@@ -1386,12 +1372,12 @@ extern "C" int spk_model_train_counters_set(spk_model* m, uint64_t steps, uint64
 // loss_fn = nn.CrossEntropyLoss(weight, label_smoothing) of the training and validation steps (train.py:127).  The
 // arguments are checked before any HIP call; (NULL, 0) frees the buffers and the steps launch ce_kernel again.
 extern "C" int spk_model_set_loss(spk_model* m, const float* class_weights, float label_smoothing) {
-  if (!m) return tfail(SPK_ERR_ARG, "model_set_loss: null model");
+  if (!m) return spk_fail(SPK_ERR_ARG, "model_set_loss: null model");
   if (!(label_smoothing >= 0.f && label_smoothing <= 1.f))
-    return tfail(SPK_ERR_ARG, "model_set_loss: label_smoothing must be in [0, 1]");
+    return spk_fail(SPK_ERR_ARG, "model_set_loss: label_smoothing must be in [0, 1]");
   for (int c = 0; class_weights && c < m->num_classes; ++c)
     if (!std::isfinite(class_weights[c]) || !(class_weights[c] > 0.f))
-      return tfail(SPK_ERR_ARG, "model_set_loss: weight of class " + std::to_string(c) + " is not a finite number above 0");
+      return spk_fail(SPK_ERR_ARG, "model_set_loss: weight of class " + std::to_string(c) + " is not a finite number above 0");
   HIP_TRY(hipSetDevice(m->device));
   HIP_TRY(hipStreamSynchronize(m->stream));   // a step still in flight reads the buffers about to change
   const bool ex = class_weights != nullptr || label_smoothing > 0.f;
@@ -1417,9 +1403,9 @@ extern "C" int spk_model_set_loss(spk_model* m, const float* class_weights, floa
 // Per-class (rows seen, rows correct) of the steps since the last reset, widened to int64.  Without a loss that counts
 // (spk_model_set_loss never called, or set back to the defaults) there is nothing to read: SPK_ERR_UNSUPPORTED.
 extern "C" int spk_model_class_counts_read(spk_model* m, int64_t* host, int reset) {
-  if (!m || !host) return tfail(SPK_ERR_ARG, "model_class_counts_read: bad arguments");
+  if (!m || !host) return spk_fail(SPK_ERR_ARG, "model_class_counts_read: bad arguments");
   if (!m->class_counts)
-    return tfail(SPK_ERR_UNSUPPORTED, "model_class_counts_read: the default loss keeps no per-class counters "
+    return spk_fail(SPK_ERR_UNSUPPORTED, "model_class_counts_read: the default loss keeps no per-class counters "
                                       "(spk_model_set_loss with weights or label smoothing does)");
   HIP_TRY(hipSetDevice(m->device));
   HIP_TRY(hipStreamSynchronize(m->stream));
@@ -1437,11 +1423,11 @@ extern "C" int spk_model_class_counts_read(spk_model* m, int64_t* host, int rese
 // float32 NCHW ([n,c,h,w]; [n,c] in the head).
 extern "C" int spk_model_read_activation_grad(spk_model* m, int t, int n, float* host, int64_t numel) {
   if (!m || !host || !m->train || !m->train->arena || t <= 0 || t >= m->n_tensors || n > m->train->cap_n)
-    return tfail(SPK_ERR_ARG, "read_activation_grad: bad arguments or no training step has run");
+    return spk_fail(SPK_ERR_ARG, "read_activation_grad: bad arguments or no training step has run");
   const TDim& d = m->tdims[t];
   const int cl = d.c_log > 0 ? d.c_log : d.c;   // the caller sees the layer's own channels, not the padding
   const size_t cnt = (size_t)n * d.h * d.w * d.c;
-  if ((int64_t)((size_t)n * d.h * d.w * cl) != numel) return tfail(SPK_ERR_ARG, "read_activation_grad: size mismatch");
+  if ((int64_t)((size_t)n * d.h * d.w * cl) != numel) return spk_fail(SPK_ERR_ARG, "read_activation_grad: size mismatch");
   HIP_TRY(hipSetDevice(m->device));
   SPK_TRY(spk_train_join(m));
   HIP_TRY(hipStreamSynchronize(m->stream));
@@ -1468,7 +1454,7 @@ extern "C" int spk_model_read_activation_grad(spk_model* m, int t, int n, float*
 extern "C" int spk_model_profile_train(spk_model* m, const void* x, int n, int h, int w, int layout,
                                        int dtype, const int64_t* y, float* stats, int iters,
                                        spk_layer_time* out, int cap) {
-  if (!m || !out || cap < PH_COUNT || iters <= 0) return tfail(SPK_ERR_ARG, "profile_train: bad arguments");
+  if (!m || !out || cap < PH_COUNT || iters <= 0) return spk_fail(SPK_ERR_ARG, "profile_train: bad arguments");
   SPK_TRY(spk_train_forward_backward(m, x, n, h, w, layout, dtype, y, stats, nullptr));  // warm-up + plan
   TrainState* t = m->train;
   std::vector<double> ms(PH_COUNT, 0.0);

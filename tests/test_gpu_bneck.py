@@ -137,6 +137,90 @@ def test_network_output_does_not_depend_on_the_form_the_blocks_run_in():
     assert set(seen) == {"64", "33"} and all(len(v) == 1 for v in seen.values()), seen
 
 
+FORM_HANDLES = {
+    "A": {"SPK_BNECK": "2", "SPK_CHAIN": "2"},                           # whole-block kernels + chained convs
+    "B": {"SPK_BNECK": "3", "SPK_CHAIN": "2", "SPK_BTAIL": "1"},       # ... 7-row blocks, + the block-tail kernel on stage 1
+    "P": {"SPK_BNECK": "0", "SPK_CHAIN": "0", "SPK_FUSE_STEM_POOL": "0"},   # every layer its own launch
+}
+
+
+@pytest.fixture(scope="module")
+def form_nets():
+    """ResNet-50 (50 classes, synthetic weights, single fp16 weight images: the default mode splits conv1 / conv3 and rules the
+    fused forms out) as three handles that differ only in the forms their layers run in, the tensor shapes of the graph for
+    2 images at 224 x 224 (one CPU oracle pass) and two inputs.  The switches are read when a handle is created."""
+    import numpy as np
+    from oracle import graph_eval
+    from sykepic_hip import arch, synth
+    from sykepic_hip.net import HipNet
+    g = arch.build_graph("resnet50", 50)
+    sd = synth.synth_state_dict(arch.param_specs(g), seed=2)
+    tsd = {k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}
+    nets = {}
+    for tag, env in FORM_HANDLES.items():
+        with pytest.MonkeyPatch.context() as mp:
+            for k, v in env.items():
+                mp.setenv(k, v)
+            net = HipNet("resnet50", 50, weights=None)
+        net.load_state_dict(tsd)
+        nets[tag] = net.eval().set_precision(split_weights=0)
+    xs = [torch.from_numpy(synth.synth_images(2, 3, 224, 224, seed=s)) for s in (11, 12)]
+    shapes = {t: tuple(v.shape) for t, v in graph_eval.run(g, tsd, xs[0]).items()}
+    return g, nets, xs, shapes
+
+
+def test_every_tensor_reads_back_the_same_whatever_form_ran(form_nets):
+    """The logits AND every tensor of the graph read back through `read_activation` - in graph order, then in reverse - are bit-
+    equal between the fused forms and the plain launches: a tensor a fused kernel never wrote is recomputed by the stand-alone
+    kernels on request, whatever was read before it.  A forward on another input afterwards gives the plain handle's logits
+    again: a read-back leaves nothing behind that changes the next forward."""
+    g, nets, xs, shapes = form_nets
+    z = {tag: net.forward(xs[0].cuda()).cpu() for tag, net in nets.items()}
+    for tag in "AB":
+        assert torch.equal(z[tag], z["P"]), (tag, float((z[tag] - z["P"]).abs().max()))
+    order = [op.dst for op in g.ops]
+    for ts in (order, order[::-1]):
+        for t in ts:
+            want = nets["P"].read_activation(t, 2, shapes[t])
+            for tag in "AB":
+                got = nets[tag].read_activation(t, 2, shapes[t])
+                assert torch.equal(got, want), (tag, t, float((got - want).abs().max()), int((got != want).sum()))
+    z = {tag: net.forward(xs[1].cuda()).cpu() for tag, net in nets.items()}
+    for tag in "AB":
+        assert torch.equal(z[tag], z["P"]), (tag, float((z[tag] - z["P"]).abs().max()))
+
+
+def test_layer_table_counts_every_flop_once(form_nets):
+    """`profile_layers`: a fused launch's row carries the FLOPs of everything it computed and the rows of the layers it absorbed
+    carry none, so the column sums to the graph's 2 n oh ow cout cin k^2 / groups over the convs and linear layers whatever forms
+    ran (integers below 2^53: exact).  ResNet-50 at 224 x 224 has 3 identity blocks with cm 128 and 5 with cm 256 for the whole-
+    block kernel, and three chain pairs (base.4.0 -> 4.1, 4.1 -> 4.2, 4.2 -> 5.0)."""
+    from sykepic_hip import arch
+    g, nets, xs, shapes = form_nets
+    want = 0
+    for op in g.ops:
+        if op.kind == arch.OP_CONV:
+            n, _, oh, ow = shapes[op.dst]
+            want += 2 * n * oh * ow * op.cout * op.cin * op.k * op.k // op.groups
+        elif op.kind == arch.OP_LINEAR:
+            want += 2 * shapes[op.dst][0] * op.cout * op.cin
+    rows = {tag: net.profile_layers(xs[0].cuda(), iters=1) for tag, net in nets.items()}
+    whole = "+conv2+conv3 (one kernel)"
+    for tag in "ABP":
+        assert all(r[2] == int(r[2]) for r in rows[tag])
+        assert sum(int(r[2]) for r in rows[tag]) == want, (tag, sum(int(r[2]) for r in rows[tag]), want)
+    for tag in "AB":
+        by_name = {r[0]: r for r in rows[tag]}
+        heads = [r[0][:-len(whole)] for r in rows[tag] if r[0].endswith(whole)]
+        assert len(heads) == 8, (tag, heads)
+        for h in heads:
+            assert h.endswith(".conv1")
+            for other in (h[:-1] + "2", h[:-1] + "3"):
+                assert by_name[other][2] == 0 and by_name[other][3] == 0, (tag, by_name[other])
+        assert sum(">" in r[0] for r in rows[tag]) == 3, (tag, [r[0] for r in rows[tag] if ">" in r[0]])
+    assert not any(r[0].endswith(whole) or ">" in r[0] for r in rows["P"]), [r[0] for r in rows["P"]]
+
+
 @pytest.mark.parametrize("flags", ["0", "4"], ids=["14-row blocks", "7-row blocks"])
 def test_blocks_that_share_and_inherit_cus(flags):
     """More blocks than the chip holds at once (7-row form: two per CU, later blocks start beside running ones): still the
