@@ -717,6 +717,25 @@ int spk_augment_batch(const unsigned char* in_dev, unsigned char* out_dev, unsig
 int spk_mix_batch(const void* in_dev, void* out_dev, int n, int h, int w, int c, int layout, int dtype,
                   int shift, float ca, float cb, int y1, int x1, int y2, int x2, void* hip_stream);
 
+/* Test-time augmentation (not in the reference, which classifies every ROI once): the symmetric views of a batch and
+ * the mean of the probabilities they give.  A view code v is in 0..7, the dihedral group of the square: bit value 4
+ * transposes H and W and is applied first, bit value 2 then reverses the rows, bit value 1 the columns - 0 identity,
+ * 1 / 2 the flips, 3 the half turn, 4 the transpose, 5 / 6 the quarter turns, 7 the anti-transpose.
+ * spk_tta_views: out_dev = [k][n] images, view-major, out[j * n + i] = T_views[j](in[i]); every output element is a
+ * copy of one input element, bit for bit (no arithmetic), one launch writes all k views and reads each input tile
+ * once.  Batches as for spk_mix_batch: SPK_LAYOUT_NHWC / SPK_DTYPE_U8 [n,h,w,c] or SPK_LAYOUT_NCHW / SPK_DTYPE_F32
+ * [n,c,h,w], c 1 or 3, any n, h, w >= 1 and any pointer alignment the element type allows.  views_host: k codes in
+ * host memory, duplicates allowed.  Out of place.  Checked before any HIP call, each SPK_ERR_ARG: a null pointer,
+ * n / h / w < 1, c not 1 or 3, another layout / dtype pair, k outside 1..8, a code outside 0..7, a transposing code
+ * with h != w, overlapping buffers.  Asynchronous on hip_stream. */
+int spk_tta_views(const void* in_dev, void* out_dev, int n, int h, int w, int c, int layout, int dtype,
+                  const int32_t* views_host, int k, void* hip_stream);
+/* p_dev = [k][numel], out_dev = [numel]: out[j] = ((...(p[0][j] + p[1][j]) + ...) + p[k-1][j]) / (float)k - float32
+ * adds in view order, then one IEEE float32 division (no reciprocal multiply, no contraction): a defined bit pattern.
+ * k in 1..8, numel >= 1, any 4-byte alignment.  Checked before any HIP call, each SPK_ERR_ARG: a null pointer, k
+ * outside 1..8, numel < 1, overlapping buffers.  Asynchronous on hip_stream. */
+int spk_tta_mean(const float* p_dev, float* out_dev, int k, int64_t numel, void* hip_stream);
+
 /* --- prediction from probabilities and thresholds ---
  * row_prediction of sykepic/compute/prediction.py:49-71 for n rows at once:
  * thresholds_dev = float[num_classes] (+inf for a class without a threshold):

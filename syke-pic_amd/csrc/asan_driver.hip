@@ -316,6 +316,37 @@ int main(int argc, char** argv) {
     EXPECT(spk_op_swap_f32(ea, ea + 7, 8, nullptr) == SPK_ERR_ARG);
     EXPECT(spk_op_swap_f32(ea, (float*)((char*)eb + 2), 4, nullptr) == SPK_ERR_ARG);
     EXPECT(spk_op_swap_f32(nullptr, eb, 8, nullptr) == SPK_ERR_ARG);
+    // ... and test-time augmentation's: null pointers, the sizes, the channel count, the batch kind, the number of views, a
+    // code outside 0..7, a transposing code on a rectangle, overlapping buffers; the mean's k, numel and overlap
+    unsigned char sq_a[2 * 4 * 4 * 3] = {0}, sq_b[8 * 2 * 4 * 4 * 3] = {0};
+    const int32_t flips[4] = {0, 1, 2, 3}, nine[9] = {0, 1, 2, 3, 4, 5, 6, 7, 0}, wrong[2] = {0, 8}, neg[1] = {-1}, tp[2] = {0, 5};
+    const int U8L = SPK_LAYOUT_NHWC, U8 = SPK_DTYPE_U8;
+    EXPECT(spk_tta_views(nullptr, sq_b, 2, 4, 4, 3, U8L, U8, flips, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_views(sq_a, nullptr, 2, 4, 4, 3, U8L, U8, flips, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_views(sq_a, sq_b, 2, 4, 4, 3, U8L, U8, nullptr, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_views(sq_a, sq_b, 0, 4, 4, 3, U8L, U8, flips, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_views(sq_a, sq_b, 2, 0, 4, 3, U8L, U8, flips, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_views(sq_a, sq_b, 2, 4, -1, 3, U8L, U8, flips, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_views(sq_a, sq_b, 2, 4, 4, 2, U8L, U8, flips, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_views(sq_a, sq_b, 2, 4, 4, 3, SPK_LAYOUT_NCHW, U8, flips, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_views(sq_a, sq_b, 2, 4, 4, 3, U8L, SPK_DTYPE_F32, flips, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_views(sq_a, sq_b, 2, 4, 4, 3, U8L, U8, flips, 0, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_views(sq_a, sq_b, 2, 4, 4, 3, U8L, U8, nine, 9, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_views(sq_a, sq_b, 2, 4, 4, 3, U8L, U8, wrong, 2, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_views(sq_a, sq_b, 2, 4, 4, 3, U8L, U8, neg, 1, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_views(sq_a, sq_b, 2, 4, 2, 3, U8L, U8, tp, 2, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_views(sq_b + 96, sq_b, 2, 4, 4, 3, U8L, U8, flips, 4, nullptr) == SPK_ERR_ARG);   // in inside out
+    EXPECT(spk_tta_views(sq_b, sq_b + 47, 1, 4, 4, 3, U8L, U8, flips, 4, nullptr) == SPK_ERR_ARG);   // out begins in in's last byte
+    EXPECT(strstr(spk_last_error(), "spk_tta_views") != nullptr);
+    float pm[8 * 4] = {0}, om[4] = {0};
+    EXPECT(spk_tta_mean(nullptr, om, 8, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_mean(pm, nullptr, 8, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_mean(pm, om, 0, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_mean(pm, om, 9, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_mean(pm, om, 8, 0, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_mean(pm, pm + 31, 8, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_tta_mean(pm + 3, pm, 7, 4, nullptr) == SPK_ERR_ARG);
+    EXPECT(strstr(spk_last_error(), "spk_tta_mean") != nullptr);
   }
 
   // ---- a small bottleneck graph: stem, pool, 1x1 / 3x3 / 1x1 + shortcut, pool, head ----

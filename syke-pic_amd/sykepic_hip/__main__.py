@@ -39,6 +39,11 @@ def build_parser():
         pp.add_argument("-b", "--batch-size", type=int, default=64, metavar="INT", help="Default is 64")
         pp.add_argument("-w", "--num-workers", type=int, default=2, metavar="INT", help="Default is 2")
         pp.add_argument("-f", "--force", action="store_true", help="Force overwrite of previous probabilities")
+        # not in the reference, which classifies every ROI once, as the camera saw it
+        pp.add_argument("--tta", choices=("none", "flip", "dihedral"), default="none",
+                        help="Test-time augmentation: average the probabilities over the 4 flipped (flip) or all 8 "
+                             "flipped and rotated (dihedral, square images only) views of every ROI; costs one forward "
+                             "per view.  Default is none")
         pp.set_defaults(func=_prob)
     # not in the reference: one-off preparation of a model directory for the calibrated single-pass mode
     cp = sub.add_parser("calibrate", description="Measure activation means for a model directory (writes act_means.pth: "

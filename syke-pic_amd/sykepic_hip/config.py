@@ -102,6 +102,15 @@ def get_model_ema(config, net):
     return ModelEma(net, tr.ema_decay, tr.ema_warmup)
 
 
+def _test_tta(s):
+    """``test_tta``: the test-time augmentation mode (tta.py) of a second report per test set, empty = none."""
+    from .tta import MODES
+    v = s.strip().lower() or "none"
+    if v not in MODES:
+        raise ValueError(f"test_tta must be one of {', '.join(MODES)}. Got: {s}")
+    return v
+
+
 def _index_prob_pairs(s):
     """``dropout = 1,0.5;2,0.3`` -> [(1, 0.5), (2, 0.3)] (list index in the head, probability)."""
     return [(int(i), float(p)) for i, p in (pair.split(",") for pair in s.split(";"))] if s else []
@@ -141,6 +150,9 @@ KEYS = {
         # exponential moving average of the weights (ema.py): validated, checkpointed and shipped as best_state.pth while the
         # raw weights keep training; decay 0: off, the run of a file without the keys
         "ema_decay": (_ema_decay, "0"), "ema_warmup": (_flag, "yes"),
+        # test-time augmentation (tta.py) of the test split(s): a second report, test_report*_tta.txt, beside the plain one;
+        # none: the run of a file without the key
+        "test_tta": (_test_tta, "none"),
     },
     "lr_warmup": {
         "use": (_flag, REQUIRED), "factor_1": (float, REQUIRED), "factor_2": (float, REQUIRED), "step_1": (int, REQUIRED),

@@ -160,6 +160,8 @@ SYMBOLS = {
     "spk_predict_rows": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_float, _P, _P, _P]),
     "spk_augment_batch": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
     "spk_mix_batch": (C.c_int, [_P, _P] + [C.c_int] * 7 + [C.c_float, C.c_float] + [C.c_int] * 4 + [_P]),
+    "spk_tta_views": (C.c_int, [_P, _P] + [C.c_int] * 6 + [C.POINTER(C.c_int32), C.c_int, _P]),
+    "spk_tta_mean": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P]),
     "spk_model_profile_infer": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.POINTER(LayerTime), C.c_int]),
     "spk_model_profile_train": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,

@@ -461,11 +461,16 @@ class HipNet:
         x = x.float().contiguous()
         return x, x.shape[0], x.shape[2], x.shape[3], lib.LAYOUT_NCHW, lib.DTYPE_F32
 
-    def forward(self, x, softmax_base=0.0):
-        """Eval-mode forward.  softmax_base <= 0: raw logits."""
+    def forward(self, x, softmax_base=0.0, out=None):
+        """Eval-mode forward.  softmax_base <= 0: raw logits.  out: the caller's contiguous float32 [n, classes] device
+        buffer, else a new tensor."""
         self._ensure_init()
         x, n, h, w, layout, dtype = self._prep(x)
-        out = torch.empty((n, self.num_classes), dtype=torch.float32, device=self.device)
+        if out is None:
+            out = torch.empty((n, self.num_classes), dtype=torch.float32, device=self.device)
+        elif not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32
+                  and tuple(out.shape) == (n, self.num_classes)):
+            raise ValueError(f"out must be a contiguous float32 [{n}, {self.num_classes}] device tensor")
         with torch.cuda.device(self.device):
             lib.check(self._lib.spk_model_set_stream(self._h, self._stream()))
             lib.check(self._lib.spk_forward_infer(self._h, C.c_void_p(x.data_ptr()), n, h, w, layout,
@@ -485,6 +490,24 @@ class HipNet:
     def probabilities(self, x, base=SOFTMAX_EXP):
         """softmax(net(x) * ln(base)) fused on the GPU (net_pass body)."""
         return self.forward(x, softmax_base=base)
+
+    def probabilities_tta(self, x, views, base=SOFTMAX_EXP):
+        """Test-time augmentation (tta.py): the mean over `views` (codes 0..7) of `probabilities` of each view of x,
+        float32 [n, classes].  One spk_tta_views launch, one eval forward of n images per view on the contiguous slices
+        of its output (the workspace of a plain batch of n), one spk_tta_mean launch: ((p_0 + p_1) + ...) / k in float32.
+        Asynchronous on the current stream.  views == (0,): `probabilities(x, base)` itself, no further launch."""
+        from . import ops, tta
+        views = tuple(int(v) for v in views)
+        if views == (0,):
+            return self.probabilities(x, base)
+        self._ensure_init()
+        x, n, h, w, _, _ = self._prep(x)
+        tta.check_shape(views, (self.graph.in_chans, h, w))
+        xv = ops.tta_views(x, views)
+        p = torch.empty((len(views), n, self.num_classes), dtype=torch.float32, device=self.device)
+        for j in range(len(views)):
+            self.forward(xv[j], softmax_base=base, out=p[j])
+        return ops.tta_mean(p)
 
     def _stats_buf(self):
         if self._stats is None:

@@ -795,6 +795,47 @@ def mix_batch(x, ca, cb, box, shift=1, out=None):
     return out
 
 
+def tta_views(x, views, out=None):
+    """spk_tta_views: the dihedral views of a batch, [k, *x.shape] view-major, out[j, i] = T_views[j](x[i]) bit for bit.
+    x: a contiguous device batch, uint8 [N,H,W,C] or float32 [N,C,H,W], C 1 or 3.  views: 1 to 8 codes in 0..7 (bit
+    value 4 transposes H and W first, 2 then reverses the rows, 1 the columns; see tta.py).  out: the caller's buffer of
+    that shape and x's dtype (it must not overlap x), else a new tensor.  One launch, enqueued on the current stream."""
+    so = lib.load()
+    dev = x.device
+    assert x.is_cuda and x.is_contiguous() and x.dim() == 4 and x.dtype in (torch.uint8, torch.float32), \
+        "contiguous uint8 [N,H,W,C] or float32 [N,C,H,W] device batch expected"
+    if x.dtype == torch.uint8:
+        n, h, w, c = x.shape
+        layout, dtype = lib.LAYOUT_NHWC, lib.DTYPE_U8
+    else:
+        n, c, h, w = x.shape
+        layout, dtype = lib.LAYOUT_NCHW, lib.DTYPE_F32
+    codes = [int(v) for v in views]
+    if out is None:
+        out = torch.empty((len(codes),) + tuple(x.shape), dtype=x.dtype, device=dev)
+    assert out.is_cuda and out.is_contiguous() and out.shape == (len(codes),) + tuple(x.shape) and out.dtype == x.dtype
+    with torch.cuda.device(dev):
+        lib.check(so.spk_tta_views(_p(x), _p(out), n, h, w, c, layout, dtype, (C.c_int32 * len(codes))(*codes), len(codes),
+                                   _stream(dev)))
+    return out
+
+
+def tta_mean(p, out=None):
+    """spk_tta_mean: p [k, ...] float32 (k in 1..8) -> the mean over the first dimension, ((p[0] + p[1]) + ...) / k in
+    float32: adds in that order, then one IEEE division.  out: the caller's float32 buffer of shape p.shape[1:] (it must
+    not overlap p), else a new tensor.  One launch, enqueued on the current stream."""
+    so = lib.load()
+    dev = p.device
+    assert p.is_cuda and p.is_contiguous() and p.dtype == torch.float32 and p.dim() >= 2, \
+        "contiguous float32 [k, ...] device tensor expected"
+    if out is None:
+        out = torch.empty(tuple(p.shape[1:]), dtype=torch.float32, device=dev)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() * p.shape[0] == p.numel()
+    with torch.cuda.device(dev):
+        lib.check(so.spk_tta_mean(_p(p), _p(out), int(p.shape[0]), int(out.numel()), _stream(dev)))
+    return out
+
+
 def maxpool(x, k, stride, pad, want_idx=False):
     """MaxPool2d on x [N,H,W,C] bf16 / fp16 (spk_op_maxpool).  want_idx: the training kernel, which also returns the
     saved taps [N,Ho,Wo,C] uint8; else the eval kernel.  Returns (y, idx or None)."""

@@ -26,8 +26,23 @@ SOFTMAX_EXP = 1.3
 FILE_SUFFIX = ".prob"
 log = logging.getLogger("prob")
 
+# `tta`: the test-time augmentation mode (tta.MODES); trailing and defaulted, so six-argument constructions stay valid
 EvalParams = namedtuple(
-    "EvalParams", ["batch_size", "num_workers", "classes", "img_shape", "transform", "device"])
+    "EvalParams", ["batch_size", "num_workers", "classes", "img_shape", "transform", "device", "tta"], defaults=("none",))
+
+
+def _views(params):
+    """The view codes of `params.tta` for `net_pass*`, None for a run without test-time augmentation."""
+    from . import tta
+    mode = getattr(params, "tta", "none")
+    return None if mode == "none" else tta.views_of(mode)
+
+
+def _probabilities(net, x, views):
+    """One batch's probabilities: the plain forward, or the mean over the views (`HipNet.probabilities_tta`)."""
+    if views is None:
+        return net.probabilities(x, SOFTMAX_EXP)
+    return net.probabilities_tta(x, views, SOFTMAX_EXP)
 
 
 def roi_number(path):
@@ -47,11 +62,12 @@ def _in_process_group():
     return td.is_available() and td.is_initialized() and td.get_world_size() > 1
 
 
-def net_pass(net, dataloader, device="cuda:0"):
+def net_pass(net, dataloader, device="cuda:0", views=None):
     """[(roi, [p_class...]), ...] sorted by ROI number.
 
     ``dataloader`` yields ``(x [B,C,H,W] float32 in [0,1], paths)``.  The
-    probabilities are softmax(logits * ln 1.3), computed on the GPU."""
+    probabilities are softmax(logits * ln 1.3), computed on the GPU.  views: view codes (tta.py) whose probabilities
+    are averaged; the auto-calibration still measures on the batch as it arrives."""
     results = []
     net.to(device)
     net.eval()
@@ -60,7 +76,7 @@ def net_pass(net, dataloader, device="cuda:0"):
         x, paths = batch[0], batch[1]
         if getattr(net, "_auto_calibration_dir", None) is not None and not _in_process_group():
             auto_calibrate(net, x)
-        probs = net.probabilities(x, SOFTMAX_EXP)  # async on the stream
+        probs = _probabilities(net, x, views)  # async on the stream
         pending.append((tuple(roi_number(p) for p in paths), probs))
     for rois, probs in pending:  # one device->host copy per batch, after all launches
         results.extend(zip(rois, probs.tolist()))
@@ -115,7 +131,7 @@ class PendingRows:
         return ProbRows(np.concatenate(self.nums), self.host.numpy()).sorted()
 
 
-def net_pass_launch(net, batches, device="cuda:0"):
+def net_pass_launch(net, batches, device="cuda:0", views=None):
     """`net_pass` for batches of (x, ROI numbers), launch half: every batch is queued on the stream, nothing is
     read back and no per-ROI Python object is built."""
     net.to(device)
@@ -124,13 +140,13 @@ def net_pass_launch(net, batches, device="cuda:0"):
     for x, numbers in batches:
         if getattr(net, "_auto_calibration_dir", None) is not None and not _in_process_group():
             auto_calibrate(net, x)
-        outs.append(net.probabilities(x, SOFTMAX_EXP))      # async on the stream
+        outs.append(_probabilities(net, x, views))          # async on the stream
         nums.append(np.asarray(numbers, dtype=np.int64))
     return PendingRows(nums, outs)
 
 
-def net_pass_arrays(net, batches, device="cuda:0"):
-    return net_pass_launch(net, batches, device).result()
+def net_pass_arrays(net, batches, device="cuda:0", views=None):
+    return net_pass_launch(net, batches, device, views).result()
 
 
 def _format_rows(rows, n_classes):
@@ -436,14 +452,14 @@ def launch_sample(sample_path, net, params, out_dir, force=False, dist=None, ahe
                     yield gs.batch(b, e, th, tw, code), gs.numbers[b:e]
             if world > 1 and getattr(net, "_auto_calibration_dir", None) is not None:
                 auto_calibrate(net, gs.batch(lo, min(hi, lo + AUTO_CALIBRATION_IMAGES), th, tw, code) if hi > lo else None, dist)
-            rows = net_pass_launch(net, gpu_batches(), params.device)
+            rows = net_pass_launch(net, gpu_batches(), params.device, _views(params))
         else:
             rois = ifcb.read_rois(sample_path.with_suffix(".adc"), sample_path.with_suffix(".roi"))
             lo, hi = dp.shard_range(len(rois), rank, world)
             items = [(f"{sample}_{num:05d}.png", _as_chans(img, params.img_shape[0])) for num, img in rois[lo:hi]]
             if world > 1 and getattr(net, "_auto_calibration_dir", None) is not None:
                 auto_calibrate(net, next(_batches(items, params.transform, AUTO_CALIBRATION_IMAGES))[0] if items else None, dist)
-            rows = net_pass(net, _batches(items, params.transform, params.batch_size), params.device)
+            rows = net_pass(net, _batches(items, params.transform, params.batch_size), params.device, _views(params))
     except Exception as e:  # noqa: BLE001 - re-raised by complete_sample on every rank
         error = e
     return sample, rows, error, csv_path
@@ -493,18 +509,23 @@ def process_images(img_paths, net, params, csv_path, force=False, dist=None):
         items = [(str(p), pngio.read_image(p, params.img_shape[0])) for p in img_paths[lo:hi]]
         if world > 1 and getattr(net, "_auto_calibration_dir", None) is not None:
             auto_calibrate(net, next(_batches(items, params.transform, AUTO_CALIBRATION_IMAGES))[0] if items else None, dist)
-        rows = net_pass(net, _batches(items, params.transform, params.batch_size), params.device)
+        rows = net_pass(net, _batches(items, params.transform, params.batch_size), params.device, _views(params))
     except Exception as e:  # noqa: BLE001 - re-raised below on every rank
         error = e
     _finish(rows, error, csv_path.name, params.classes, csv_path, dist)
 
 
 def main(sample_paths, model_dir, out_dir, batch_size=64, num_workers=2, force=False,
-         progress_bar=True, samples_as_images=False):
+         progress_bar=True, samples_as_images=False, tta="none"):
     from . import dp
+    from . import tta as tta_mod
+    views = tta_mod.views_of(tta)                   # (an unknown mode: ValueError before anything is loaded)
     dist, rank, world, local = dp.init_from_env()   # one process per GPU under torch.distributed.run
     net, classes, img_shape, eval_transform, device = prepare_model(model_dir, f"cuda:{local}")
-    params = EvalParams(batch_size, num_workers, classes, img_shape, eval_transform, device)
+    tta_mod.check_shape(views, img_shape)
+    if tta != "none":
+        log.info(f"test-time augmentation {tta}: every ROI is classified in {len(views)} views, their probabilities averaged")
+    params = EvalParams(batch_size, num_workers, classes, img_shape, eval_transform, device, tta)
     progress_bar = progress_bar and rank == 0
     try:
         from tqdm import tqdm
@@ -665,4 +686,4 @@ def call(args):
             else:
                 log.warning(f"{sp.name} is over 1G, skipping")
     return main(selected, args.model, args.out, args.batch_size, args.num_workers, args.force,
-                progress_bar=True, samples_as_images=as_images)
+                progress_bar=True, samples_as_images=as_images, tta=getattr(args, "tta", "none"))

@@ -27,6 +27,7 @@ import torch
 from . import arch, data, schedule
 from . import ema as ema_mod
 from . import loss as loss_mod
+from . import tta as tta_mod
 from .config import Settings, get_batch_mix, get_model_ema, get_network, get_transforms
 from . import dp
 from .dp import GradSync
@@ -87,6 +88,10 @@ def main(args):
         model_data.oversample(None, decay)
 
     img_shape = im.shape
+    # test-time augmentation of the test reports (tta.py): a bad mode or a shape it cannot view ends the run here, not
+    # behind the last epoch
+    test_tta = tr.test_tta
+    tta_mod.check_shape(tta_mod.views_of(test_tta), img_shape)
     train_transform, eval_transform = get_transforms(config, img_shape)
     if getattr(args, "collage", None):
         from . import plots
@@ -211,6 +216,11 @@ def main(args):
         report = test_net(net, loader, model_data.le.classes_, device, test_name=name)
         print(report)
         (model_dir / (f"test_report_{name}.txt" if name else "test_report.txt")).write_text(report)
+        if test_tta != "none":
+            # the same images again, every one classified in the mode's views: the two accuracies side by side
+            report = test_net(net, loader, model_data.le.classes_, device, test_name=name, tta=test_tta)
+            print(report)
+            (model_dir / (f"test_report_{name}_tta.txt" if name else "test_report_tta.txt")).write_text(report)
 
 
 TRAIN_STATE_FILE = "train_state.pth"
@@ -538,15 +548,21 @@ def _plot(train_accs, train_losses, val_accs, val_losses, model_dir, epoch):
         pass
 
 
-def test_net(net, dataloader, classes, device, test_name=None):
+def test_net(net, dataloader, classes, device, test_name=None, tta="none"):
+    """tta: a mode of tta.MODES; other than `none` the predictions are the arg-max of the probabilities averaged over
+    the mode's views (`HipNet.probabilities_tta`), and the first printed line names the mode."""
     net = net.to(device)
     net.eval()
-    print(f"\n----- Model Evaluation ({test_name}) -----" if test_name else "\n----- Model Evaluation -----")
+    views = tta_mod.views_of(tta)
+    title = "Model Evaluation" + (f" ({test_name})" if test_name else "")
+    if tta != "none":
+        title += f", test-time augmentation {tta}: {len(views)} views"
+    print(f"\n----- {title} -----")
     true_labels, predicted = [], []
     pending = []
     for batch in dataloader:
         x, y = batch[0], batch[1]
-        pending.append((net(x).argmax(1), y))
+        pending.append(((net(x) if tta == "none" else net.probabilities_tta(x, views)).argmax(1), y))
     for preds, y in pending:
         predicted.extend(preds.tolist())
         true_labels.extend(torch.as_tensor(y).tolist())
