@@ -408,6 +408,12 @@ int spk_op_conv_dgrad_bn_backward(const void* dy, const float* w_ohwi, void* dx,
  * spk_op_conv1x1 / spk_op_conv3x3 (cfg < 0) fail with SPK_ERR_UNSUPPORTED ("does not fit") when the flavour is not
  * instantiated for the problem's tile (configs 5 -> 4 -> 3 are still narrowed when Cout % 256 / % 128).  For tests. */
 int spk_op_conv_pin(int cfg, int dma, int wgrad_nbuf);
+/* The tuner table of the process (csrc/tune_table.h) by the tag of a tune-cache line: "conv", "pw1x1", ... and the
+ * paired siblings "conv_p", ... that the half batches of a two-stream eval forward are tuned under.  what 0: looks the
+ * key up (exact, else the nearest tuned batch), *found = 1 and vals filled, or *found = 0; what 1: stores vals for the
+ * key and appends the line to the SPK_TUNE_CACHE file; what 2: forgets every entry, the next call reads the file again
+ * (tag, key and vals are not used).  n_key / n_vals must be the tag's field counts.  No HIP call.  For tests. */
+int spk_op_tune_table(int what, const char* tag, const int* key, int n_key, int* vals, int n_vals, int* found);
 /* Conv2d weight gradient: dw [Cout][kh][kw][Cin] float32 from x [n,h,w,cin] and dy [n,ho,wo,cout]. */
 int spk_op_conv_wgrad(const void* x_dev, const void* dy_dev, float* dw_dev, int n, int h, int w, int cin, int cout,
                       int k, int stride, int pad, void* hip_stream);

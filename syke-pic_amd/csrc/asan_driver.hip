@@ -109,6 +109,26 @@ static void tuner_table_checks(const std::string& tmp, const std::string& seed_p
   EXPECT(look(TUNE_DW, {0, 65, 28, 28, 240, 5, 1}) == -1000);
   EXPECT(look(TUNE_DW, {0, 64, 28, 28, 240, 5, 2}) == -1000);
 
+  // the paired siblings: entries of their own - neither answers for the other - chosen by the thread's twin context
+  EXPECT(spk_tune_tag(TUNE_C3) == TUNE_C3 && spk_tune_tag(TUNE_WGRAD) == TUNE_WGRAD);
+  spk_twin().mode = SpkTwin::LOOKUP;
+  EXPECT(spk_tune_tag(TUNE_CONV) == TUNE_CONV_P && spk_tune_tag(TUNE_PW1) == TUNE_PW1_P && spk_tune_tag(TUNE_PW2) == TUNE_PW2_P &&
+         spk_tune_tag(TUNE_C3) == TUNE_C3_P && spk_tune_tag(TUNE_CHAIN) == TUNE_CHAIN_P && spk_tune_tag(TUNE_BNECK) == TUNE_BNECK_P &&
+         spk_tune_tag(TUNE_D3) == TUNE_D3_P && spk_tune_tag(TUNE_WGRAD) == TUNE_WGRAD && spk_tune_tag(TUNE_DW) == TUNE_DW);
+  EXPECT(look(spk_tune_tag(TUNE_C3), {1, 14, 14, 256, 256, 64}) == -1000);   // the isolated entry above is not a paired one
+  const int pk[] = {1, 14, 14, 256, 256, 128}, pv = 11, bk[] = {14, 256, 128}, bv = 1;
+  spk_tune_store(spk_tune_tag(TUNE_C3), pk, &pv, true);
+  spk_tune_store(spk_tune_tag(TUNE_BNECK), bk, &bv, true);
+  EXPECT(look(spk_tune_tag(TUNE_C3), {1, 14, 14, 256, 256, 128}) == pv && look(spk_tune_tag(TUNE_C3), {1, 14, 14, 256, 256, 129}) == pv);
+  EXPECT(look(spk_tune_tag(TUNE_BNECK), {14, 256, 128}) == bv);
+  spk_twin() = SpkTwin();
+  EXPECT(look(spk_tune_tag(TUNE_C3), {1, 14, 14, 256, 256, 128}) == b && look(TUNE_BNECK, {14, 256, 128}) == -1000);
+  for (int t = TUNE_CONV_P; t <= TUNE_D3_P; ++t) {   // a paired line is its sibling's line behind another tag
+    const TuneSchema &p = kTuneSchemas[t], &q = kTuneSchemas[t - TUNE_CONV_P <= TUNE_BNECK ? t - TUNE_CONV_P : TUNE_D3];
+    EXPECT(p.tag && q.tag && std::string(p.tag) == std::string(q.tag) + "_p");
+    EXPECT(p.n_key == q.n_key && p.n_pos == q.n_pos && p.n_val == q.n_val && p.val_min == q.val_min && p.val_max == q.val_max);
+  }
+
   // the shipped seed: loads whole, and writing every entry back through spk_tune_store gives the seed's own lines
   std::vector<TuneLine> lines = read_tune_lines(seed);
   EXPECT(lines.size() == 282);

@@ -16,7 +16,7 @@
 // couts of one pixel).  MTW (7, 8 or 10 pixel tiles per wave) is tuned per problem: the tile count decides how evenly
 // the 256 CUs are filled (14x14 x batch 256: 448 tiles of 112 pixels = 1.75 rounds).
 #include "spk_common.h"
-#include "tune_table.h"
+#include "tune_pair.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -312,8 +312,10 @@ int spk_launch_pack_c3(const float* w, bf16_t* out, int cout, int cin, int nb, h
 int spk_conv3x3_launch(const C3Args& a, hipStream_t s) {
   const int key[] = {a.nb, a.H, a.W, a.Cin, a.Cout, a.N};
   int choice;
-  if (!spk_tune_find(TUNE_C3, key, &choice)) {
+  const TuneTag tag = spk_tune_tag(TUNE_C3);
+  if (!spk_tune_find(tag, key, &choice)) {
     const bool tune = spk_autotune_on();
+    const SpkPair<C3Args> pair(a);
     float best = 1e30f;
     choice = -1;
     SpkLaunchTimer timer;
@@ -322,10 +324,12 @@ int spk_conv3x3_launch(const C3Args& a, hipStream_t s) {
       if (spk_c3_launch(a, cfg, s)) continue;
       if (!tune) { choice = cfg; break; }   // no tuning: the first configuration that launches, for this process only
       float ms = 0.f;
-      if (!timer.time(s, 3, [&] { return spk_c3_launch(a, cfg, s); }, &ms)) continue;
+      if (!timer.time(s, 3, pair.ok, [&](int i, hipStream_t st) { return spk_c3_launch(pair[i], cfg, st); }, &ms)) continue;
+      if (spk_tune_log() > 1)
+        fprintf(stderr, "[spk c3 cand] N%d %dx%d C%d->%d nb%d: cfg %d %.1f us\n", a.N, a.H, a.W, a.Cin, a.Cout, a.nb, cfg, ms * 1000.f / 3.f);
       if (ms < best) { best = ms; choice = cfg; }
     }
-    spk_tune_store(TUNE_C3, key, &choice, tune);
+    spk_tune_store(tag, key, &choice, tune);
     if (spk_tune_log())
       fprintf(stderr, "[spk tune 3x3] N%d %dx%d C%d->%d nb%d: cfg %d (%.1f us)\n", a.N, a.H, a.W, a.Cin, a.Cout, a.nb, choice,
               best * 1000.f / 3.f);

@@ -26,7 +26,7 @@
 // K order: taps 0..8, each as two 32-deep steps ascending - the implicit GEMM's order for Cin = 64, with the same
 // fp32 epilogue: the output is bit-identical to conv_igemm.hip's (tests/test_gpu_d3.py).
 #include "spk_common.h"
-#include "tune_table.h"
+#include "tune_pair.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -377,18 +377,23 @@ int spk_conv3x3_d3_launch(const ConvArgs& a, const C3Args& q, hipStream_t s) {
   if (d3_mode() == 0) return spk_conv_launch(a, CONV_MODE_GENERIC, s, nullptr);
   const int key[] = {q.H, q.W, q.res != nullptr, q.N};
   int choice = -1;
-  const bool found = spk_tune_find(TUNE_D3, key, &choice);
+  const TuneTag tag = spk_tune_tag(TUNE_D3);
+  const bool found = spk_tune_find(tag, key, &choice);
   if (d3_mode() == 2 && (!found || choice < 0)) choice = 0;
   if (!found && spk_autotune_on()) {
     SpkLaunchTimer timer;
     if (!timer.ok) return -1;
     float t_igemm = 1e30f, t_d3 = 1e30f;
     int best_d3 = -1;
+    const SpkPair<ConvArgs> pa(a);
+    const SpkPair<C3Args> pq(q);
     for (int cfg = (d3_mode() == 2 ? 0 : -1); cfg < kD3NumCfgs; ++cfg) {
-      auto run = [&]() { return cfg < 0 ? spk_conv_launch(a, CONV_MODE_GENERIC, s, nullptr) : spk_d3_launch(q, cfg, s); };
-      if (run()) continue;   // warm-up (and the implicit GEMM's own tuning); -3: does not fit
+      auto run = [&](int i, hipStream_t st) {
+        return cfg < 0 ? spk_conv_launch(pa[i], CONV_MODE_GENERIC, st, nullptr) : spk_d3_launch(pq[i], cfg, st);
+      };
+      if (run(0, s)) continue;   // warm-up (and the implicit GEMM's own tuning); -3: does not fit
       float ms = 0.f;
-      if (!timer.time(s, 3, run, &ms)) continue;
+      if (!timer.time(s, 3, pa.ok && pq.ok, run, &ms)) continue;
       if (spk_tune_log() > 1)
         fprintf(stderr, "[spk d3 cand] N%d %dx%d res%d: %s %d %.1f us\n", q.N, q.H, q.W, q.res != nullptr,
                 cfg < 0 ? "igemm" : "d3", cfg, ms * 1000.f / 3.f);
@@ -398,7 +403,7 @@ int spk_conv3x3_d3_launch(const ConvArgs& a, const C3Args& q, hipStream_t s) {
     choice = best_d3 >= 0 && t_d3 < 0.92f * t_igemm ? best_d3 : -1;
     // (SPK_D3=2 did not time the implicit GEMM: its forced winner stays in the process and is not written to the file,
     // where a default run would read it as a choice made with the margin)
-    spk_tune_store(TUNE_D3, key, &choice, d3_mode() != 2);
+    spk_tune_store(tag, key, &choice, d3_mode() != 2);
     if (spk_tune_log())
       fprintf(stderr, "[spk tune d3] N%d %dx%d res%d: %s %d (%.1f us)\n", q.N, q.H, q.W, q.res != nullptr,
               choice < 0 ? "igemm" : "d3", choice, (choice < 0 ? t_igemm : t_d3) * 1000.f / 3.f);

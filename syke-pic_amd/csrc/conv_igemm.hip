@@ -19,7 +19,7 @@
 // of tiles, N-tiles of one M-tile adjacent, so the activation tile a block
 // streams is an L2 hit for its neighbour.
 #include "spk_common.h"
-#include "tune_table.h"
+#include "tune_pair.h"
 
 namespace {
 
@@ -915,7 +915,8 @@ int spk_conv_launch(const ConvArgs& a_in, int mode, hipStream_t s, int* m_tiles_
   const int key[] = {mode, a.dt, a.splitw, a.N, a.H, a.W, a.Cin, a.Cout, a.kh, a.stride, pad_cls, a.stats != nullptr,
                      (a.res != nullptr && (const void*)a.res != (const void*)a.y) + 2 * (a.cin_s > 0) + 4 * (a.cout_s > 0) + 8 * (mode == CONV_MODE_GENERIC && a.pool_y != nullptr)};
   int win[2];   // tile config, main-loop flavour
-  if (!spk_tune_find(TUNE_CONV, key, win)) {
+  const TuneTag tag = spk_tune_tag(TUNE_CONV);   // (the forward convs of a two-stream eval forward: "conv_p", timed as pairs)
+  if (!spk_tune_find(tag, key, win)) {
     // in-place accumulation (dgrad into an existing gradient): re-running it would add twice, so the candidates
     // write to a scratch tensor and read the real one as their shortcut operand - same traffic, nothing clobbered
     bf16_t* scratch = nullptr;
@@ -934,6 +935,8 @@ int spk_conv_launch(const ConvArgs& a_in, int mode, hipStream_t s, int* m_tiles_
     float best = 1e30f;
     win[0] = pick_cfg(a.M, a.Cout);
     win[1] = 0;
+    const SpkPair<ConvArgs> pair(a);
+    const bool twin_ok = pair.ok && (mode == CONV_MODE_GENERIC || mode == CONV_MODE_STEM);
     const int cands[] = {0, 1, 2, 3, 4, 5, 6};
     for (int cfg : cands) {
       const int bn = cfg == 5 ? 256 : ((cfg == 0 || cfg == 4) ? 128 : 64);
@@ -950,7 +953,12 @@ int spk_conv_launch(const ConvArgs& a_in, int mode, hipStream_t s, int* m_tiles_
         a.dma = dma;
         if (launch_with(a, mode, cfg, s, nullptr)) continue;  // warm-up
         float ms = 0.f;
-        if (!timer.time(s, 3, [&] { return launch_with(a, mode, cfg, s, nullptr); }, &ms)) continue;
+        auto run = [&](int i, hipStream_t st) {
+          ConvArgs h = pair[i];
+          h.dma = dma;
+          return launch_with(h, mode, cfg, st, nullptr);
+        };
+        if (!timer.time(s, 3, twin_ok, run, &ms)) continue;
         if (spk_tune_log() > 1)
           fprintf(stderr, "[spk cand] %dx%d C%d->%d k%d s%d sw%d: cfg %d dma %d %.1f us\n", a.H, a.W, a.Cin, a.Cout,
                   a.kh, a.stride, a.splitw, cfg, dma, ms * 1000.f / 3.f);
@@ -962,7 +970,7 @@ int spk_conv_launch(const ConvArgs& a_in, int mode, hipStream_t s, int* m_tiles_
       (void)hipFree(scratch);
       a.y = real_y;
     }
-    spk_tune_store(TUNE_CONV, key, win, true);
+    spk_tune_store(tag, key, win, true);
     if (spk_tune_log())
       fprintf(stderr, "[spk tune] mode %d dt %d sw %d N%d %dx%d C%d->%d k%d s%d: cfg %d dma %d (%.1f us)\n", mode,
               a.dt, a.splitw, a.N, a.H, a.W, a.Cin, a.Cout, a.kh, a.stride, win[0], win[1], best * 1000.f / 3.f);

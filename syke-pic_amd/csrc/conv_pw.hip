@@ -24,7 +24,7 @@
 //    MFMAs of the others.  RING flavour (deep K): classic K-outer loop, weights register-staged through a 2-stage LDS
 //    ring, one barrier per 32-deep K step.
 #include "spk_common.h"
-#include "tune_table.h"
+#include "tune_pair.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -666,16 +666,21 @@ int spk_conv1x1_launch(const ConvArgs& a, const PwConvArgs& q, hipStream_t s) {
   if (pw_mode() == 0 || a.Cin % 64 || a.Cout % 64 || q.dt != DT_F16) return spk_conv_launch(a, CONV_MODE_GENERIC, s, nullptr);
   const int key[] = {q.nb, q.H, q.W, q.Cin, q.Cout, q.stride, q.res != nullptr, q.relu, q.N};
   int choice = -1;   // -1: implicit GEMM (also what an untuned problem runs on without tuning), else configuration id
-  if (!spk_tune_find(TUNE_PW1, key, &choice) && spk_autotune_on()) {
+  const TuneTag tag = spk_tune_tag(TUNE_PW1);
+  if (!spk_tune_find(tag, key, &choice) && spk_autotune_on()) {
     SpkLaunchTimer timer;
     if (!timer.ok) return -1;
     float best = 1e30f, t_igemm = 1e30f, t_pw = 1e30f;
     int best_pw = -1;
+    const SpkPair<ConvArgs> pa(a);
+    const SpkPair<PwConvArgs> pq(q);
     for (int cfg = (pw_mode() == 2 ? 0 : -1); cfg < kNumCfgs; ++cfg) {
-      auto run = [&]() { return cfg < 0 ? spk_conv_launch(a, CONV_MODE_GENERIC, s, nullptr) : spk_pw_launch(q, cfg, s); };
-      if (run()) continue;  // warm-up (and the implicit GEMM's own tuning); -3: configuration does not fit
+      auto run = [&](int i, hipStream_t st) {
+        return cfg < 0 ? spk_conv_launch(pa[i], CONV_MODE_GENERIC, st, nullptr) : spk_pw_launch(pq[i], cfg, st);
+      };
+      if (run(0, s)) continue;  // warm-up (and the implicit GEMM's own tuning); -3: configuration does not fit
       float ms = 0.f;
-      if (!timer.time(s, 3, run, &ms)) continue;
+      if (!timer.time(s, 3, pa.ok && pq.ok, run, &ms)) continue;
       if (spk_tune_log() > 1)
         fprintf(stderr, "[spk pw cand] %dx%d C%d->%d s%d nb%d res%d: %s %d %.1f us\n", q.H, q.W, q.Cin, q.Cout, q.stride,
                 q.nb, q.res != nullptr, cfg < 0 ? "igemm" : "pw", cfg, ms * 1000.f / 3.f);
@@ -684,7 +689,7 @@ int spk_conv1x1_launch(const ConvArgs& a, const PwConvArgs& q, hipStream_t s) {
     }
     if (best_pw >= 0 && t_pw < 0.92f * t_igemm) { choice = best_pw; best = t_pw; }
     else { choice = -1; best = t_igemm; }
-    spk_tune_store(TUNE_PW1, key, &choice, true);
+    spk_tune_store(tag, key, &choice, true);
     if (spk_tune_log())
       fprintf(stderr, "[spk tune 1x1] N%d %dx%d C%d->%d s%d nb%d res%d: %s %d (%.1f us)\n", q.N, q.H, q.W, q.Cin, q.Cout,
               q.stride, q.nb, q.res != nullptr, choice < 0 ? "igemm" : "pw", choice, best * 1000.f / 3.f);
@@ -704,7 +709,8 @@ int spk_conv1x1_dual_launch(const PwConvArgs& q, hipStream_t s) {
   if (!q.x2 || q.dt != DT_F16) return -3;
   const int key[] = {q.nb, q.H, q.W, q.Cin, q.H2, q.W2, q.Cin2, q.Cout, q.stride, q.stride2, q.N};
   int choice;
-  if (spk_tune_find(TUNE_PW2, key, &choice)) return spk_pw_launch(q, choice, s);
+  const TuneTag tag = spk_tune_tag(TUNE_PW2);
+  if (spk_tune_find(tag, key, &choice)) return spk_pw_launch(q, choice, s);
   if (!spk_autotune_on()) {
     for (int cfg : {5, 1, 0, 3, 4})   // no tuning: the first ring configuration that fits
       if (spk_pw_launch(q, cfg, s) == 0) return 0;
@@ -714,17 +720,18 @@ int spk_conv1x1_dual_launch(const PwConvArgs& q, hipStream_t s) {
   if (!timer.ok) return -1;
   float best = 1e30f;
   choice = -1;
+  const SpkPair<PwConvArgs> pq(q);
   for (int cfg = 0; cfg < kNumCfgs; ++cfg) {
     if (spk_pw_launch(q, cfg, s)) continue;
     float ms = 0.f;
-    if (!timer.time(s, 3, [&] { return spk_pw_launch(q, cfg, s); }, &ms)) continue;
+    if (!timer.time(s, 3, pq.ok, [&](int i, hipStream_t st) { return spk_pw_launch(pq[i], cfg, st); }, &ms)) continue;
     if (spk_tune_log() > 1)
       fprintf(stderr, "[spk pw2 cand] %dx%d C%d+%d->%d nb%d: pw %d %.1f us\n", q.Ho, q.Wo, q.Cin, q.Cin2, q.Cout, q.nb, cfg,
               ms * 1000.f / 3.f);
     if (ms < best) { best = ms; choice = cfg; }
   }
   if (choice < 0) return -3;   // nothing fits: nothing remembered
-  spk_tune_store(TUNE_PW2, key, &choice, true);
+  spk_tune_store(tag, key, &choice, true);
   if (spk_tune_log())
     fprintf(stderr, "[spk tune 1x1 dual] N%d %dx%d C%d+%d->%d nb%d: pw %d (%.1f us)\n", q.N, q.Ho, q.Wo, q.Cin, q.Cin2,
             q.Cout, q.nb, choice, best * 1000.f / 3.f);

@@ -124,7 +124,8 @@ struct spk_model {
   int bneck = 1;               // whole-bottleneck kernel: 1 where it is faster (rule + timing: bneck_choice), SPK_BNECK=0 never, 2 always
                                // (14-row blocks), 3 always (7-row blocks)
   bool two_streams_now = false;   // the executor is enqueueing the two halves of a batch on two streams
-  int btail = 0;               // conv2 + conv3 (+ chained conv) kernel on the stage the whole-block kernel does not take: off - it is
+  int twin_img0 = 0, twin_cnt = 0;   // ... and the first image / image count of the OTHER half (paired tuning, tune_table.h)
+  int btail = 0;              // conv2 + conv3 (+ chained conv) kernel on the stage the whole-block kernel does not take: off - it is
                                // bit-identical but no faster than the launches it replaces; SPK_BTAIL=1
   std::vector<EvalRan> ran[2]; // per layer: what the last eval forward did with it, for each of the two half-batch chains
                                // (index = spk_model::half; a single-stream forward leaves chain 1 at EF_NONE).  Cleared by spk_eval_begin

@@ -3,7 +3,7 @@
 // Public contract and the reference lines each entry point replaces:
 // include/sykepic_hip.h.
 #include "model.h"
-#include "tune_table.h"
+#include "tune_pair.h"
 
 #include <algorithm>
 #include <cmath>
@@ -174,31 +174,87 @@ static bool chain_possible(const spk_model* m, const Layer& L, unsigned allow) {
 
 static int run_conv_eval(spk_model* m, Layer& L, int nb, unsigned allow);
 
+// ---- paired tuning (tune_table.h): what the executor contributes ----
+// SpkTwin::rebase: a pointer to the first image of the half in work inside activation tensor t becomes the other half's
+// first image of t; pointers outside the activation tensors (weights, folded BatchNorm) stay; anything else has no twin
+static bool twin_rebase(void* user, const void** p) {
+  const spk_model* m = (const spk_model*)user;
+  const char* a = (const char*)m->arena;
+  const char* q = (const char*)*p;
+  if (!a || q < a || q >= a + m->arena_bytes) return true;
+  const size_t o = (size_t)(q - a);
+  if (o >= m->se_off) return false;   // scratch behind the tensors: not a per-image slice of a tensor
+  const int t = (int)(std::upper_bound(m->toff.begin(), m->toff.end(), o) - m->toff.begin()) - 1;
+  if (t < 0 || t >= m->n_tensors) return false;
+  const TDim& d = m->tdims[t];
+  const size_t img = (size_t)d.h * d.w * d.c * (d.bf16 ? 2 : 4);
+  if (o != m->toff[t] + (size_t)m->img0 * img || m->twin_img0 + m->twin_cnt > m->cap_n) return false;
+  *p = a + m->toff[t] + (size_t)m->twin_img0 * img;
+  return true;
+}
+// the twin context of half hf of a two-stream forward (mode: SpkTwin::PAIRS on the first forward of a shape, LOOKUP after)
+static void twin_set(spk_model* m, int mode, const int* off, const int* cnt, int hf) {
+  m->twin_img0 = off[1 - hf];
+  m->twin_cnt = cnt[1 - hf];
+  SpkTwin& tw = spk_twin();
+  tw.mode = mode;
+  tw.stream = m->half_stream;
+  tw.n_self = cnt[hf];
+  tw.n_twin = cnt[1 - hf];
+  tw.rebase = twin_rebase;
+  tw.user = m;
+}
+// While it lives (which = 1 only) the executor works on the other half: the candidates that run whole layers through
+// run_conv_eval take their twin's tensors, image count and stream from the handle like any other launch
+struct OnTwin {
+  spk_model* m;
+  const bool on;
+  const int img0, half;
+  const hipStream_t stream;
+  OnTwin(spk_model* m_, int which) : m(m_), on(which != 0), img0(m_->img0), half(m_->half), stream(m_->stream) {
+    if (!on) return;
+    m->img0 = m->twin_img0;
+    m->half = 1 - half;
+    m->stream = spk_twin().stream;
+  }
+  ~OnTwin() {
+    if (!on) return;
+    m->img0 = img0;
+    m->half = half;
+    m->stream = stream;
+  }
+  OnTwin(const OnTwin&) = delete;
+};
+
 // chained kernel (1) or two kernels (0)?  Timed once per problem (both give the same bits), "chain" entries of the tuner
 // table; without tuning the chained kernel, not remembered
 static int chain_choice(spk_model* m, Layer& L, const PwConvArgs& q, int nb, unsigned allow) {
   if (m->chain >= 2) return 1;
   const int key[] = {q.H, q.W, q.Cin, q.x2 ? q.Cin2 : 0, q.Coutz, q.N};
   int choice = 1;
-  if (spk_tune_find(TUNE_CHAIN, key, &choice) || !spk_autotune_on()) return choice;
+  const TuneTag tag = spk_tune_tag(TUNE_CHAIN);
+  if (spk_tune_find(tag, key, &choice) || !spk_autotune_on()) return choice;
   SpkLaunchTimer timer;
   if (!timer.ok) return choice;
   Layer& Q = m->layers[L.chain_next];
   const unsigned unchained = allow & ~(FUSE_CHAIN | EVAL_FORWARD);
-  auto two = [&]() {
-    int r = run_conv_eval(m, L, nb, unchained);
-    if (r == SPK_OK) r = run_conv_eval(m, Q, nb, unchained);
+  const SpkPair<PwConvArgs> pq(q);
+  const int nbs[2] = {nb, spk_twin().n_twin};
+  auto two = [&](int i, hipStream_t) {   // (the layers run on the handle's stream: the twin's while OnTwin lives)
+    OnTwin other(m, i);
+    int r = run_conv_eval(m, L, nbs[i], unchained);
+    if (r == SPK_OK) r = run_conv_eval(m, Q, nbs[i], unchained);
     return r;
   };
-  auto one = [&]() { return spk_pw_chain_launch(q, m->stream); };
+  auto one = [&](int i, hipStream_t st) { return spk_pw_chain_launch(pq[i], st); };
   float t_two = 0.f, t_one = 0.f;
-  const bool ok = two() == SPK_OK && one() == 0 &&   // warm-up (and the other kernels' own tuning)
-                  timer.time(m->stream, 3, two, &t_two) && timer.time(m->stream, 3, one, &t_one);
+  const bool ok = two(0, m->stream) == SPK_OK && one(0, m->stream) == 0 &&   // warm-up (and the other kernels' own tuning)
+                  timer.time(m->stream, 3, pq.ok, two, &t_two) && timer.time(m->stream, 3, pq.ok, one, &t_one);
   choice = ok && t_one < t_two ? 1 : 0;
   if (spk_tune_log())
     fprintf(stderr, "[spk tune chain] N%d %dx%d C%d+%d->256->%d: two kernels %.1f us, chained %.1f us\n", q.N, q.H, q.W, q.Cin,
             q.x2 ? q.Cin2 : 0, q.Coutz, t_two * 1000.f / 3.f, t_one * 1000.f / 3.f);
-  spk_tune_store(TUNE_CHAIN, key, &choice, true);
+  spk_tune_store(tag, key, &choice, true);
   return choice;
 }
 
@@ -233,11 +289,15 @@ static void bneck_args(spk_model* m, const Layer& L, BneckArgs& a, int nb) {
   a.x_bytes = (unsigned)((size_t)nb * in.h * in.w * in.c * 2);
 }
 
+static int bneck_choice_paired(spk_model* m, Layer& L, const BneckArgs& a, int nb, unsigned allow, int* choice);
+
 // whole-bottleneck kernel or three launches?  0: three launches, 1: blocks of 14 rows x 8 waves (one per CU), 2: blocks of
 // 7 rows x 4 waves (two per CU).  Below a quarter of the chip 0 and 2 are timed once per problem (the same bits either
 // way), "bneck" entries of the tuner table; without tuning 2, not remembered
 static int bneck_choice(spk_model* m, Layer& L, const BneckArgs& a, int nb, unsigned allow) {
   if (m->bneck >= 2) return m->bneck == 3 ? 2 : 1;
+  int paired = 0;
+  if (bneck_choice_paired(m, L, a, nb, allow, &paired)) return paired;
   const int big_blocks = a.N * (a.H / 14);
   // Two half batches on two streams: each half's large blocks take every other CU (140 KB of LDS: one block per CU), the two
   // launches start a few microseconds apart and their HBM-bound phases do not coincide (ResNet-50, batch 256: 3.33 ms; with
@@ -271,6 +331,49 @@ static int bneck_choice(spk_model* m, Layer& L, const BneckArgs& a, int nb, unsi
             a.C4, a.CM, a.C4, t_three * 1000.f / 3.f, t_one * 1000.f / 3.f);
   spk_tune_store(TUNE_BNECK, key, &choice, true);
   return choice;
+}
+
+// The same question under a twin context (a half batch of a two-stream forward, tune_table.h): no rule - the three forms
+// are timed as pairs beside the other half's launch of the same form, "bneck_p" entries.  (The rule of bneck_choice for
+// the two-stream forward, 14-row blocks from 96 large blocks on, was found by hand in whole-forward runs; this
+// measures it per problem.)  false: no twin context, or nothing tuned and no tuning now - the rules above decide.
+static int bneck_choice_paired(spk_model* m, Layer& L, const BneckArgs& a, int nb, unsigned allow, int* choice) {
+  const SpkTwin& tw = spk_twin();
+  if (tw.mode == SpkTwin::OFF) return 0;
+  const int key[] = {a.H, a.CM, a.N};
+  const TuneTag tag = spk_tune_tag(TUNE_BNECK);
+  if (spk_tune_find(tag, key, choice)) return 1;
+  if (tw.mode != SpkTwin::PAIRS || !spk_autotune_on()) return 0;
+  SpkLaunchTimer timer;
+  const SpkPair<BneckArgs> pa(a);
+  if (!timer.ok || !pa.ok) return 0;
+  const unsigned unfused = allow & ~(FUSE_BNECK | FUSE_BTAIL | EVAL_FORWARD);
+  const int nbs[2] = {nb, tw.n_twin};
+  float t[3] = {1e30f, 1e30f, 1e30f};
+  for (int form = 0; form < 3; ++form) {
+    auto run = [&](int i, hipStream_t st) {
+      if (form) {
+        BneckArgs h = pa[i];
+        if (form == 2) h.flags |= 4;
+        return spk_bneck_launch(h, st);
+      }
+      OnTwin other(m, i);   // (the layers run on the handle's stream: the twin's while it lives)
+      int r = run_conv_eval(m, L, nbs[i], unfused);
+      if (r == SPK_OK) r = run_conv_eval(m, m->layers[L.bn_c2], nbs[i], unfused);
+      if (r == SPK_OK) r = run_conv_eval(m, m->layers[L.bn_c3], nbs[i], unfused);
+      return r;
+    };
+    float ms = 0.f;
+    if (run(0, m->stream) != 0) { (void)hipGetLastError(); continue; }   // warm-up (and the other kernels' own tuning)
+    if (timer.time(m->stream, 3, true, run, &ms)) t[form] = ms;
+  }
+  *choice = (int)(std::min_element(t, t + 3) - t);
+  if (t[*choice] >= 1e30f) return 0;
+  if (spk_tune_log())
+    fprintf(stderr, "[spk tune bottleneck] N%d+%d %dx%d %d->%d->%d, pairs: three kernels %.1f us, one (14-row blocks) %.1f us, one (7-row blocks) %.1f us\n",
+            a.N, tw.n_twin, a.H, a.W, a.C4, a.CM, a.C4, t[0] * 1000.f / 3.f, t[1] * 1000.f / 3.f, t[2] * 1000.f / 3.f);
+  spk_tune_store(tag, key, choice, true);
+  return 1;
 }
 
 // ---- one function per form a conv can run in.  FORM_PASS: not this form (or its kernel has no instantiation for the
@@ -771,7 +874,14 @@ int spk_forward_eval_logits(spk_model* m, const void* x, int n, int h, int w, in
     int rc = SPK_OK;
     // one step of half hf: what a layer leaves for the next one of ITS chain (pool-partial rows, gates, e4m3 shadow, the
     // record) is indexed by spk_model::half
-    auto on_half = [&](int hf) { m->img0 = off[hf]; m->stream = str[hf]; m->half = hf; };
+    // paired tuning: the tuners reached from a half's launches time their candidates beside the other half's (the first
+    // forward, whose second stream is idle) and look their "_p" entries up (every forward); the MBConv networks keep
+    // the isolated entries
+    const int twin_mode = !spk_tune_paired_on() || m->effnet ? SpkTwin::OFF : (warm ? SpkTwin::LOOKUP : SpkTwin::PAIRS);
+    auto on_half = [&](int hf) {
+      m->img0 = off[hf]; m->stream = str[hf]; m->half = hf;
+      twin_set(m, twin_mode, off, cnt, hf);
+    };
     for (int hf = 0; hf < 2 && rc == SPK_OK; ++hf) {
       on_half(hf);
       const char* xi = (const char*)x + (size_t)off[hf] * spk_image_stride_bytes(m->in_chans, h, w, dtype);
@@ -792,6 +902,7 @@ int spk_forward_eval_logits(spk_model* m, const void* x, int n, int h, int w, in
     m->img0 = m->half = 0;
     m->stream = main_s;
     m->two_streams_now = false;
+    spk_twin() = SpkTwin();
     // (join even after an error: nothing may be left running on the second stream behind the caller's back)
     (void)hipEventRecord(m->half_join, m->half_stream);
     (void)hipStreamWaitEvent(main_s, m->half_join, 0);

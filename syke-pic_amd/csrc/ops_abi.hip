@@ -63,6 +63,24 @@ extern "C" int spk_op_conv_pin(int cfg, int dma, int wgrad_nbuf) {
   return SPK_OK;
 }
 
+// The tuner table by tag name: find (0), store and append (1), forget (2).  Host only.
+extern "C" int spk_op_tune_table(int what, const char* tag, const int* key, int n_key, int* vals, int n_vals, int* found) {
+  if (what == 2) {
+    spk_tune_reset_for_test();
+    return SPK_OK;
+  }
+  if ((what != 0 && what != 1) || !tag || !key || !vals || (what == 0 && !found))
+    return ofail(SPK_ERR_ARG, "op_tune_table: what 0 (find), 1 (store) or 2 (forget); tag, key and vals must be given");
+  int t = 0;
+  while (t < TUNE_NTAGS && !(kTuneSchemas[t].tag && !strcmp(kTuneSchemas[t].tag, tag))) ++t;
+  if (t == TUNE_NTAGS) return ofail(SPK_ERR_ARG, std::string("op_tune_table: no tuner writes the tag ") + tag);
+  if (n_key != kTuneSchemas[t].n_key || n_vals != kTuneSchemas[t].n_val)
+    return ofail(SPK_ERR_ARG, std::string("op_tune_table: wrong field counts for the tag ") + tag);
+  if (what == 1) spk_tune_store((TuneTag)t, key, vals, true);
+  else *found = spk_tune_find((TuneTag)t, key, vals) ? 1 : 0;
+  return SPK_OK;
+}
+
 extern "C" int spk_op_conv_bn_train_forward(const void* x, const float* w_ohwi, const float* gamma, const float* beta,
                                             float* running_mean, float* running_var, const void* res, void* out,
                                             void* raw, unsigned char* mask, float* mean_invstd, int n, int h, int w,

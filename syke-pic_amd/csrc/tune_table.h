@@ -10,6 +10,15 @@
 //
 // The mutex is never held while candidates run: a tuner's warm-up launch may reach the nested tuner of the kernel it
 // calls (the chain / bottleneck choosers run whole layers, the 1x1 chooser runs the implicit GEMM).
+//
+// Paired mode (SpkTwin below).  The two-stream eval forward runs every kernel beside its twin - the same layer of the
+// other half batch - so what the step pays for a candidate is the time of the PAIR, not the candidate's time alone on
+// the chip.  While the executor has a twin context set, the seven eval tuners look their problems up under "<tag>_p"
+// entries of their own (a miss is tuned, never answered from the isolated entry) and time each candidate as `reps`
+// pairs: the candidate on the caller's stream, the same candidate on the other half's slices of the same tensors on the
+// twin stream, forked and joined with events.  SPK_TUNE_PAIRED=0: no twin context is ever set, isolated tuning
+// everywhere.  Forwards on one stream, batches below 64, the per-layer profile, the single-operator hooks, training
+// and the MBConv networks never set one and keep the isolated entries.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -28,7 +37,9 @@ constexpr int kD3NumCfgs = 6;    // configurations of spk_d3_launch (conv_d3.hip
 // One line of the file is "<tag> <n_key ints> <n_val ints>".  n_pos is the position of the batch size N among the key
 // fields (-1: the key has none and matches exactly only); values outside [val_min, val_max] are dropped on load.
 struct TuneSchema { const char* tag; int n_key, n_pos, n_val, val_min, val_max; };
-enum TuneTag { TUNE_CONV, TUNE_PW1, TUNE_PW2, TUNE_C3, TUNE_CHAIN, TUNE_BNECK, TUNE_WGRAD, TUNE_DW, TUNE_D3, TUNE_NTAGS };
+enum TuneTag { TUNE_CONV, TUNE_PW1, TUNE_PW2, TUNE_C3, TUNE_CHAIN, TUNE_BNECK, TUNE_WGRAD, TUNE_DW, TUNE_D3,
+               // the paired siblings of the seven eval tuners (spk_tune_tag below): same key and values, timed beside a twin
+               TUNE_CONV_P, TUNE_PW1_P, TUNE_PW2_P, TUNE_C3_P, TUNE_CHAIN_P, TUNE_BNECK_P, TUNE_D3_P, TUNE_NTAGS };
 constexpr TuneSchema kTuneSchemas[TUNE_NTAGS] = {
     // mode dt splitw N H W Cin Cout k stride pad_cls stats operands -> tile config, main-loop flavour
     {"conv", 13, 3, 2, INT_MIN, INT_MAX},
@@ -40,6 +51,13 @@ constexpr TuneSchema kTuneSchemas[TUNE_NTAGS] = {
     {"wgrad", 8, -1, 1, INT_MIN, INT_MAX},    // M Cin Cout k stride stem splits tile -> pipeline stages
     {nullptr, 7, -1, 1, 0, 1},                // depthwise (never in the file): et N H W C k stride -> 0 gather, 1 LDS ring
     {"d3", 4, 3, 1, -1, kD3NumCfgs - 1},      // H W res N -> -1 implicit GEMM, else configuration of the direct 64 -> 64 3x3 kernel
+    {"conv_p", 13, 3, 2, INT_MIN, INT_MAX},   // the fields of the line without "_p"; N is the half batch the entry was timed for
+    {"pw1x1_p", 9, 8, 1, -1, kPwNumCfgs - 1},
+    {"pw2_p", 11, 10, 1, 0, kPwNumCfgs - 1},
+    {"c3_p", 6, 5, 1, -1, kC3NumCfgs - 1},
+    {"chain_p", 6, 5, 1, 0, 1},
+    {"bneck_p", 3, 2, 1, 0, 2},
+    {"d3_p", 4, 3, 1, -1, kD3NumCfgs - 1},
 };
 
 // nullptr: no file (SPK_TUNE_CACHE unset, empty or "off")
@@ -56,6 +74,45 @@ inline int spk_tune_log() {
   static const int v = getenv("SPK_TUNE_LOG") ? (atoi(getenv("SPK_TUNE_LOG")) > 1 ? atoi(getenv("SPK_TUNE_LOG")) : 1) : 0;
   return v;
 }
+
+inline bool spk_tune_paired_on() {
+  static const bool v = !getenv("SPK_TUNE_PAIRED") || atoi(getenv("SPK_TUNE_PAIRED")) != 0;
+  return v;
+}
+
+// The twin context of the calling thread, set by the eval executor around the launches of one half batch and nowhere
+// else.  PAIRS: the first forward of a shape - both halves run in order on the caller's stream, `stream` is idle, a
+// tuner times pairs.  LOOKUP: the halves are live on their two streams (or a pair is being timed): the paired entries
+// are looked up, nothing is launched beside anything.
+struct SpkTwin {
+  enum Mode { OFF = 0, PAIRS = 1, LOOKUP = 2 };
+  int mode = OFF;
+  hipStream_t stream = nullptr;   // where the twin's launches go
+  int n_self = 0, n_twin = 0;     // images of this half and of the other one
+  // *p points at this half's first image of an activation tensor (or outside the activations: weights, folded
+  // BatchNorm): makes it the other half's first image of the same tensor; false: neither
+  bool (*rebase)(void* user, const void** p) = nullptr;
+  void* user = nullptr;
+};
+inline SpkTwin& spk_twin() {
+  static thread_local SpkTwin t;
+  return t;
+}
+// the tag a tuner site works with: its own, or the paired sibling while a twin context is set
+inline TuneTag spk_tune_tag(TuneTag t) {
+  if (spk_twin().mode == SpkTwin::OFF) return t;
+  switch (t) {
+    case TUNE_CONV: return TUNE_CONV_P;
+    case TUNE_PW1: return TUNE_PW1_P;
+    case TUNE_PW2: return TUNE_PW2_P;
+    case TUNE_C3: return TUNE_C3_P;
+    case TUNE_CHAIN: return TUNE_CHAIN_P;
+    case TUNE_BNECK: return TUNE_BNECK_P;
+    case TUNE_D3: return TUNE_D3_P;
+    default: return t;
+  }
+}
+inline bool spk_tune_tag_is_paired(TuneTag t) { return t >= TUNE_CONV_P && t <= TUNE_D3_P; }
 
 namespace spk_tune_detail {
 constexpr int kMaxKey = 13, kMaxVal = 2, kLineBuf = 512;
@@ -161,11 +218,14 @@ inline void spk_tune_store(TuneTag t, const int* key, const int* val, bool persi
   for (int i = 0; i < sc.n_val; ++i) v[i] = val[i];
   T.map[make_key(t, key)] = v;
   const char* path = persist && sc.tag ? spk_tune_cache_path() : nullptr;
-  if (!path) return;
+  const bool say = spk_tune_log() && spk_tune_tag_is_paired(t);   // (the sites' own log lines do not name the tag)
+  if (!path && !say) return;
   char line[kLineBuf];
   int n = snprintf(line, sizeof line, "%s", sc.tag);
   for (int i = 0; i < sc.n_key; ++i) n += snprintf(line + n, sizeof line - n, " %d", key[i]);
   for (int i = 0; i < sc.n_val; ++i) n += snprintf(line + n, sizeof line - n, " %d", val[i]);
+  if (say) fprintf(stderr, "[spk tune paired] %s\n", line);
+  if (!path) return;
   if (FILE* f = fopen(path, "a")) {
     fprintf(f, "%s\n", line);
     fclose(f);
@@ -186,9 +246,10 @@ struct SpkLaunchTimer {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   const bool ok;   // false: the events could not be created
   SpkLaunchTimer() : ok(hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {}
+  hipEvent_t fork = nullptr, join = nullptr;   // paired timing only, created on first use
   ~SpkLaunchTimer() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
+    for (hipEvent_t e : {e0, e1, fork, join})
+      if (e) (void)hipEventDestroy(e);
   }
   SpkLaunchTimer(const SpkLaunchTimer&) = delete;
   template <class F>
@@ -197,5 +258,38 @@ struct SpkLaunchTimer {
     for (int r = 0; r < reps; ++r) (void)run();
     (void)hipEventRecord(e1, s);
     return hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(ms, e0, e1) == hipSuccess;
+  }
+  // The eval tuners' form: run(0, s) launches the candidate for the problem in hand, run(1, twin stream) the same
+  // candidate for its twin (twin_ok: the site has the twin's arguments, SpkPair in tune_pair.h).  In a PAIRS context the
+  // time is that of `reps` pairs - s forks the twin stream, both run their launches back to back, s waits for the
+  // twin - and a candidate that does not launch for the twin is no candidate; otherwise the time of run(0, s) alone.
+  // While the pair runs the context is LOOKUP: a launch that reaches another tuner finds what that tuner's own (paired)
+  // warm-up stored and starts no pairs of its own.
+  template <class F>
+  bool time(hipStream_t s, int reps, bool twin_ok, F run, float* ms) {
+    SpkTwin& tw = spk_twin();
+    if (tw.mode != SpkTwin::PAIRS || !twin_ok || !tw.stream || tw.stream == s)
+      return time(s, reps, [&] { return run(0, s); }, ms);
+    if (!fork && (hipEventCreateWithFlags(&fork, hipEventDisableTiming) != hipSuccess ||
+                  hipEventCreateWithFlags(&join, hipEventDisableTiming) != hipSuccess))
+      return false;
+    tw.mode = SpkTwin::LOOKUP;
+    const hipStream_t ts = tw.stream;
+    auto fork_twin = [&] { return hipEventRecord(fork, s) == hipSuccess && hipStreamWaitEvent(ts, fork, 0) == hipSuccess; };
+    auto join_twin = [&] { return hipEventRecord(join, ts) == hipSuccess && hipStreamWaitEvent(s, join, 0) == hipSuccess; };
+    // the twin's warm-up, outside the timed span (the site has warmed the candidate itself)
+    bool ok = fork_twin() && run(1, ts) == 0;
+    ok = join_twin() && ok;
+    (void)hipEventRecord(e0, s);
+    ok = ok && fork_twin();
+    for (int r = 0; r < reps && ok; ++r) {
+      (void)run(0, s);
+      ok = run(1, ts) == 0;
+    }
+    // (join whatever happened: nothing may be left running on the twin stream behind the caller's back)
+    ok = join_twin() && ok;
+    (void)hipEventRecord(e1, s);
+    tw.mode = SpkTwin::PAIRS;
+    return hipEventSynchronize(e1) == hipSuccess && ok && hipEventElapsedTime(ms, e0, e1) == hipSuccess;
   }
 };

@@ -124,6 +124,7 @@ SYMBOLS = {
     "spk_op_conv_group_dgrad": (C.c_int, [_P, _P, _P] + [C.c_int] * 7 + [_P]),
     "spk_op_conv_group_wgrad": (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [_P]),
     "spk_op_conv_pin": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "spk_op_tune_table": (C.c_int, [C.c_int, C.c_char_p, _P, C.c_int, _P, C.c_int, _P]),
     "spk_op_pw_fp8": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_float, C.c_float, _P]),
     "spk_op_dwconv": (C.c_int, [_P, _P, _P, _P, _P, _P] + [C.c_int] * 8 + [_P]),
@@ -195,20 +196,24 @@ def _default_tune_cache():
         if os.access(d, os.W_OK):
             path = os.path.join(d, f"tune-{st.st_size:x}-{int(st.st_mtime):x}.txt")
             os.environ["SPK_TUNE_CACHE"] = path
-            seed_tune_cache(path)
+            seed_tune_cache(path, extra=(TUNE_SEED_PAIRED,))
     except OSError:
         pass   # no writable cache directory: tune per process
 
 
 TUNE_SEED = Path(__file__).resolve().parent / "tune_seed_gfx950.txt"
+# the "<tag>_p" winners of the two-stream forwards' half batches, timed as pairs (csrc/tune_table.h): a file of its own
+TUNE_SEED_PAIRED = Path(__file__).resolve().parent / "tune_seed_gfx950_paired.txt"
 
 
-def seed_tune_cache(path, seed=None):
+def seed_tune_cache(path, seed=None, extra=()):
     """A tuning cache that does not exist yet starts as a copy of the winners measured on one MI355X for the shapes of
     the shipped benchmarks (`tune_seed_gfx950.txt`: comment lines are skipped by the loaders): the first `sykepic prob`
     of a fresh installation then times nothing for those shapes; every other problem is tuned on first use and appended,
     as before.  Every candidate of a problem computes the same values, so a seed can only cost speed on a machine that
-    would have chosen differently.  `SPK_TUNE_SEED=0` starts from an empty cache.  Returns True when it wrote the file."""
+    would have chosen differently.  `SPK_TUNE_SEED=0` starts from an empty cache.  `extra`: further seed files appended
+    behind the seed (the default cache of a process gets the paired winners this way).  Returns True when it wrote the
+    file."""
     import os
     seed = Path(seed) if seed is not None else TUNE_SEED
     if os.environ.get("SPK_TUNE_SEED", "1").strip().lower() in ("0", "off", "no") or os.path.exists(path) or not seed.is_file():
@@ -217,6 +222,9 @@ def seed_tune_cache(path, seed=None):
     try:
         with open(tmp, "w") as f:
             f.write(seed.read_text())
+            for more in extra:
+                if Path(more).is_file():
+                    f.write(Path(more).read_text())
         os.replace(tmp, path)      # atomic: ranks of one job race for the same file, any winner is complete
         return True
     except OSError:
