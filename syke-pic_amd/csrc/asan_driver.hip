@@ -1,7 +1,8 @@
 // Host-side sanitizer driver (the reference has no native code, so no sanitizer story; this
 // library has ~9 k lines of it).  Built by `build.sh asan` with -fsanitize=address,undefined on the HOST pass of every
 // translation unit and run on the CPU (tests/test_abi.py): it walks the host logic that does not need a GPU - handle
-// creation and its error paths, the parameter table, spk_last_error, and the tuner table (tune_table.h: one parser for
+// creation and its error paths, the parameter table, spk_last_error, the graph analysis, the eval executor's cursor
+// addressing and twin rebase (on addresses only), and the tuner table (tune_table.h: one parser for
 // the tags of the tune-cache file, the nearest-batch rule, the appended lines) - so that heap overflows,
 // use-after-free and undefined behaviour there abort the run.  With no GPU every HIP call fails and the error paths
 // are what runs; on a GPU box the same binary works on real (small) buffers.  argv[1]: the shipped tuning seed
@@ -276,11 +277,64 @@ static void graph_checks() {
   }
 }
 
+// ---- the half-batch cursor and the twin rebase of the eval executor (model.h, model.hip): addresses in a host buffer
+// that stands for the arena - nothing is dereferenced, no HIP call ----
+static void cursor_checks() {
+  spk_model m;
+  std::vector<char> arena(1024);
+  char* const a = arena.data();
+  m.arena = a;
+  m.arena_bytes = arena.size();
+  m.cap_n = 5;
+  m.n_tensors = 3;
+  m.tdims = {{2, 2, 4, true}, {1, 3, 8, true}, {1, 1, 10, false}};
+  const size_t img[3] = {2 * 2 * 4 * 2, 1 * 3 * 8 * 2, 1 * 1 * 10 * 4};   // bytes per image: two 2-byte tensors, one 4-byte
+  m.toff = {0, 256, 512};
+  m.se_off = 768;
+  m.se_stride = 6;
+  const EvalCursor ch[2] = {{0, 0, 2, nullptr}, {1, 2, 3, nullptr}};      // five images as halves of 2 + 3
+  EvalTwin tw[2] = {{&m, 0, 2, 3, false}, {&m, 2, 0, 2, false}};
+  for (int t = 0; t < 3; ++t)
+    for (int hf = 0; hf < 2; ++hf) {
+      EXPECT((char*)m.TI(ch[hf], t) == a + m.toff[t] + ch[hf].img0 * img[t]);
+      // this half's first image of the tensor becomes the twin's first image, in both directions
+      const void* p = m.TI(ch[hf], t);
+      EXPECT(spk_twin_rebase(&tw[hf], &p) && p == m.TI(ch[1 - hf], t));
+      // any other image of the tensor has no twin
+      const void* inner = (char*)m.TI(ch[hf], t) + img[t];
+      p = inner;
+      EXPECT(!spk_twin_rebase(&tw[hf], &p) && p == inner);
+    }
+  EXPECT((char*)m.TI8(ch[1], 1) == a + m.toff[1] + 2 * img[1] / 2);
+  EXPECT(m.SE(ch[0]) == (float*)(a + m.se_off) && m.SE(ch[1]) == (float*)(a + m.se_off) + 2 * m.se_stride);
+  for (int hf = 0; hf < 2; ++hf) {
+    // a pointer outside the arena (weights, folded BatchNorm) stays as it is
+    const void* outside[2] = {&m, a + arena.size()};
+    for (const void* o : outside) {
+      const void* p = o;
+      EXPECT(spk_twin_rebase(&tw[hf], &p) && p == o);
+    }
+    // the scratch at and behind se_off is no per-image slice of a tensor
+    const void* scratch[3] = {a + m.se_off, m.SE(ch[hf]) + 1, a + arena.size() - 1};
+    for (const void* o : scratch) {
+      const void* p = o;
+      EXPECT(!spk_twin_rebase(&tw[hf], &p) && p == o);
+    }
+  }
+  // a twin whose images would pass the plan's capacity
+  EvalTwin past = {&m, 0, 2, 4, false};
+  const void* p = m.T(0);
+  EXPECT(!spk_twin_rebase(&past, &p) && p == m.T(0));
+  past.twin_n = 3;
+  EXPECT(spk_twin_rebase(&past, &p) && p == m.TI(ch[1], 0));
+}
+
 int main(int argc, char** argv) {
   int ndev = 0;
   const bool gpu = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
   printf("asan_driver: %d GPU(s)\n", gpu ? ndev : 0);
   graph_checks();
+  cursor_checks();
 
   // ---- argument errors ----
   spk_model* m = nullptr;

@@ -56,7 +56,7 @@ struct Layer {
   int chained_by = -1;            // that conv: index of the block-closing conv
   // eval, single-weight modes: a whole identity bottleneck block - conv1 1x1 -> conv2 3x3 -> conv3 1x1 + shortcut, ReLU behind
   // each BatchNorm - as ONE kernel (conv_bneck.hip): the two mid tensors are never written.  (Or conv2's launch also
-  // computes conv3 + shortcut (+ the chained conv): conv_btail_kernel.)  Which form ran: spk_model::ran
+  // computes conv3 + shortcut (+ the chained conv): conv_btail_kernel.)  Which form ran: EvalCarry::ran
   int bn_c2 = -1, bn_c3 = -1;     // the block's conv1: indices of its conv2 / conv3, or -1
   int bn_head = -1;               // conv2 / conv3 of such a block: index of its conv1
   size_t mu_off = 0;              // generic convs: offset of this layer's cin input-channel means in spk_model::act_mean
@@ -81,7 +81,7 @@ struct Layer {
   bool pooled_by_stem = false;  // that max-pool layer
 };
 
-// What the eval forward did with one layer (spk_model::ran) - the ONE place that says which launch computed a layer and
+// What the eval forward did with one layer (EvalCarry::ran) - the ONE place that says which launch computed a layer and
 // whether its output tensor is in the arena; the cases, one by one: DESIGN.md section 1.  form: EF_OWN plus what else its
 // launch did, or EF_INSIDE the launch of layer `by` (EF_NONE: has not run in this forward); wrote: the output tensor was
 // written.  A layer that finds itself EF_INSIDE when its turn comes has nothing left to do.
@@ -89,8 +89,20 @@ enum EvalForm : uint8_t { EF_NONE = 0, EF_OWN = 1, EF_POOL = 2, EF_DUAL = 4, EF_
 struct EvalRan { uint8_t form = EF_NONE; bool wrote = false; int by = -1; };
 // The fusions a call of the executor may use, and whether the call is the forward itself.  The tuners time their "two
 // kernels" / "three launches" alternatives with the fusion under test (and EVAL_FORWARD) taken out, a read-back recomputes
-// with 0: only the forward consults and writes spk_model::ran.
+// with 0: only the forward consults and writes EvalCarry::ran.
 enum : unsigned { FUSE_POOL = 1, FUSE_DUAL = 2, FUSE_CHAIN = 4, FUSE_BNECK = 8, FUSE_BTAIL = 16, FUSE_GATE = 32, FUSE_ALL = 63, EVAL_FORWARD = 64 };
+
+// which images of the planned batch a call of the executor works on, and where its launches go
+struct EvalCursor { int half = 0, img0 = 0, n = 0; hipStream_t stream = nullptr; };
+// what one layer leaves for the next one of ITS chain, and what the chain's forward did with each layer
+struct EvalCarry {
+  int dw_chunks = 0;            // pool-partial rows per image the depthwise layer that ran last wrote
+  const float* gate = nullptr;  // gates of the squeeze-excitation op that ran last (consumed by the project conv)
+  int gate_stride = 0;
+  int shadow_t = -1;            // fp8 mode: tensor id whose e4m3 copy the last project conv left (-1: none valid)
+  int shadow_stride = 0;        // ... and its row stride in bytes
+  std::vector<EvalRan> ran;     // per layer: what the last eval forward did with it.  Cleared by spk_eval_begin
+};
 
 struct TrainState;
 
@@ -123,12 +135,10 @@ struct spk_model {
   int chain = 1;               // conv3 -> next conv1 chaining: 1 where it is faster (timed once per problem), SPK_CHAIN=0 never, 2 always
   int bneck = 1;               // whole-bottleneck kernel: 1 where it is faster (rule + timing: bneck_choice), SPK_BNECK=0 never, 2 always
                                // (14-row blocks), 3 always (7-row blocks)
-  bool two_streams_now = false;   // the executor is enqueueing the two halves of a batch on two streams
-  int twin_img0 = 0, twin_cnt = 0;   // ... and the first image / image count of the OTHER half (paired tuning, tune_table.h)
   int btail = 0;              // conv2 + conv3 (+ chained conv) kernel on the stage the whole-block kernel does not take: off - it is
                                // bit-identical but no faster than the launches it replaces; SPK_BTAIL=1
-  std::vector<EvalRan> ran[2]; // per layer: what the last eval forward did with it, for each of the two half-batch chains
-                               // (index = spk_model::half; a single-stream forward leaves chain 1 at EF_NONE).  Cleared by spk_eval_begin
+  EvalCarry carry[2];          // the two half-batch chains of the eval forward (index = EvalCursor::half; a single-stream
+                               // forward leaves chain 1's record at EF_NONE)
   bool effnet = false;         // EfficientNet graph (widths that are not multiples of 64, depthwise / SE / SiLU ops): its
                                // TRAINING plan pads every activation tensor to a multiple of 64 channels (train_effnet.hip)
   bool mobilenet = false;      // MobileNetV3 arithmetic (a Hardswish layer or a ReLU / Hardsigmoid squeeze-excitation gate):
@@ -177,13 +187,6 @@ struct spk_model {
   size_t fp8_shadow_img = 0;            // bytes per image of the shadow: the largest h * w * stride of any shadowed tensor; a chunk
                                         // [img0, ...) starts at img0 * fp8_shadow_img in every block (disjoint slices per half-batch)
                                         // (0: this forward leaves no copy)
-  // state one layer leaves for the next, per half-batch chain of the two-stream forward (index = spk_model::half)
-  int half = 0;                      // which of the two chains the executor is enqueueing (0: the caller's stream)
-  int dw_chunks_h[2] = {0, 0};       // pool-partial rows per image the depthwise layer that ran last wrote
-  const float* gate_h[2] = {nullptr, nullptr};   // gates of the squeeze-excitation op that ran last (consumed by the project conv)
-  int gate_stride_h[2] = {0, 0};
-  int shadow_t_h[2] = {-1, -1};      // fp8 mode: tensor id whose e4m3 copy the last project conv left (-1: none valid)
-  int shadow_stride_h[2] = {0, 0};   // ... and its row stride in bytes
   size_t se_stride = 0;              // floats of squeeze-excitation scratch per image (the halves use disjoint slices)
   std::vector<float> t_fp8_scale;    // per tensor: 0 = 16-bit storage, else value = byte * scale
 
@@ -205,23 +208,22 @@ struct spk_model {
   float bn_eps = 1e-5f, bn_momentum = 0.1f;   // BatchNorm2d(eps, momentum) of the graph (spk_model_set_bn)
   TrainState* train = nullptr;
 
-  int img0 = 0;                 // first image of the chunk the eval executor is working on (prefix micro-batching)
   bool fuse_stem_pool = true;   // eval: stem conv + max-pool in one kernel (SPK_FUSE_STEM_POOL=0 turns it off)
   int last_eval_nb = 0;         // images of the last eval micro-batch (read_activation recomputes a tensor it did not write)
   float* P(int pi) const { return pbuf + params[pi].off; }
   void* T(int t) const { return (char*)arena + toff[t]; }
-  // tensor t from image img0 on
-  void* TI(int t) const {
+  // tensor t from the cursor's first image on
+  void* TI(const EvalCursor& c, int t) const {
     const TDim& d = tdims[t];
-    return (char*)arena + toff[t] + (size_t)img0 * d.h * d.w * d.c * (d.bf16 ? 2 : 4);
+    return (char*)arena + toff[t] + (size_t)c.img0 * d.h * d.w * d.c * (d.bf16 ? 2 : 4);
   }
   // ... when it holds e4m3 bytes (fp8 mode: one byte per element in a slot sized for two)
-  void* TI8(int t) const {
+  void* TI8(const EvalCursor& c, int t) const {
     const TDim& d = tdims[t];
-    return (char*)arena + toff[t] + (size_t)img0 * d.h * d.w * d.c;
+    return (char*)arena + toff[t] + (size_t)c.img0 * d.h * d.w * d.c;
   }
-  // squeeze-excitation scratch of the chunk in work
-  float* SE() const { return (float*)((char*)arena + se_off) + (size_t)img0 * se_stride; }
+  // squeeze-excitation scratch of the cursor's images
+  float* SE(const EvalCursor& c) const { return (float*)((char*)arena + se_off) + (size_t)c.img0 * se_stride; }
   void* TLo(int t) const { return toff_lo[t] ? (char*)arena + toff_lo[t] : nullptr; }
 };
 
@@ -285,7 +287,14 @@ int spk_plan(spk_model* m, int n, int h, int w, bool pad = false);
 SPK_LOCAL int spk_micro_batch(spk_model* m, int n);
 static inline size_t spk_image_stride_bytes(int c, int h, int w, int dtype) { return (size_t)c * h * w * (dtype == SPK_DTYPE_U8 ? 1 : 4); }
 SPK_LOCAL void spk_eval_begin(spk_model* m, int nb);   // a forward of nb images starts: nothing has run, no e4m3 shadow is valid
-int spk_run_layer_eval(spk_model* m, Layer& L, int nb, unsigned allow);   // allow: FUSE_* | EVAL_FORWARD
+int spk_run_layer_eval(spk_model* m, Layer& L, const EvalCursor& c, unsigned allow);   // allow: FUSE_* | EVAL_FORWARD
+// SpkTwin::user of the eval executor (tune_table.h): what a half's launches know of the other half, set with the cursor
+struct EvalTwin {
+  const spk_model* m;
+  int img0, twin_img0, twin_n;   // this half's first image; the other half's first image and image count
+  bool two_streams;              // the halves are live on two streams (not the first forward of a shape, which tunes on one)
+};
+SPK_LOCAL bool spk_twin_rebase(void* user, const void** p);   // SpkTwin::rebase of the eval executor (user: an EvalTwin)
 int spk_forward_eval_logits(spk_model* m, const void* x, int n, int h, int w, int layout, int dtype,
                             float* logits_dev);
 int spk_read_flat(spk_model* m, const float* flat, const Param& p, float* host);

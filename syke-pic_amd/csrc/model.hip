@@ -118,17 +118,19 @@ int spk_micro_batch(spk_model* m, int n) {
 // ---------------------------------------------------------------------------
 // eval-mode forward of images [i0, i0+nb) into logits rows [i0, i0+nb)
 // ---------------------------------------------------------------------------
-// The record (spk_model::ran, model.h): written by the forward only - a tuner's timing run or a read-back's recompute
+// The record (EvalCarry::ran, model.h): written by the forward only - a tuner's timing run or a read-back's recompute
 // passes `allow` without EVAL_FORWARD and neither consults nor changes it.
-static void note(spk_model* m, unsigned allow, int li, unsigned form, bool wrote, int by = -1) {
-  if (allow & EVAL_FORWARD) m->ran[m->half][li] = {(uint8_t)form, wrote, by};
+static void note(spk_model* m, const EvalCursor& c, unsigned allow, int li, unsigned form, bool wrote, int by = -1) {
+  if (allow & EVAL_FORWARD) m->carry[c.half].ran[li] = {(uint8_t)form, wrote, by};
 }
 static int index_of(const spk_model* m, const Layer& L) { return (int)(&L - m->layers.data()); }
 
 void spk_eval_begin(spk_model* m, int nb) {
   m->last_eval_nb = nb;
-  m->shadow_t_h[0] = m->shadow_t_h[1] = -1;
-  for (std::vector<EvalRan>& r : m->ran) r.assign(m->layers.size(), EvalRan());
+  for (EvalCarry& k : m->carry) {
+    k.shadow_t = -1;
+    k.ran.assign(m->layers.size(), EvalRan());
+  }
 }
 
 // eval: does the stem kernel also compute the max-pool that follows it?  (not with the rounding-remainder tensors of
@@ -172,13 +174,14 @@ static bool chain_possible(const spk_model* m, const Layer& L, unsigned allow) {
   return true;
 }
 
-static int run_conv_eval(spk_model* m, Layer& L, int nb, unsigned allow);
+static int run_conv_eval(spk_model* m, Layer& L, const EvalCursor& c, unsigned allow);
 
 // ---- paired tuning (tune_table.h): what the executor contributes ----
 // SpkTwin::rebase: a pointer to the first image of the half in work inside activation tensor t becomes the other half's
 // first image of t; pointers outside the activation tensors (weights, folded BatchNorm) stay; anything else has no twin
-static bool twin_rebase(void* user, const void** p) {
-  const spk_model* m = (const spk_model*)user;
+bool spk_twin_rebase(void* user, const void** p) {
+  const EvalTwin& tw = *(const EvalTwin*)user;
+  const spk_model* m = tw.m;
   const char* a = (const char*)m->arena;
   const char* q = (const char*)*p;
   if (!a || q < a || q >= a + m->arena_bytes) return true;
@@ -188,47 +191,33 @@ static bool twin_rebase(void* user, const void** p) {
   if (t < 0 || t >= m->n_tensors) return false;
   const TDim& d = m->tdims[t];
   const size_t img = (size_t)d.h * d.w * d.c * (d.bf16 ? 2 : 4);
-  if (o != m->toff[t] + (size_t)m->img0 * img || m->twin_img0 + m->twin_cnt > m->cap_n) return false;
-  *p = a + m->toff[t] + (size_t)m->twin_img0 * img;
+  if (o != m->toff[t] + (size_t)tw.img0 * img || tw.twin_img0 + tw.twin_n > m->cap_n) return false;
+  *p = a + m->toff[t] + (size_t)tw.twin_img0 * img;
   return true;
 }
-// the twin context of half hf of a two-stream forward (mode: SpkTwin::PAIRS on the first forward of a shape, LOOKUP after)
-static void twin_set(spk_model* m, int mode, const int* off, const int* cnt, int hf) {
-  m->twin_img0 = off[1 - hf];
-  m->twin_cnt = cnt[1 - hf];
-  SpkTwin& tw = spk_twin();
-  tw.mode = mode;
-  tw.stream = m->half_stream;
-  tw.n_self = cnt[hf];
-  tw.n_twin = cnt[1 - hf];
-  tw.rebase = twin_rebase;
-  tw.user = m;
+// the twin context of the calling thread as the executor set it, or null; and the other half's cursor (PAIRS: its stream is idle)
+static const EvalTwin* eval_twin() { return spk_twin().rebase == spk_twin_rebase ? (const EvalTwin*)spk_twin().user : nullptr; }
+static EvalCursor twin_cursor(const EvalCursor& c) {
+  const EvalTwin* tw = eval_twin();
+  return tw ? EvalCursor{1 - c.half, tw->twin_img0, tw->twin_n, spk_twin().stream} : c;
 }
-// While it lives (which = 1 only) the executor works on the other half: the candidates that run whole layers through
-// run_conv_eval take their twin's tensors, image count and stream from the handle like any other launch
-struct OnTwin {
-  spk_model* m;
-  const bool on;
-  const int img0, half;
-  const hipStream_t stream;
-  OnTwin(spk_model* m_, int which) : m(m_), on(which != 0), img0(m_->img0), half(m_->half), stream(m_->stream) {
-    if (!on) return;
-    m->img0 = m->twin_img0;
-    m->half = 1 - half;
-    m->stream = spk_twin().stream;
-  }
-  ~OnTwin() {
-    if (!on) return;
-    m->img0 = img0;
-    m->half = half;
-    m->stream = stream;
-  }
-  OnTwin(const OnTwin&) = delete;
-};
+
+// the unfused forms the choosers below time, as whole layers (and with them the other kernels' own tuning)
+static int two_kernels(spk_model* m, Layer& L, const EvalCursor& c, unsigned allow) {
+  allow &= ~(FUSE_CHAIN | EVAL_FORWARD);
+  SPK_TRY(run_conv_eval(m, L, c, allow));
+  return run_conv_eval(m, m->layers[L.chain_next], c, allow);
+}
+static int three_launches(spk_model* m, Layer& L, const EvalCursor& c, unsigned allow) {
+  allow &= ~(FUSE_BNECK | FUSE_BTAIL | EVAL_FORWARD);
+  SPK_TRY(run_conv_eval(m, L, c, allow));
+  SPK_TRY(run_conv_eval(m, m->layers[L.bn_c2], c, allow));
+  return run_conv_eval(m, m->layers[L.bn_c3], c, allow);
+}
 
 // chained kernel (1) or two kernels (0)?  Timed once per problem (both give the same bits), "chain" entries of the tuner
 // table; without tuning the chained kernel, not remembered
-static int chain_choice(spk_model* m, Layer& L, const PwConvArgs& q, int nb, unsigned allow) {
+static int chain_choice(spk_model* m, Layer& L, const PwConvArgs& q, const EvalCursor& c, unsigned allow) {
   if (m->chain >= 2) return 1;
   const int key[] = {q.H, q.W, q.Cin, q.x2 ? q.Cin2 : 0, q.Coutz, q.N};
   int choice = 1;
@@ -236,20 +225,13 @@ static int chain_choice(spk_model* m, Layer& L, const PwConvArgs& q, int nb, uns
   if (spk_tune_find(tag, key, &choice) || !spk_autotune_on()) return choice;
   SpkLaunchTimer timer;
   if (!timer.ok) return choice;
-  Layer& Q = m->layers[L.chain_next];
-  const unsigned unchained = allow & ~(FUSE_CHAIN | EVAL_FORWARD);
   const SpkPair<PwConvArgs> pq(q);
-  const int nbs[2] = {nb, spk_twin().n_twin};
-  auto two = [&](int i, hipStream_t) {   // (the layers run on the handle's stream: the twin's while OnTwin lives)
-    OnTwin other(m, i);
-    int r = run_conv_eval(m, L, nbs[i], unchained);
-    if (r == SPK_OK) r = run_conv_eval(m, Q, nbs[i], unchained);
-    return r;
-  };
+  const EvalCursor cs[2] = {c, twin_cursor(c)};
+  auto two = [&](int i, hipStream_t) { return two_kernels(m, L, cs[i], allow); };   // (each on its cursor's stream)
   auto one = [&](int i, hipStream_t st) { return spk_pw_chain_launch(pq[i], st); };
   float t_two = 0.f, t_one = 0.f;
-  const bool ok = two(0, m->stream) == SPK_OK && one(0, m->stream) == 0 &&   // warm-up (and the other kernels' own tuning)
-                  timer.time(m->stream, 3, pq.ok, two, &t_two) && timer.time(m->stream, 3, pq.ok, one, &t_one);
+  const bool ok = two(0, c.stream) == SPK_OK && one(0, c.stream) == 0 &&   // warm-up (and the other kernels' own tuning)
+                  timer.time(c.stream, 3, pq.ok, two, &t_two) && timer.time(c.stream, 3, pq.ok, one, &t_one);
   choice = ok && t_one < t_two ? 1 : 0;
   if (spk_tune_log())
     fprintf(stderr, "[spk tune chain] N%d %dx%d C%d+%d->256->%d: two kernels %.1f us, chained %.1f us\n", q.N, q.H, q.W, q.Cin,
@@ -259,50 +241,50 @@ static int chain_choice(spk_model* m, Layer& L, const PwConvArgs& q, int nb, uns
 }
 
 // fills the chained conv's fields of q; false: shapes the kernel does not cover
-static bool chain_args(spk_model* m, const Layer& L, PwConvArgs& q, int nb) {
+static bool chain_args(spk_model* m, const Layer& L, PwConvArgs& q, const EvalCursor& c) {
   const Layer& Q = m->layers[L.chain_next];
   const TDim& zo = m->tdims[Q.d.dst];
   const TDim& o = m->tdims[L.d.dst];
   if (zo.h != o.h || zo.w != o.w || zo.c != Q.d.cout || Q.d.cin != L.d.cout) return false;
   q.wpz = m->wpack + Q.wpw_off;
-  q.z = (bf16_t*)m->TI(Q.d.dst);
+  q.z = (bf16_t*)m->TI(c, Q.d.dst);
   q.scalez = m->scale_bias + Q.sb_off;
   q.shiftz = q.scalez + Q.cout_p;
   q.Coutz = Q.d.cout;
   q.reluz = Q.d.relu;
-  q.z_bytes = (unsigned)((size_t)nb * zo.h * zo.w * zo.c * 2);
+  q.z_bytes = (unsigned)((size_t)c.n * zo.h * zo.w * zo.c * 2);
   return true;
 }
 
-static void bneck_args(spk_model* m, const Layer& L, BneckArgs& a, int nb) {
+static void bneck_args(spk_model* m, const Layer& L, BneckArgs& a, const EvalCursor& c) {
   const Layer& L2 = m->layers[L.bn_c2];
   const Layer& L3 = m->layers[L.bn_c3];
   const TDim& in = m->tdims[L.d.src];
   memset(&a, 0, sizeof a);
-  a.x = (const bf16_t*)m->TI(L.d.src);
-  a.y = (bf16_t*)m->TI(L3.d.dst);
+  a.x = (const bf16_t*)m->TI(c, L.d.src);
+  a.y = (bf16_t*)m->TI(c, L3.d.dst);
   a.w1 = m->wpack + L.wpw_off; a.w2 = m->wpack + L2.wpw_off; a.w3 = m->wpack + L3.wpw_off;
   a.s1 = m->scale_bias + L.sb_off; a.b1 = a.s1 + L.cout_p;
   a.s2 = m->scale_bias + L2.sb_off; a.b2 = a.s2 + L2.cout_p;
   a.s3 = m->scale_bias + L3.sb_off; a.b3 = a.s3 + L3.cout_p;
-  a.N = nb; a.H = in.h; a.W = in.w; a.C4 = L.d.cin; a.CM = L.d.cout;
-  a.x_bytes = (unsigned)((size_t)nb * in.h * in.w * in.c * 2);
+  a.N = c.n; a.H = in.h; a.W = in.w; a.C4 = L.d.cin; a.CM = L.d.cout;
+  a.x_bytes = (unsigned)((size_t)c.n * in.h * in.w * in.c * 2);
 }
 
-static int bneck_choice_paired(spk_model* m, Layer& L, const BneckArgs& a, int nb, unsigned allow, int* choice);
+static int bneck_choice_paired(spk_model* m, Layer& L, const BneckArgs& a, const EvalCursor& c, unsigned allow, int* choice);
 
 // whole-bottleneck kernel or three launches?  0: three launches, 1: blocks of 14 rows x 8 waves (one per CU), 2: blocks of
 // 7 rows x 4 waves (two per CU).  Below a quarter of the chip 0 and 2 are timed once per problem (the same bits either
 // way), "bneck" entries of the tuner table; without tuning 2, not remembered
-static int bneck_choice(spk_model* m, Layer& L, const BneckArgs& a, int nb, unsigned allow) {
+static int bneck_choice(spk_model* m, Layer& L, const BneckArgs& a, const EvalCursor& c, unsigned allow) {
   if (m->bneck >= 2) return m->bneck == 3 ? 2 : 1;
   int paired = 0;
-  if (bneck_choice_paired(m, L, a, nb, allow, &paired)) return paired;
+  if (bneck_choice_paired(m, L, a, c, allow, &paired)) return paired;
   const int big_blocks = a.N * (a.H / 14);
   // Two half batches on two streams: each half's large blocks take every other CU (140 KB of LDS: one block per CU), the two
   // launches start a few microseconds apart and their HBM-bound phases do not coincide (ResNet-50, batch 256: 3.33 ms; with
   // the small blocks, which share CUs across the halves and run in step, 3.41).
-  if (m->two_streams_now && big_blocks >= 96) return 1;
+  if (eval_twin() && eval_twin()->two_streams && big_blocks >= 96) return 1;
   // One launch alone on the chip: the small blocks when the large ones would leave CUs idle or run every CU in step
   // (isolated, 14 x 14: 256 images 123 -> 114 us, 128 images 96 -> 67 us, 64 images 89 -> 57 us; 28 x 28: 197 -> 189, 87 -> 79,
   // 65 -> 51 us); below a quarter of the chip the three launches are timed against them.
@@ -314,17 +296,11 @@ static int bneck_choice(spk_model* m, Layer& L, const BneckArgs& a, int nb, unsi
   if (!timer.ok) return choice;
   BneckArgs as = a;
   as.flags |= 4;
-  const unsigned unfused = allow & ~(FUSE_BNECK | FUSE_BTAIL | EVAL_FORWARD);
-  auto three = [&]() {
-    int r = run_conv_eval(m, L, nb, unfused);
-    if (r == SPK_OK) r = run_conv_eval(m, m->layers[L.bn_c2], nb, unfused);
-    if (r == SPK_OK) r = run_conv_eval(m, m->layers[L.bn_c3], nb, unfused);
-    return r;
-  };
-  auto one = [&]() { return spk_bneck_launch(as, m->stream); };
+  auto three = [&]() { return three_launches(m, L, c, allow); };
+  auto one = [&]() { return spk_bneck_launch(as, c.stream); };
   float t_three = 0.f, t_one = 0.f;
   const bool ok = three() == SPK_OK && one() == 0 &&   // warm-up (and the other kernels' own tuning)
-                  timer.time(m->stream, 3, three, &t_three) && timer.time(m->stream, 3, one, &t_one);
+                  timer.time(c.stream, 3, three, &t_three) && timer.time(c.stream, 3, one, &t_one);
   choice = ok && t_one < t_three ? 2 : 0;
   if (spk_tune_log())
     fprintf(stderr, "[spk tune bottleneck] N%d %dx%d %d->%d->%d: three kernels %.1f us, one (7-row blocks) %.1f us\n", a.N, a.H, a.W,
@@ -337,7 +313,7 @@ static int bneck_choice(spk_model* m, Layer& L, const BneckArgs& a, int nb, unsi
 // are timed as pairs beside the other half's launch of the same form, "bneck_p" entries.  (The rule of bneck_choice for
 // the two-stream forward, 14-row blocks from 96 large blocks on, was found by hand in whole-forward runs; this
 // measures it per problem.)  false: no twin context, or nothing tuned and no tuning now - the rules above decide.
-static int bneck_choice_paired(spk_model* m, Layer& L, const BneckArgs& a, int nb, unsigned allow, int* choice) {
+static int bneck_choice_paired(spk_model* m, Layer& L, const BneckArgs& a, const EvalCursor& c, unsigned allow, int* choice) {
   const SpkTwin& tw = spk_twin();
   if (tw.mode == SpkTwin::OFF) return 0;
   const int key[] = {a.H, a.CM, a.N};
@@ -347,8 +323,7 @@ static int bneck_choice_paired(spk_model* m, Layer& L, const BneckArgs& a, int n
   SpkLaunchTimer timer;
   const SpkPair<BneckArgs> pa(a);
   if (!timer.ok || !pa.ok) return 0;
-  const unsigned unfused = allow & ~(FUSE_BNECK | FUSE_BTAIL | EVAL_FORWARD);
-  const int nbs[2] = {nb, tw.n_twin};
+  const EvalCursor cs[2] = {c, twin_cursor(c)};
   float t[3] = {1e30f, 1e30f, 1e30f};
   for (int form = 0; form < 3; ++form) {
     auto run = [&](int i, hipStream_t st) {
@@ -357,15 +332,11 @@ static int bneck_choice_paired(spk_model* m, Layer& L, const BneckArgs& a, int n
         if (form == 2) h.flags |= 4;
         return spk_bneck_launch(h, st);
       }
-      OnTwin other(m, i);   // (the layers run on the handle's stream: the twin's while it lives)
-      int r = run_conv_eval(m, L, nbs[i], unfused);
-      if (r == SPK_OK) r = run_conv_eval(m, m->layers[L.bn_c2], nbs[i], unfused);
-      if (r == SPK_OK) r = run_conv_eval(m, m->layers[L.bn_c3], nbs[i], unfused);
-      return r;
+      return three_launches(m, L, cs[i], allow);   // (on its cursor's stream)
     };
     float ms = 0.f;
-    if (run(0, m->stream) != 0) { (void)hipGetLastError(); continue; }   // warm-up (and the other kernels' own tuning)
-    if (timer.time(m->stream, 3, true, run, &ms)) t[form] = ms;
+    if (run(0, c.stream) != 0) { (void)hipGetLastError(); continue; }   // warm-up (and the other kernels' own tuning)
+    if (timer.time(c.stream, 3, true, run, &ms)) t[form] = ms;
   }
   *choice = (int)(std::min_element(t, t + 3) - t);
   if (t[*choice] >= 1e30f) return 0;
@@ -381,105 +352,105 @@ static int bneck_choice_paired(spk_model* m, Layer& L, const BneckArgs& a, int n
 enum { FORM_PASS = 1 };
 
 // conv2 (L) + conv3 + shortcut of an identity bottleneck (+ the next block's first conv): conv_btail_kernel
-static int conv_block_tail(spk_model* m, Layer& L, int nb, unsigned allow) {
+static int conv_block_tail(spk_model* m, Layer& L, const EvalCursor& c, unsigned allow) {
   if (!btail_possible(m, L, allow)) return FORM_PASS;
   const Layer& H = m->layers[L.bn_head];
   const Layer& L3 = m->layers[H.bn_c3];
   BneckArgs ba;
-  bneck_args(m, H, ba, nb);   // (the block's input is conv3's shortcut operand; w1 is not used)
-  ba.y1 = (const bf16_t*)m->TI(L.d.src);
+  bneck_args(m, H, ba, c);   // (the block's input is conv3's shortcut operand; w1 is not used)
+  ba.y1 = (const bf16_t*)m->TI(c, L.d.src);
   bool chained = false;
   if (chain_possible(m, L3, allow)) {   // the next block's first conv from the output tile in registers, as conv_pw.hip's chained flavour
     PwConvArgs qc;
     memset(&qc, 0, sizeof qc);
-    if (chain_args(m, L3, qc, nb)) {
+    if (chain_args(m, L3, qc, c)) {
       ba.wz = qc.wpz; ba.z = qc.z; ba.sz = qc.scalez; ba.bz = qc.shiftz; ba.Coutz = qc.Coutz; ba.z_bytes = qc.z_bytes;
       chained = qc.reluz == 1;
       if (!chained) ba.wz = nullptr;
     }
   }
-  int r = spk_btail_launch(ba, m->stream);
+  int r = spk_btail_launch(ba, c.stream);
   if (r == -3 && chained) {      // (no instantiation with this chained width: without it)
     ba.wz = nullptr;
     chained = false;
-    r = spk_btail_launch(ba, m->stream);
+    r = spk_btail_launch(ba, c.stream);
   }
   if (r != 0) {
     (void)hipGetLastError();
     return FORM_PASS;
   }
   const int li = index_of(m, L);
-  note(m, allow, li, EF_OWN | EF_BTAIL | (chained ? EF_CHAIN : 0), false);   // y2 was not written
-  note(m, allow, H.bn_c3, EF_INSIDE, true, li);
-  if (chained) note(m, allow, L3.chain_next, EF_INSIDE, true, li);
+  note(m, c, allow, li, EF_OWN | EF_BTAIL | (chained ? EF_CHAIN : 0), false);   // y2 was not written
+  note(m, c, allow, H.bn_c3, EF_INSIDE, true, li);
+  if (chained) note(m, c, allow, L3.chain_next, EF_INSIDE, true, li);
   return SPK_OK;
 }
 
 // the whole identity bottleneck whose first conv is L: conv_bneck.hip
-static int conv_whole_block(spk_model* m, Layer& L, int nb, unsigned allow) {
+static int conv_whole_block(spk_model* m, Layer& L, const EvalCursor& c, unsigned allow) {
   if (!bneck_possible(m, L, allow)) return FORM_PASS;
   BneckArgs ba;
-  bneck_args(m, L, ba, nb);
-  const int form = bneck_choice(m, L, ba, nb, allow);
+  bneck_args(m, L, ba, c);
+  const int form = bneck_choice(m, L, ba, c, allow);
   if (!form) return FORM_PASS;
   if (form == 2) ba.flags |= 4;
-  if (spk_bneck_launch(ba, m->stream) != 0) {
+  if (spk_bneck_launch(ba, c.stream) != 0) {
     (void)hipGetLastError();               // (no instantiation after all, or the launch was refused: three launches)
     return FORM_PASS;
   }
   const int li = index_of(m, L);
-  note(m, allow, li, EF_OWN | EF_BNECK, false);          // y1 was not written,
-  note(m, allow, L.bn_c2, EF_INSIDE, false, li);         // nor y2;
-  note(m, allow, L.bn_c3, EF_INSIDE, true, li);          // conv3's output was
+  note(m, c, allow, li, EF_OWN | EF_BNECK, false);          // y1 was not written,
+  note(m, c, allow, L.bn_c2, EF_INSIDE, false, li);         // nor y2;
+  note(m, c, allow, L.bn_c3, EF_INSIDE, true, li);          // conv3's output was
   return SPK_OK;
 }
 
-static int conv_stem3(spk_model* m, const Layer& L, int nb) {
+static int conv_stem3(spk_model* m, const Layer& L, const EvalCursor& c) {
   const TDim& in = m->tdims[L.d.src];
   const TDim& o = m->tdims[L.d.dst];
   const float* sc = m->scale_bias + L.sb_off;
-  if (spk_launch_stem3x3((const bf16_t*)m->TI(L.d.src), m->dwpack + L.wpack_off, sc, sc + L.cout_p,
-                         (bf16_t*)m->TI(L.d.dst), nb, in.h, in.w, in.w, o.h, o.w, L.d.cout, L.cout_p, L.d.relu,
-                         m->infer_dt, m->stream))
+  if (spk_launch_stem3x3((const bf16_t*)m->TI(c, L.d.src), m->dwpack + L.wpack_off, sc, sc + L.cout_p,
+                         (bf16_t*)m->TI(c, L.d.dst), c.n, in.h, in.w, in.w, o.h, o.w, L.d.cout, L.cout_p, L.d.relu,
+                         m->infer_dt, c.stream))
     return spk_fail(SPK_ERR_HIP, std::string("stem launch failed for ") + L.d.name);
   return SPK_OK;
 }
 
-static int conv_grouped(spk_model* m, const Layer& L, int nb) {
+static int conv_grouped(spk_model* m, const Layer& L, const EvalCursor& c) {
   const TDim& in = m->tdims[L.d.src];
   const float* sc = m->scale_bias + L.sb_off;
-  if (spk_launch_group_fwd((const bf16_t*)m->TI(L.d.src), m->P(L.p_w), sc, sc + L.cout_p, (bf16_t*)m->TI(L.d.dst), nb,
-                           in.h, in.w, L.d.cin, L.groups, L.d.stride, L.d.relu, m->infer_dt, m->stream))
+  if (spk_launch_group_fwd((const bf16_t*)m->TI(c, L.d.src), m->P(L.p_w), sc, sc + L.cout_p, (bf16_t*)m->TI(c, L.d.dst), c.n,
+                           in.h, in.w, L.d.cin, L.groups, L.d.stride, L.d.relu, m->infer_dt, c.stream))
     return spk_fail(SPK_ERR_HIP, std::string("grouped conv launch failed for ") + L.d.name);
   return SPK_OK;
 }
 
 // the implicit GEMM's arguments: what every dense form below starts from
-static void conv_args(spk_model* m, const Layer& L, int nb, ConvArgs& a) {
+static void conv_args(spk_model* m, const Layer& L, const EvalCursor& c, ConvArgs& a) {
   const TDim& in = m->tdims[L.d.src];
   const TDim& o = m->tdims[L.d.dst];
   memset(&a, 0, sizeof a);
   a.cfg = a.dma = -1;
   a.cls_ph = a.cls_pw = -1;
-  a.x = (const bf16_t*)m->TI(L.d.src);
+  a.x = (const bf16_t*)m->TI(c, L.d.src);
   a.w = m->wpack + L.wpack_off;
-  a.y = (bf16_t*)m->TI(L.d.dst);
-  a.res = L.d.res >= 0 ? (const bf16_t*)m->TI(L.d.res) : nullptr;
+  a.y = (bf16_t*)m->TI(c, L.d.dst);
+  a.res = L.d.res >= 0 ? (const bf16_t*)m->TI(c, L.d.res) : nullptr;
   a.res_lo = L.d.res >= 0 ? (const bf16_t*)m->TLo(L.d.res) : nullptr;
   a.y_lo = (bf16_t*)m->TLo(L.d.dst);
   a.scale = m->scale_bias + L.sb_off;
   a.bias = a.scale + L.cout_p;
-  a.N = nb; a.H = in.h; a.W = in.w; a.Cin = L.mode == CONV_MODE_GENERIC ? L.cin_p : in.c;
+  a.N = c.n; a.H = in.h; a.W = in.w; a.Cin = L.mode == CONV_MODE_GENERIC ? L.cin_p : in.c;
   a.Ho = o.h; a.Wo = o.w; a.Cout = L.cout_p;
   a.cin_s = in.c != a.Cin ? in.c : 0;       // EfficientNet: tensors are not padded, the GEMM is
   a.cout_s = o.c != a.Cout ? o.c : 0;
   a.kh = a.kw = L.d.k; a.stride = L.d.stride; a.pad = L.d.pad;
-  a.M = nb * o.h * o.w;
+  a.M = c.n * o.h * o.w;
   a.K = L.kpad;
   a.relu = L.d.relu;
   a.dt = m->infer_dt;
   a.splitw = layer_split(m, L);
-  a.x_bytes = (unsigned)((size_t)nb * in.h * in.w * in.c * 2);
+  a.x_bytes = (unsigned)((size_t)c.n * in.h * in.w * in.c * 2);
   a.w_bytes = (unsigned)((size_t)L.cout_p * L.kpad * 2 * (a.splitw ? 2 : 1));
 }
 
@@ -507,13 +478,13 @@ static C3Args c3_args(const ConvArgs& a, const bf16_t* wp, int nbw) {
 }
 
 // the chained flavour of the block-closing conv's launch q: true when it ran - the next block's first conv is done
-static bool conv_chained(spk_model* m, Layer& L, const PwConvArgs& q, int nb, unsigned allow) {
+static bool conv_chained(spk_model* m, Layer& L, const PwConvArgs& q, const EvalCursor& c, unsigned allow) {
   if (!chain_possible(m, L, allow)) return false;
   PwConvArgs qc = q;
-  if (chain_args(m, L, qc, nb) && chain_choice(m, L, qc, nb, allow) == 1 && spk_pw_chain_launch(qc, m->stream) == 0) {
+  if (chain_args(m, L, qc, c) && chain_choice(m, L, qc, c, allow) == 1 && spk_pw_chain_launch(qc, c.stream) == 0) {
     const int li = index_of(m, L);
-    note(m, allow, li, EF_OWN | EF_CHAIN | (q.x2 ? EF_DUAL : 0), true);
-    note(m, allow, L.chain_next, EF_INSIDE, true, li);
+    note(m, c, allow, li, EF_OWN | EF_CHAIN | (q.x2 ? EF_DUAL : 0), true);
+    note(m, c, allow, L.chain_next, EF_INSIDE, true, li);
     return true;
   }
   (void)hipGetLastError();
@@ -521,89 +492,90 @@ static bool conv_chained(spk_model* m, Layer& L, const PwConvArgs& q, int nb, un
 }
 
 // block-closing conv + the shortcut conv of its block as one K-concatenated GEMM
-static int conv_dual(spk_model* m, Layer& L, int nb, unsigned allow, const ConvArgs& a) {
+static int conv_dual(spk_model* m, Layer& L, const EvalCursor& c, unsigned allow, const ConvArgs& a) {
   if (!dual_active(m, L, allow) || a.y_lo) return FORM_PASS;
   Layer& D = m->layers[L.dual_src];
   const TDim& din = m->tdims[D.d.src];
   PwConvArgs q = pw_args(a, m->wdual + L.wdual_off);   // (stride 1: what the pairing asks of L)
   q.res = nullptr;
   q.scale = m->sdual + L.sdual_off; q.shift = q.scale + L.d.cout;
-  q.x2 = (const bf16_t*)m->TI(D.d.src); q.Cin2 = D.d.cin; q.H2 = din.h; q.W2 = din.w; q.stride2 = D.d.stride;
-  q.x2_bytes = (unsigned)((size_t)nb * din.h * din.w * din.c * 2);
-  if (conv_chained(m, L, q, nb, allow)) return SPK_OK;
-  const int r = spk_conv1x1_dual_launch(q, m->stream);
+  q.x2 = (const bf16_t*)m->TI(c, D.d.src); q.Cin2 = D.d.cin; q.H2 = din.h; q.W2 = din.w; q.stride2 = D.d.stride;
+  q.x2_bytes = (unsigned)((size_t)c.n * din.h * din.w * din.c * 2);
+  if (conv_chained(m, L, q, c, allow)) return SPK_OK;
+  const int r = spk_conv1x1_dual_launch(q, c.stream);
   if (r == 0) {
-    note(m, allow, index_of(m, L), EF_OWN | EF_DUAL, true);
+    note(m, c, allow, index_of(m, L), EF_OWN | EF_DUAL, true);
     return SPK_OK;
   }
   if (r != -3) return spk_fail(SPK_ERR_HIP, std::string("fused 1x1 conv launch failed for ") + L.d.name);
   // no configuration fits this problem: the shortcut conv on its own after all, then this layer the usual way
-  SPK_TRY(run_conv_eval(m, D, nb, 0));
-  note(m, allow, L.dual_src, EF_OWN, true);
+  SPK_TRY(run_conv_eval(m, D, c, 0));
+  note(m, c, allow, L.dual_src, EF_OWN, true);
   L.dual_ok = false;
   return FORM_PASS;
 }
 
-static int conv_1x1(spk_model* m, Layer& L, int nb, unsigned allow, const ConvArgs& a) {
+static int conv_1x1(spk_model* m, Layer& L, const EvalCursor& c, unsigned allow, const ConvArgs& a) {
   if (!(L.pw_ok && a.dt == DT_F16 && !a.res_lo && !a.y_lo && !a.cin_s && !a.cout_s && !a.pool_y)) return FORM_PASS;
   const PwConvArgs q = pw_args(a, m->wpack + L.wpw_off);
-  if (q.res && conv_chained(m, L, q, nb, allow)) return SPK_OK;
-  if (spk_conv1x1_launch(a, q, m->stream))
+  if (q.res && conv_chained(m, L, q, c, allow)) return SPK_OK;
+  if (spk_conv1x1_launch(a, q, c.stream))
     return spk_fail(SPK_ERR_HIP, std::string("1x1 conv launch failed for ") + L.d.name);
   return SPK_OK;
 }
 
-static int conv_3x3_c3(spk_model* m, const Layer& L, const ConvArgs& a) {
+static int conv_3x3_c3(spk_model* m, const Layer& L, const EvalCursor& c, const ConvArgs& a) {
   static const bool use_c3 = !getenv("SPK_C3") || atoi(getenv("SPK_C3")) != 0;
   if (!(use_c3 && L.c3_ok && a.dt == DT_F16 && !a.res_lo && !a.y_lo && !a.cin_s && !a.cout_s)) return FORM_PASS;
-  const int r = spk_conv3x3_launch(c3_args(a, m->wpack + L.wpw_off, a.splitw ? 2 : 1), m->stream);
+  const int r = spk_conv3x3_launch(c3_args(a, m->wpack + L.wpw_off, a.splitw ? 2 : 1), c.stream);
   if (r == 0) return SPK_OK;
   if (r != -3) return spk_fail(SPK_ERR_HIP, std::string("3x3 conv launch failed for ") + L.d.name);
   return FORM_PASS;
 }
 
-static int conv_3x3_d3(spk_model* m, const Layer& L, const ConvArgs& a) {
+static int conv_3x3_d3(spk_model* m, const Layer& L, const EvalCursor& c, const ConvArgs& a) {
   if (!(L.d3_ok && a.dt == DT_F16 && !a.splitw && !a.res_lo && !a.y_lo && !a.cin_s && !a.cout_s && !a.pool_y)) return FORM_PASS;
-  if (spk_conv3x3_d3_launch(a, c3_args(a, m->wpack + L.wd3_off, 1), m->stream))
+  if (spk_conv3x3_d3_launch(a, c3_args(a, m->wpack + L.wd3_off, 1), c.stream))
     return spk_fail(SPK_ERR_HIP, std::string("3x3 conv launch failed for ") + L.d.name);
   return SPK_OK;
 }
 
 // One conv layer in the first form that applies, in this order of precedence.  (spk_run_layer_eval has recorded it as
 // "its own launch, written"; the forms that do more, or less, say so.)
-static int run_conv_eval(spk_model* m, Layer& L, int nb, unsigned allow) {
+static int run_conv_eval(spk_model* m, Layer& L, const EvalCursor& c, unsigned allow) {
   const int li = index_of(m, L);
+  EvalCarry& carry = m->carry[c.half];
   int r;
-  if ((r = conv_block_tail(m, L, nb, allow)) != FORM_PASS) return r;
-  if ((r = conv_whole_block(m, L, nb, allow)) != FORM_PASS) return r;
+  if ((r = conv_block_tail(m, L, c, allow)) != FORM_PASS) return r;
+  if ((r = conv_whole_block(m, L, c, allow)) != FORM_PASS) return r;
   if (L.fused_into >= 0 && dual_active(m, m->layers[L.fused_into], allow)) {
-    note(m, allow, li, EF_INSIDE, false, L.fused_into);   // computed inside the block-closing conv's kernel, never written
+    note(m, c, allow, li, EF_INSIDE, false, L.fused_into);   // computed inside the block-closing conv's kernel, never written
     return SPK_OK;
   }
-  if (L.mode == CONV_MODE_STEM3) return conv_stem3(m, L, nb);
-  if (L.mode == CONV_MODE_GROUP) return conv_grouped(m, L, nb);
+  if (L.mode == CONV_MODE_STEM3) return conv_stem3(m, L, c);
+  if (L.mode == CONV_MODE_GROUP) return conv_grouped(m, L, c);
   ConvArgs a;
-  conv_args(m, L, nb, a);
-  if (L.gate_from >= 0 && (allow & EVAL_FORWARD) && (m->ran[m->half][L.gate_from].form & EF_GATES)) {
+  conv_args(m, L, c, a);
+  if (L.gate_from >= 0 && (allow & EVAL_FORWARD) && (carry.ran[L.gate_from].form & EF_GATES)) {
     // the squeeze-excitation layer in front left its gates instead of the scaled tensor: read what IT read
-    if (!m->gate_h[m->half]) return spk_fail(SPK_ERR_STATE, std::string("no squeeze-excitation gates for ") + L.d.name);
-    a.x = (const bf16_t*)m->TI(m->layers[L.gate_from].d.src);
-    spk_set_gate(a, m->gate_h[m->half], m->gate_stride_h[m->half]);
+    if (!carry.gate) return spk_fail(SPK_ERR_STATE, std::string("no squeeze-excitation gates for ") + L.d.name);
+    a.x = (const bf16_t*)m->TI(c, m->layers[L.gate_from].d.src);
+    spk_set_gate(a, carry.gate, carry.gate_stride);
   }
   if (stem_pool_fused(m, L, allow)) {   // the max-pool layer that follows is computed here and finds itself done
     const Layer& P = m->layers[L.fuse_pool];
     const TDim& po = m->tdims[P.d.dst];
-    a.pool_y = (bf16_t*)m->TI(P.d.dst);
+    a.pool_y = (bf16_t*)m->TI(c, P.d.dst);
     a.pool_ho = po.h;
     a.pool_wo = po.w;
-    note(m, allow, li, EF_OWN | EF_POOL, false);
-    note(m, allow, L.fuse_pool, EF_INSIDE, true, li);
+    note(m, c, allow, li, EF_OWN | EF_POOL, false);
+    note(m, c, allow, L.fuse_pool, EF_INSIDE, true, li);
   }
-  if ((r = conv_dual(m, L, nb, allow, a)) != FORM_PASS) return r;
-  if ((r = conv_1x1(m, L, nb, allow, a)) != FORM_PASS) return r;
-  if ((r = conv_3x3_c3(m, L, a)) != FORM_PASS) return r;
-  if ((r = conv_3x3_d3(m, L, a)) != FORM_PASS) return r;
-  if (spk_conv_launch(a, L.mode, m->stream, nullptr))
+  if ((r = conv_dual(m, L, c, allow, a)) != FORM_PASS) return r;
+  if ((r = conv_1x1(m, L, c, allow, a)) != FORM_PASS) return r;
+  if ((r = conv_3x3_c3(m, L, c, a)) != FORM_PASS) return r;
+  if ((r = conv_3x3_d3(m, L, c, a)) != FORM_PASS) return r;
+  if (spk_conv_launch(a, L.mode, c.stream, nullptr))
     return spk_fail(SPK_ERR_HIP, std::string("conv launch failed for ") + L.d.name);
   return SPK_OK;
 }
@@ -686,7 +658,9 @@ static int fp8_shadow_prepare(spk_model* m) {
 
 // fp8 mode: the two 1x1 convs of an MBConv block with e4m3 tensors between them (pw_fp8.hip; the depthwise and squeeze-
 // excitation layers between them: spk_run_layer_eval)
-static int run_layer_fp8(spk_model* m, Layer& L, int nb) {
+static int run_layer_fp8(spk_model* m, Layer& L, const EvalCursor& c) {
+  EvalCarry& carry = m->carry[c.half];
+  const int nb = c.n;
   const TDim& in = m->tdims[L.d.src];
   const TDim& o = m->tdims[L.d.dst];
   const float* sc = m->scale_bias + L.sb_off;
@@ -696,18 +670,18 @@ static int run_layer_fp8(spk_model* m, Layer& L, int nb) {
       const float ys = spk_fp8_scale_of(L.amax_out);
       m->t_fp8_scale[L.d.dst] = ys;
       // the trunk as e4m3 bytes when the previous block's project conv left them (same bytes as converting here)
-      const bool shadow = m->shadow_t_h[m->half] == L.d.src && m->fp8_shadow;
+      const bool shadow = carry.shadow_t == L.d.src && m->fp8_shadow;
       // (the shadow holds the images of this chunk at its own row stride)
-      const void* xsrc = shadow ? (const void*)(m->fp8_shadow + (size_t)m->img0 * m->fp8_shadow_img) : m->TI(L.d.src);
+      const void* xsrc = shadow ? (const void*)(m->fp8_shadow + (size_t)c.img0 * m->fp8_shadow_img) : m->TI(c, L.d.src);
       if (spk_launch_pw_fp8(xsrc, shadow ? 1 : 0, m->w8pack + L.w8_off,
-                            m->TI8(L.d.dst), 1, nullptr, m->s8 + L.s8_off + L.cout_p, sc + L.cout_p, nullptr, 0, in.h * in.w,
-                            nb * o.h * o.w, kpad, L.cout_p, shadow ? m->shadow_stride_h[m->half] : in.c, o.c, L.d.relu,
-                            1.f / spk_fp8_scale_of(L.amax_in), 1.f / ys, m->stream))
+                            m->TI8(c, L.d.dst), 1, nullptr, m->s8 + L.s8_off + L.cout_p, sc + L.cout_p, nullptr, 0, in.h * in.w,
+                            nb * o.h * o.w, kpad, L.cout_p, shadow ? carry.shadow_stride : in.c, o.c, L.d.relu,
+                            1.f / spk_fp8_scale_of(L.amax_in), 1.f / ys, c.stream))
         return spk_fail(SPK_ERR_HIP, std::string("fp8 expand conv launch failed for ") + L.d.name);
       return SPK_OK;
     }
     default: {  // 4 project: A = the depthwise output (e4m3) x gate; fp16 trunk out (+ shortcut)
-      if (L.src_se < 0 || m->layers[L.src_se].fp8_role != 3 || !m->gate_h[m->half])
+      if (L.src_se < 0 || m->layers[L.src_se].fp8_role != 3 || !carry.gate)
         return spk_fail(SPK_ERR_STATE, "fp8 project conv without its squeeze-excitation gate");
       const int se_src = m->layers[L.src_se].d.src;
       const TDim& e = m->tdims[se_src];
@@ -716,42 +690,43 @@ static int run_layer_fp8(spk_model* m, Layer& L, int nb) {
       unsigned char* y8 = nullptr;
       int y8_stride = 0;
       float y8_inv = 0.f;
-      m->shadow_t_h[m->half] = -1;
+      carry.shadow_t = -1;
       if (m->fp8_shadow_img && L.exp_next >= 0 && m->layers[L.exp_next].fp8_role == 1) {
         y8_stride = (o.c + 15) / 16 * 16;
-        y8 = m->fp8_shadow + (size_t)m->img0 * m->fp8_shadow_img;
+        y8 = m->fp8_shadow + (size_t)c.img0 * m->fp8_shadow_img;
         y8_inv = 1.f / spk_fp8_scale_of(m->layers[L.exp_next].amax_in);
       }
-      if (spk_launch_pw_fp8(m->TI8(se_src), 1, m->w8pack + L.w8_off, m->TI(L.d.dst), 0,
-                            L.d.res >= 0 ? (const bf16_t*)m->TI(L.d.res) : nullptr, m->s8 + L.s8_off + L.cout_p, sc + L.cout_p,
-                            m->gate_h[m->half], m->gate_stride_h[m->half], e.h * e.w, nb * o.h * o.w, kpad, L.cout_p, e.c, o.c, L.d.relu,
-                            1.f, 1.f, m->stream, y8, y8_stride, y8_inv))
+      if (spk_launch_pw_fp8(m->TI8(c, se_src), 1, m->w8pack + L.w8_off, m->TI(c, L.d.dst), 0,
+                            L.d.res >= 0 ? (const bf16_t*)m->TI(c, L.d.res) : nullptr, m->s8 + L.s8_off + L.cout_p, sc + L.cout_p,
+                            carry.gate, carry.gate_stride, e.h * e.w, nb * o.h * o.w, kpad, L.cout_p, e.c, o.c, L.d.relu,
+                            1.f, 1.f, c.stream, y8, y8_stride, y8_inv))
         return spk_fail(SPK_ERR_HIP, std::string("fp8 project conv launch failed for ") + L.d.name);
-      if (y8) { m->shadow_t_h[m->half] = L.d.dst; m->shadow_stride_h[m->half] = y8_stride; }
+      if (y8) { carry.shadow_t = L.d.dst; carry.shadow_stride = y8_stride; }
       m->t_fp8_scale[L.d.dst] = 0.f;
       return SPK_OK;
     }
   }
 }
 
-int spk_run_layer_eval(spk_model* m, Layer& L, int nb, unsigned allow) {
+int spk_run_layer_eval(spk_model* m, Layer& L, const EvalCursor& c, unsigned allow) {
   const TDim& in = m->tdims[L.d.src];
   const TDim& o = m->tdims[L.d.dst];
-  const int li = index_of(m, L);
+  const int li = index_of(m, L), nb = c.n;
+  EvalCarry& carry = m->carry[c.half];
   // an earlier launch of this forward computed this layer too
-  if ((allow & EVAL_FORWARD) && (m->ran[m->half][li].form & EF_INSIDE)) return SPK_OK;
-  note(m, allow, li, EF_OWN, true);   // (what most layers are; the forms that do more, or less, say so)
+  if ((allow & EVAL_FORWARD) && (carry.ran[li].form & EF_INSIDE)) return SPK_OK;
+  note(m, c, allow, li, EF_OWN, true);   // (what most layers are; the forms that do more, or less, say so)
   // fp8 mode, inside an MBConv block on the e4m3 path (spk_model_set_fp8): tensors of e4m3 bytes, value = byte * scale
   const bool e4m3 = m->fp8 && m->fp8_calibrated && L.fp8_role;
-  if (e4m3 && L.d.kind == SPK_OP_CONV) return run_layer_fp8(m, L, nb);
+  if (e4m3 && L.d.kind == SPK_OP_CONV) return run_layer_fp8(m, L, c);
   switch (L.d.kind) {
-    case SPK_OP_CONV: return run_conv_eval(m, L, nb, allow);
+    case SPK_OP_CONV: return run_conv_eval(m, L, c, allow);
     case SPK_OP_DWCONV: {
       const float* sc = m->scale_bias + L.sb_off;
-      float* partial = m->SE();
+      float* partial = m->SE(c);
       const float s_in = e4m3 ? spk_fp8_scale_of(L.amax_in) : 1.f, ys = e4m3 ? spk_fp8_scale_of(L.amax_out) : 1.f;
       if (e4m3) m->t_fp8_scale[L.d.dst] = ys;
-      void *xs = e4m3 ? m->TI8(L.d.src) : m->TI(L.d.src), *yd = e4m3 ? m->TI8(L.d.dst) : m->TI(L.d.dst);
+      void *xs = e4m3 ? m->TI8(c, L.d.src) : m->TI(c, L.d.src), *yd = e4m3 ? m->TI8(c, L.d.dst) : m->TI(c, L.d.dst);
       // the pool partial sums of the squeeze-excitation gate that follows are a by-product
       const bool lds = e4m3 || m->infer_dt == DT_F16;
       const int chunks[2] = {spk_dw_chunks(nb, o.h * (e4m3 ? (o.w + 1) / 2 : (o.w + 3) / 4), in.c),
@@ -759,16 +734,16 @@ int spk_run_layer_eval(spk_model* m, Layer& L, int nb, unsigned allow) {
       auto run = [&](int v) {
         if (v)
           return spk_launch_dwconv_lds(e4m3, xs, m->dwpack + L.wpack_off, sc, sc + L.cout_p, yd, partial, nb, in.h, in.w, in.c,
-                                       o.h, o.w, L.d.k, L.d.stride, L.d.relu, s_in, 1.f / ys, m->stream);
+                                       o.h, o.w, L.d.k, L.d.stride, L.d.relu, s_in, 1.f / ys, c.stream);
         if (e4m3)
           return spk_launch_dwconv_fp8((const unsigned char*)xs, m->dwpack + L.wpack_off, sc, sc + L.cout_p, (unsigned char*)yd,
                                        partial, nb, in.h, in.w, in.c, o.h, o.w, L.d.k, L.d.stride, L.d.relu, chunks[0], s_in,
-                                       1.f / ys, m->stream);
+                                       1.f / ys, c.stream);
         return spk_launch_dwconv((const bf16_t*)xs, m->dwpack + L.wpack_off, sc, sc + L.cout_p, (bf16_t*)yd, partial, nb, in.h,
-                                 in.w, in.c, o.h, o.w, L.d.k, L.d.stride, L.d.relu, m->infer_dt, m->stream);
+                                 in.w, in.c, o.h, o.w, L.d.k, L.d.stride, L.d.relu, m->infer_dt, c.stream);
       };
-      const int v = dw_choose(e4m3, nb, in.h, in.w, in.c, L.d.k, L.d.stride, m->stream, run, chunks);
-      m->dw_chunks_h[m->half] = chunks[v];
+      const int v = dw_choose(e4m3, nb, in.h, in.w, in.c, L.d.k, L.d.stride, c.stream, run, chunks);
+      carry.dw_chunks = chunks[v];
       if (run(v) != 0)
         return e4m3 ? spk_fail(SPK_ERR_HIP, std::string("fp8 depthwise launch failed for ") + L.d.name)
                     : spk_fail(SPK_ERR_UNSUPPORTED, std::string("depthwise conv launch failed (fp16 eval only) for ") + L.d.name);
@@ -777,42 +752,42 @@ int spk_run_layer_eval(spk_model* m, Layer& L, int nb, unsigned allow) {
     case SPK_OP_SE: {
       // src is the output of a depthwise conv, which left its pool partials in the scratch
       if (L.se_dw < 0) return spk_fail(SPK_ERR_UNSUPPORTED, "squeeze-excitation must follow a depthwise conv");
-      float* partial = m->SE();
-      const int chunks = m->dw_chunks_h[m->half];   // as the depthwise launch that just ran
+      float* partial = m->SE(c);
+      const int chunks = carry.dw_chunks;   // as the depthwise launch that just ran
       float* scale = partial + (size_t)nb * chunks * in.c;
       // the gates only when the project conv behind this layer multiplies them into its operand (SPK_SE_FUSE=0: never; the
       // e4m3 path: always): the scaled tensor - one read and one write of the widest tensor of the block - is then not
       // materialised
       const bool gate_only = e4m3 || ((allow & FUSE_GATE) && m->fuse_se && L.gate_conv >= 0 && m->infer_dt == DT_F16 && !m->precise_res);
-      if (spk_launch_se(gate_only ? nullptr : (const bf16_t*)m->TI(L.d.src), gate_only ? nullptr : (bf16_t*)m->TI(L.d.dst),
+      if (spk_launch_se(gate_only ? nullptr : (const bf16_t*)m->TI(c, L.d.src), gate_only ? nullptr : (bf16_t*)m->TI(c, L.d.dst),
                         partial, chunks, scale, m->P(L.p_w), m->P(L.p_b), m->dwpack + L.wpack_off, m->P(L.p_b2), nb,
-                        in.h * in.w, L.d.cin, in.c, L.d.k, e4m3 ? DT_F16 : m->infer_dt, m->stream, L.d.relu == SPK_ACT_RELU ? 1 : 0))
+                        in.h * in.w, L.d.cin, in.c, L.d.k, e4m3 ? DT_F16 : m->infer_dt, c.stream, L.d.relu == SPK_ACT_RELU ? 1 : 0))
         return e4m3 ? spk_fail(SPK_ERR_HIP, std::string("squeeze-excitation launch failed for ") + L.d.name)
                     : spk_fail(SPK_ERR_UNSUPPORTED, std::string("squeeze-excitation launch failed (fp16 eval only) for ") + L.d.name);
-      m->gate_h[m->half] = gate_only ? scale : nullptr;
-      m->gate_stride_h[m->half] = in.c;
+      carry.gate = gate_only ? scale : nullptr;
+      carry.gate_stride = in.c;
       if (e4m3) m->t_fp8_scale[L.d.dst] = 0.f;   // not materialised
-      if (gate_only) note(m, allow, li, EF_OWN | EF_GATES, false);
+      if (gate_only) note(m, c, allow, li, EF_OWN | EF_GATES, false);
       return SPK_OK;
     }
     case SPK_OP_MAXPOOL:
-      if (spk_launch_maxpool((const bf16_t*)m->TI(L.d.src), (bf16_t*)m->TI(L.d.dst), nb, in.h, in.w,
-                             in.c, L.d.k, L.d.stride, L.d.pad, o.h, o.w, m->infer_dt, m->stream))
+      if (spk_launch_maxpool((const bf16_t*)m->TI(c, L.d.src), (bf16_t*)m->TI(c, L.d.dst), nb, in.h, in.w,
+                             in.c, L.d.k, L.d.stride, L.d.pad, o.h, o.w, m->infer_dt, c.stream))
         return spk_fail(SPK_ERR_HIP, "maxpool launch failed");
       return SPK_OK;
     case SPK_OP_GAVGPOOL:
-      if (spk_launch_gavgpool((const bf16_t*)m->TI(L.d.src), (float*)m->TI(L.d.dst), nb, in.h * in.w,
-                              in.c, m->infer_dt, m->stream))
+      if (spk_launch_gavgpool((const bf16_t*)m->TI(c, L.d.src), (float*)m->TI(c, L.d.dst), nb, in.h * in.w,
+                              in.c, m->infer_dt, c.stream))
         return spk_fail(SPK_ERR_HIP, "avgpool launch failed");
       return SPK_OK;
     case SPK_OP_LINEAR:
-      if (spk_launch_linear_fwd((const float*)m->TI(L.d.src), m->P(L.p_w), m->P(L.p_b),
-                                (float*)m->TI(L.d.dst), nb, L.d.cin, L.d.cout, m->stream))
+      if (spk_launch_linear_fwd((const float*)m->TI(c, L.d.src), m->P(L.p_w), m->P(L.p_b),
+                                (float*)m->TI(c, L.d.dst), nb, L.d.cin, L.d.cout, c.stream))
         return spk_fail(SPK_ERR_HIP, "linear launch failed");
       return SPK_OK;
     case SPK_OP_DROPOUT:  // eval: identity
-      HIP_TRY(hipMemcpyAsync(m->TI(L.d.dst), m->TI(L.d.src), (size_t)nb * in.c * 4,
-                             hipMemcpyDeviceToDevice, m->stream));
+      HIP_TRY(hipMemcpyAsync(m->TI(c, L.d.dst), m->TI(c, L.d.src), (size_t)nb * in.c * 4,
+                             hipMemcpyDeviceToDevice, c.stream));
       return SPK_OK;
   }
   return spk_fail(SPK_ERR_UNSUPPORTED, "unknown layer kind");
@@ -823,8 +798,9 @@ int spk_run_layer_eval(spk_model* m, Layer& L, int nb, unsigned allow) {
 // the shortcut convs of a block forked onto a side stream, 5.40 vs 5.30 ms; the leading layers run in 32-64 image chunks so
 // that their tensors stay in the 256 MiB Infinity Cache, 5.57-5.62 vs 5.51 ms.)
 static int run_layers_eval(spk_model* m, int nb) {
+  const EvalCursor c{0, 0, nb, m->stream};
   spk_eval_begin(m, nb);
-  for (size_t i = 0; i < m->layers.size(); ++i) SPK_TRY(spk_run_layer_eval(m, m->layers[i], nb, FUSE_ALL | EVAL_FORWARD));
+  for (Layer& L : m->layers) SPK_TRY(spk_run_layer_eval(m, L, c, FUSE_ALL | EVAL_FORWARD));
   return SPK_OK;
 }
 
@@ -849,7 +825,7 @@ int spk_forward_eval_logits(spk_model* m, const void* x, int n, int h, int w, in
   // Two halves of the batch on two streams (ResNets, one micro-batch, n >= 64): the layers of a forward are a chain,
   // but the two halves are independent, so an HBM-bound layer of one half runs beside an MFMA-bound layer of the other
   // and the tail of every kernel is covered by the other stream's work.  Both halves live in the SAME activation
-  // tensors (images [0, n/2) and [n/2, n): spk_model::img0), launches are interleaved layer by layer, the caller's stream
+  // tensors (images [0, n/2) and [n/2, n): EvalCursor::img0), launches are interleaved layer by layer, the caller's stream
   // forks before the first layer and joins after the last.  Per-image results do not depend on the split.  Measured
   // (ResNet-50, batch 256): 4.52 -> 4.29 ms.  SPK_EVAL_STREAMS=1 keeps one stream.
   static const int n_streams = getenv("SPK_EVAL_STREAMS") ? atoi(getenv("SPK_EVAL_STREAMS")) : 2;
@@ -866,47 +842,45 @@ int spk_forward_eval_logits(spk_model* m, const void* x, int n, int h, int w, in
     const bool warm = std::find(m->half_warm.begin(), m->half_warm.end(), key) != m->half_warm.end();
     if (!warm) m->half_warm.push_back(key);
     const hipStream_t str[2] = {main_s, warm ? m->half_stream : main_s};
-    m->two_streams_now = warm;
     const int cnt[2] = {n / 2, n - n / 2}, off[2] = {0, n / 2};
-    HIP_TRY(hipEventRecord(m->half_fork, main_s));
-    HIP_TRY(hipStreamWaitEvent(m->half_stream, m->half_fork, 0));
-    spk_eval_begin(m, n);
-    int rc = SPK_OK;
-    // one step of half hf: what a layer leaves for the next one of ITS chain (pool-partial rows, gates, e4m3 shadow, the
-    // record) is indexed by spk_model::half
+    // one chain per half: what a layer leaves for the next one of ITS chain (pool-partial rows, gates, e4m3 shadow, the
+    // record) is spk_model::carry[half]
+    const EvalCursor ch[2] = {{0, off[0], cnt[0], str[0]}, {1, off[1], cnt[1], str[1]}};
     // paired tuning: the tuners reached from a half's launches time their candidates beside the other half's (the first
     // forward, whose second stream is idle) and look their "_p" entries up (every forward); the MBConv networks keep
     // the isolated entries
     const int twin_mode = !spk_tune_paired_on() || m->effnet ? SpkTwin::OFF : (warm ? SpkTwin::LOOKUP : SpkTwin::PAIRS);
-    auto on_half = [&](int hf) {
-      m->img0 = off[hf]; m->stream = str[hf]; m->half = hf;
-      twin_set(m, twin_mode, off, cnt, hf);
-    };
-    for (int hf = 0; hf < 2 && rc == SPK_OK; ++hf) {
-      on_half(hf);
-      const char* xi = (const char*)x + (size_t)off[hf] * spk_image_stride_bytes(m->in_chans, h, w, dtype);
-      if (spk_launch_to_nhwc4(xi, layout, dtype, cnt[hf], m->in_chans, h, w, (bf16_t*)m->TI(0), m->infer_dt, m->stream, SPK_INPUT_SCALE))
-        rc = spk_fail(SPK_ERR_HIP, "input conversion launch failed");
-    }
-    for (size_t i = 0; i < m->layers.size() && rc == SPK_OK; ++i)
-      for (int hf = 0; hf < 2 && rc == SPK_OK; ++hf) {
-        on_half(hf);
-        rc = spk_run_layer_eval(m, m->layers[i], cnt[hf], FUSE_ALL | EVAL_FORWARD);
+    const EvalTwin tw[2] = {{m, off[0], off[1], cnt[1], warm}, {m, off[1], off[0], cnt[0], warm}};
+    const SpkTwin twin[2] = {{twin_mode, m->half_stream, cnt[0], cnt[1], spk_twin_rebase, (void*)&tw[0]},
+                             {twin_mode, m->half_stream, cnt[1], cnt[0], spk_twin_rebase, (void*)&tw[1]}};
+    HIP_TRY(hipEventRecord(m->half_fork, main_s));
+    HIP_TRY(hipStreamWaitEvent(m->half_stream, m->half_fork, 0));
+    // on every way out: no twin context, and the caller's stream joins the second one (also after an error: nothing may be
+    // left running there behind the caller's back)
+    struct Leave {
+      spk_model* m;
+      ~Leave() {
+        spk_twin() = SpkTwin();
+        (void)hipEventRecord(m->half_join, m->half_stream);
+        (void)hipStreamWaitEvent(m->stream, m->half_join, 0);
       }
-    for (int hf = 0; hf < 2 && rc == SPK_OK; ++hf) {
-      on_half(hf);
-      if (hipMemcpyAsync(logits_dev + (size_t)off[hf] * m->num_classes, m->TI(last), (size_t)cnt[hf] * m->num_classes * 4,
-                         hipMemcpyDeviceToDevice, m->stream) != hipSuccess)
-        rc = spk_fail(SPK_ERR_HIP, "logits copy failed");
+    } leave{m};
+    spk_eval_begin(m, n);
+    for (const EvalCursor& c : ch) {
+      const char* xi = (const char*)x + (size_t)c.img0 * spk_image_stride_bytes(m->in_chans, h, w, dtype);
+      if (spk_launch_to_nhwc4(xi, layout, dtype, c.n, m->in_chans, h, w, (bf16_t*)m->TI(c, 0), m->infer_dt, c.stream, SPK_INPUT_SCALE))
+        return spk_fail(SPK_ERR_HIP, "input conversion launch failed");
     }
-    m->img0 = m->half = 0;
-    m->stream = main_s;
-    m->two_streams_now = false;
-    spk_twin() = SpkTwin();
-    // (join even after an error: nothing may be left running on the second stream behind the caller's back)
-    (void)hipEventRecord(m->half_join, m->half_stream);
-    (void)hipStreamWaitEvent(main_s, m->half_join, 0);
-    return rc;
+    for (Layer& L : m->layers)
+      for (int hf = 0; hf < 2; ++hf) {
+        spk_twin() = twin[hf];
+        SPK_TRY(spk_run_layer_eval(m, L, ch[hf], FUSE_ALL | EVAL_FORWARD));
+      }
+    for (const EvalCursor& c : ch)
+      if (hipMemcpyAsync(logits_dev + (size_t)c.img0 * m->num_classes, m->TI(c, last), (size_t)c.n * m->num_classes * 4,
+                         hipMemcpyDeviceToDevice, c.stream) != hipSuccess)
+        return spk_fail(SPK_ERR_HIP, "logits copy failed");
+    return SPK_OK;
   }
   for (int i0 = 0; i0 < n; i0 += mb) {
     const int nb = std::min(mb, n - i0);
@@ -956,17 +930,17 @@ extern "C" int spk_eval_step(spk_model* m, const void* x, int n, int h, int w, i
 // before its conv2 (the block's input is still there), the depthwise conv before a squeeze-excitation layer (for its pool
 // partial sums).  No fusion, and the record stays what the forward wrote.
 static int materialise(spk_model* m, int t) {
-  const int nb = m->last_eval_nb;
-  if (nb <= 0) return SPK_OK;
+  const EvalCursor c{0, 0, m->last_eval_nb, m->stream};   // all its images at once, on chain 0
+  if (c.n <= 0) return SPK_OK;
   for (size_t i = 0; i < m->layers.size(); ++i) {
     Layer& L = m->layers[i];
     if (L.d.dst != t) continue;
     bool missing = false;
-    for (const std::vector<EvalRan>& r : m->ran) missing |= i < r.size() && r[i].form != EF_NONE && !r[i].wrote;
+    for (const EvalCarry& k : m->carry) missing |= i < k.ran.size() && k.ran[i].form != EF_NONE && !k.ran[i].wrote;
     if (!missing) continue;
-    if (L.d.kind == SPK_OP_CONV && L.bn_head >= 0) SPK_TRY(spk_run_layer_eval(m, m->layers[L.bn_head], nb, 0));
-    if (L.d.kind == SPK_OP_SE && L.se_dw >= 0) SPK_TRY(spk_run_layer_eval(m, m->layers[L.se_dw], nb, 0));
-    SPK_TRY(spk_run_layer_eval(m, L, nb, 0));
+    if (L.d.kind == SPK_OP_CONV && L.bn_head >= 0) SPK_TRY(spk_run_layer_eval(m, m->layers[L.bn_head], c, 0));
+    if (L.d.kind == SPK_OP_SE && L.se_dw >= 0) SPK_TRY(spk_run_layer_eval(m, m->layers[L.se_dw], c, 0));
+    SPK_TRY(spk_run_layer_eval(m, L, c, 0));
   }
   return SPK_OK;
 }
@@ -1025,6 +999,7 @@ extern "C" int spk_model_profile_infer(spk_model* m, const void* x, int n, int h
   SPK_TRY(spk_plan(m, n, h, w));
   if (m->fp8 && m->fp8_calibrated) SPK_TRY(fp8_shadow_prepare(m));
   const int nb = std::min(n, spk_micro_batch(m, n));
+  const EvalCursor c{0, 0, nb, m->stream};
   const int nl = (int)m->layers.size();
   std::vector<hipEvent_t> ev(nl + 2);
   for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
@@ -1036,7 +1011,7 @@ extern "C" int spk_model_profile_infer(spk_model* m, const void* x, int n, int h
     HIP_TRY(hipEventRecord(ev[1], m->stream));
     spk_eval_begin(m, nb);
     for (int i = 0; i < nl; ++i) {
-      SPK_TRY(spk_run_layer_eval(m, m->layers[i], nb, FUSE_ALL | EVAL_FORWARD));
+      SPK_TRY(spk_run_layer_eval(m, m->layers[i], c, FUSE_ALL | EVAL_FORWARD));
       HIP_TRY(hipEventRecord(ev[i + 2], m->stream));
     }
     HIP_TRY(hipStreamSynchronize(m->stream));
@@ -1063,7 +1038,7 @@ extern "C" int spk_model_profile_infer(spk_model* m, const void* x, int n, int h
   // names, FLOPs and bytes: what the record of the pass above (one stream: chain 0) says each launch computed
   for (int i = 0; i < nl; ++i) {
     const Layer& L = m->layers[i];
-    const unsigned form = m->ran[0][i].form;
+    const unsigned form = m->carry[0].ran[i].form;
     const TDim& in = m->tdims[L.d.src];
     const TDim& o = m->tdims[L.d.dst];
     double fl = 0, by = 0;

@@ -186,7 +186,6 @@ extern "C" int spk_model_set_fp8_blocks(spk_model* m, const unsigned char* flags
   m->fp8_blocks.assign(flags, flags + n_blocks);
   m->fp8_calibrated = false;     // roles are assigned by the next calibration
   m->fp8_packed = false;
-  m->shadow_t_h[0] = m->shadow_t_h[1] = -1;
   return SPK_OK;
 }
 
@@ -358,7 +357,8 @@ extern "C" int spk_model_calibrate_act_means(spk_model* m, const void* x, int n,
     }
     // a forward with no fusion allowed: every tensor a conv reads must really be written (no fused stem pool / shortcut conv)
     spk_eval_begin(m, nb);
-    for (size_t i = 0; i < m->layers.size() && rc == SPK_OK; ++i) rc = spk_run_layer_eval(m, m->layers[i], nb, EVAL_FORWARD);
+    const EvalCursor c{0, 0, nb, m->stream};
+    for (size_t i = 0; i < m->layers.size() && rc == SPK_OK; ++i) rc = spk_run_layer_eval(m, m->layers[i], c, EVAL_FORWARD);
     for (size_t gi = 0; gi < gen.size() && rc == SPK_OK; ++gi) {
       const Layer& L = m->layers[gen[gi]];
       const TDim& in = m->tdims[L.d.src];

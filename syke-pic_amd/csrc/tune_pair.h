@@ -1,7 +1,8 @@
 // Paired tuning (tune_table.h, SpkTwin): the twin of a launch - the same problem on the other half batch's slices of
 // the same tensors - derived from the launch's own argument struct.  This is the one place that knows which fields of
 // an argument struct are activation pointers, image counts and byte extents; a tuner site holds a SpkPair of its
-// arguments and hands p[0] / p[1] to the candidate that SpkLaunchTimer::time asks it to run.
+// arguments and hands p[0] / p[1] to the candidate that SpkLaunchTimer::time asks it to run.  (The context is the eval
+// forward's: set beside the cursor of each half batch, SpkTwin::user = that half's EvalTwin; a site never sees the handle.)
 #pragma once
 #include "spk_common.h"
 #include "tune_table.h"

@@ -13,7 +13,7 @@
 //
 // Paired mode (SpkTwin below).  The two-stream eval forward runs every kernel beside its twin - the same layer of the
 // other half batch - so what the step pays for a candidate is the time of the PAIR, not the candidate's time alone on
-// the chip.  While the executor has a twin context set, the seven eval tuners look their problems up under "<tag>_p"
+// the chip.  While the two-stream forward has a twin context set, the seven eval tuners look their problems up under "<tag>_p"
 // entries of their own (a miss is tuned, never answered from the isolated entry) and time each candidate as `reps`
 // pairs: the candidate on the caller's stream, the same candidate on the other half's slices of the same tensors on the
 // twin stream, forked and joined with events.  SPK_TUNE_PAIRED=0: no twin context is ever set, isolated tuning
@@ -80,8 +80,8 @@ inline bool spk_tune_paired_on() {
   return v;
 }
 
-// The twin context of the calling thread, set by the eval executor around the launches of one half batch and nowhere
-// else.  PAIRS: the first forward of a shape - both halves run in order on the caller's stream, `stream` is idle, a
+// The twin context of the calling thread, set by the two-stream branch of spk_forward_eval_logits (model.hip) with the
+// cursor of the half batch it passes to the executor, cleared on every way out of that branch, and set nowhere else.  PAIRS: the first forward of a shape - both halves run in order on the caller's stream, `stream` is idle, a
 // tuner times pairs.  LOOKUP: the halves are live on their two streams (or a pair is being timed): the paired entries
 // are looked up, nothing is launched beside anything.
 struct SpkTwin {
@@ -92,7 +92,7 @@ struct SpkTwin {
   // *p points at this half's first image of an activation tensor (or outside the activations: weights, folded
   // BatchNorm): makes it the other half's first image of the same tensor; false: neither
   bool (*rebase)(void* user, const void** p) = nullptr;
-  void* user = nullptr;
+  void* user = nullptr;           // whatever rebase needs (the executor: an EvalTwin, model.h)
 };
 inline SpkTwin& spk_twin() {
   static thread_local SpkTwin t;

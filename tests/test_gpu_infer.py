@@ -304,6 +304,29 @@ def test_two_stream_forward_equals_the_halves_run_alone(golden_dir, network, n, 
     second = net.probabilities(x).cpu()         # two streams
     third = net.probabilities(x).cpu()
     assert torch.equal(first, second) and torch.equal(second, third)
+    # the tensors read back afterwards, all n images: the stem conv's output (the fused stem + pool launch did not write
+    # it: recomputed over both halves), the max-pool output (written by the stem kernel), every downsample conv's output
+    # (ResNet-50: absorbed into the dual-source launch, recomputed) and the last conv's output
+    from oracle import graph_eval
+    tsd = {k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}
+    chw = {t: tuple(v.shape[1:]) for t, v in graph_eval.run(g, tsd, x[:1].cpu()).items()}
+    convs = [op for op in g.ops if op.kind == arch.OP_CONV]
+    pool = [op for op in g.ops if op.kind == arch.OP_MAXPOOL][0]
+    shortcuts = [op for op in convs if op.name.endswith("downsample.0")]
+    assert pool.src == convs[0].dst and len(shortcuts) == (4 if network == "resnet50" else 3)
+    ids = [convs[0].dst, pool.dst] + [op.dst for op in shortcuts] + [convs[-1].dst]
+
+    def read_back(k):
+        return [net.read_activation(t, k, (k,) + chw[t]) for t in ids]
+
+    whole = read_back(n)
+    parts = []
+    for i in range(0, n, 32):                   # the same tensors after forwards of the 32-image slices (one stream)
+        net.probabilities(x[i:i + 32])
+        parts.append(read_back(min(32, n - i)))
+    for j, t in enumerate(ids):
+        assert torch.equal(whole[j], torch.cat([p[j] for p in parts])), f"tensor {t}"
+    assert torch.equal(net.probabilities(x).cpu(), second)   # a read-back leaves nothing behind
     small = torch.cat([net.probabilities(x[i:i + 32]).cpu() for i in range(0, n, 32)])   # < 64 images: one stream
     assert torch.equal(second, small)
     assert torch.isfinite(second).all() and torch.allclose(second.sum(1), torch.ones(n), atol=1e-4)
