@@ -2,12 +2,13 @@
 // library has ~9 k lines of it).  Built by `build.sh asan` with -fsanitize=address,undefined on the HOST pass of every
 // translation unit and run on the CPU (tests/test_abi.py): it walks the host logic that does not need a GPU - handle
 // creation and its error paths, the parameter table, spk_last_error, the graph analysis, the eval executor's cursor
-// addressing and twin rebase (on addresses only), and the tuner table (tune_table.h: one parser for
-// the tags of the tune-cache file, the nearest-batch rule, the appended lines) - so that heap overflows,
+// addressing and twin rebase (on addresses only), the conv descriptor builders (conv_args.h), and the tuner table
+// (tune_table.h: one parser for the tags of the tune-cache file, the nearest-batch rule, the appended lines) - so that heap overflows,
 // use-after-free and undefined behaviour there abort the run.  With no GPU every HIP call fails and the error paths
 // are what runs; on a GPU box the same binary works on real (small) buffers.  argv[1]: the shipped tuning seed
 // (default: the source tree's).
 #include "model.h"
+#include "conv_args.h"
 #include "tune_table.h"
 #include <algorithm>
 #include <cmath>
@@ -329,12 +330,88 @@ static void cursor_checks() {
   EXPECT(spk_twin_rebase(&past, &p) && p == m.TI(ch[1], 0));
 }
 
+// ---- the descriptor builders (conv_args.h): derived fields against numbers worked out by hand, and every field a
+// builder does not set left at zero.  Pointers are made-up addresses - nothing is dereferenced, no HIP call ----
+template <class T> static T zeroed() { T t; memset(&t, 0, sizeof t); return t; }
+template <class T> static bool same_bytes(const T& a, const T& b) { return memcmp(&a, &b, sizeof(T)) == 0; }
+static void descriptor_checks() {
+  bf16_t *const X = (bf16_t*)0x1000, *const Y = (bf16_t*)0x2000, *const Wt = (bf16_t*)0x3000, *const R = (bf16_t*)0x4000,
+         *const Z = (bf16_t*)0x5000;
+  float *const S = (float*)0x6000, *const B = (float*)0x7000;
+  auto cargs = [&](const ConvGeom& g, int split) { return spk_conv_args(g, X, Wt, Y, R, S, B, 1, DT_F16, split); };
+  {  // 1x1, stride 2, split weights; the same conv for conv_pw.hip, then a second source and a chained conv on it
+    const ConvArgs a = cargs(spk_conv_geom(2, 7, 7, 64, 128, 1, 2, 0), 1);
+    EXPECT(a.Ho == 4 && a.Wo == 4 && a.M == 32 && a.K == 64 && a.x_bytes == 12544 && a.w_bytes == 32768 && spk_below_2gib(a));
+    ConvArgs e = zeroed<ConvArgs>();
+    e.x = X; e.w = Wt; e.y = Y; e.res = R; e.scale = S; e.bias = B;
+    e.N = 2; e.H = 7; e.W = 7; e.Cin = 64; e.Ho = 4; e.Wo = 4; e.Cout = 128; e.kh = e.kw = 1; e.stride = 2; e.M = 32; e.K = 64;
+    e.relu = 1; e.dt = DT_F16; e.splitw = 1; e.cfg = e.dma = e.cls_ph = e.cls_pw = -1; e.x_bytes = 12544; e.w_bytes = 32768;
+    EXPECT(same_bytes(a, e));
+    PwConvArgs q = pw_args(a, Wt + 8), f = zeroed<PwConvArgs>();
+    f.x = X; f.wp = Wt + 8; f.y = Y; f.res = R; f.scale = S; f.shift = B;
+    f.N = 2; f.H = 7; f.W = 7; f.Ho = 4; f.Wo = 4; f.stride = 2; f.Cin = 64; f.Cout = 128; f.M = 32; f.relu = 1; f.dt = DT_F16;
+    f.nb = 2; f.x_bytes = 12544; f.y_bytes = 8192;
+    EXPECT(q.nb == 2 && q.y_bytes == 8192 && same_bytes(q, f));
+    spk_pw_set_second(q, R, 64, 13, 13, 4);
+    f.x2 = R; f.Cin2 = 64; f.H2 = 13; f.W2 = 13; f.stride2 = 4; f.x2_bytes = 43264;   // 2 x 13 x 13 x 64 x 2
+    EXPECT(q.x2_bytes == 43264 && same_bytes(q, f));
+    spk_pw_set_chain(q, Wt + 16, Z, S + 128, B + 128, 32, 1);
+    f.wpz = Wt + 16; f.z = Z; f.scalez = S + 128; f.shiftz = B + 128; f.Coutz = 32; f.reluz = 1; f.z_bytes = 2048;
+    EXPECT(q.z_bytes == 2048 && same_bytes(q, f) && spk_below_2gib(q));
+  }
+  {  // the 7x7 stem: four stored channels, an even row pitch, K padded to 256
+    const ConvGeom g = spk_stem_geom(1, 9, 9);
+    const ConvArgs a = cargs(g, 0);
+    EXPECT(g.W == 10 && a.W == 10 && a.H == 9 && a.Cin == 4 && a.Cout == 64 && a.Ho == 5 && a.Wo == 5 && a.M == 25 && a.K == 256);
+    EXPECT(a.kh == 7 && a.kw == 7 && a.stride == 2 && a.pad == 3 && !a.cin_s && !a.cout_s && a.x_bytes == 720 && a.w_bytes == 32768);
+    EXPECT(cargs(g, 1).w_bytes == 65536 && spk_stem_geom(1, 9, 10).W == 10 && spk_stem_geom(1, 9, 10).Wo == 5);
+  }
+  {  // EfficientNet 1x1 on unpadded tensors: 24 -> 40 stored channels, a 64 x 64 GEMM
+    const ConvArgs a = cargs({1, 5, 5, 24, 5, 5, 40, 64, 64, 64, 1, 1, 0}, 0);
+    EXPECT(a.Cin == 64 && a.Cout == 64 && a.cin_s == 24 && a.cout_s == 40 && a.x_bytes == 1200 && a.w_bytes == 8192 && a.M == 25);
+  }
+  {  // 3x3 through c3_args, hi + lo weight images
+    const ConvArgs a = cargs(spk_conv_geom(1, 6, 6, 64, 64, 3, 1, 1), 1);
+    C3Args q = c3_args(a, Wt + 8, 2), f = zeroed<C3Args>();
+    EXPECT(a.Ho == 6 && a.Wo == 6 && a.K == 576 && q.M == 36 && q.x_bytes == 4608 && q.y_bytes == 4608 && q.wp_bytes == 147456);
+    f.x = X; f.wp = Wt + 8; f.y = Y; f.scale = S; f.shift = B; f.res = R;
+    f.N = 1; f.H = 6; f.W = 6; f.Cin = 64; f.Cout = 64; f.M = 36; f.relu = 1; f.dt = DT_F16; f.nb = 2;
+    f.x_bytes = f.y_bytes = 4608; f.wp_bytes = 147456;
+    EXPECT(same_bytes(q, f) && spk_below_2gib(q));
+  }
+  {  // a whole bottleneck, then the chained conv behind it
+    BneckArgs a = spk_bneck_args(X, Y, Wt, Wt + 8, Wt + 16, S, B, S + 1, B + 1, S + 2, B + 2, 2, 14, 14, 64), e = zeroed<BneckArgs>();
+    e.x = X; e.y = Y; e.w1 = Wt; e.w2 = Wt + 8; e.w3 = Wt + 16; e.s1 = S; e.b1 = B; e.s2 = S + 1; e.b2 = B + 1; e.s3 = S + 2; e.b3 = B + 2;
+    e.N = 2; e.H = 14; e.W = 14; e.C4 = 256; e.CM = 64; e.x_bytes = 200704;
+    EXPECT(a.C4 == 256 && a.x_bytes == 200704 && same_bytes(a, e));
+    spk_bneck_set_chain(a, Wt + 24, Z, S + 3, B + 3, 128);
+    e.wz = Wt + 24; e.z = Z; e.sz = S + 3; e.bz = B + 3; e.Coutz = 128; e.z_bytes = 100352;
+    EXPECT(a.z_bytes == 100352 && same_bytes(a, e) && spk_below_2gib(a));
+  }
+  {  // the 2 GiB limit of the 32-bit buffer offsets: one element (2 bytes) below it passes, at it no more; a count past
+     // 32 bits does not wrap to a small extent
+    EXPECT(spk_extent(0x7ffffffeull) == 0x7ffffffeu && spk_extent(0x100000010ull) == 0xffffffffu);
+    ConvGeom g = {1, 1, (1 << 30) - 1, 1, 1, 1, 64, 64, 64, 64, 1, 1, 0};   // x: 2^30 - 1 one-channel pixels, then 2^30
+    EXPECT(cargs(g, 0).x_bytes == 0x7ffffffeu && spk_below_2gib(cargs(g, 0)));
+    g.W = 1 << 30;
+    EXPECT(cargs(g, 0).x_bytes == 0x80000000u && !spk_below_2gib(cargs(g, 0)));
+    g = {1, 1, 1, 64, 1, (1 << 24) - 1, 64, 64, 64, 64, 1, 1, 0};           // y: 2^24 - 1 pixels of 64 channels, then 2^24
+    EXPECT(spk_below_2gib(cargs(g, 0)) && spk_below_2gib(pw_args(cargs(g, 0), Wt)) && spk_below_2gib(c3_args(cargs(g, 0), Wt, 1)));
+    g.Wo = 1 << 24;
+    EXPECT(!spk_below_2gib(cargs(g, 0)) && !spk_below_2gib(pw_args(cargs(g, 0), Wt)) && !spk_below_2gib(c3_args(cargs(g, 0), Wt, 1)));
+    EXPECT(spk_below_2gib(spk_bneck_args(X, Y, Wt, Wt, Wt, S, B, S, B, S, B, 1, 1, (1 << 22) - 1, 64)));
+    EXPECT(!spk_below_2gib(spk_bneck_args(X, Y, Wt, Wt, Wt, S, B, S, B, S, B, 1, 1, 1 << 22, 64)));
+    EXPECT(!spk_below_2gib(spk_bneck_args(X, Y, Wt, Wt, Wt, S, B, S, B, S, B, 64, 1 << 10, 1 << 10, 64)));   // 2^35 bytes
+  }
+}
+
 int main(int argc, char** argv) {
   int ndev = 0;
   const bool gpu = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
   printf("asan_driver: %d GPU(s)\n", gpu ? ndev : 0);
   graph_checks();
   cursor_checks();
+  descriptor_checks();
 
   // ---- argument errors ----
   spk_model* m = nullptr;
@@ -539,25 +616,13 @@ int main(int argc, char** argv) {
     (void)hipMemset(wp, 0, (size_t)256 * 9 * cin * 4);
     (void)hipMemset(sb, 0, (size_t)2 * 256 * 4);
   }
-  ConvArgs a;
-  memset(&a, 0, sizeof a);
-  a.cfg = a.dma = -1; a.cls_ph = a.cls_pw = -1;
-  a.x = x; a.w = wp; a.y = y; a.scale = sb; a.bias = sb ? sb + cout : nullptr;
-  a.N = n; a.H = h; a.W = wd; a.Cin = cin; a.Ho = h; a.Wo = wd; a.Cout = cout; a.kh = a.kw = 1; a.stride = 1; a.M = M;
-  a.K = cin; a.relu = 1; a.dt = DT_F16; a.splitw = 1;
-  a.x_bytes = (unsigned)((size_t)M * cin * 2); a.w_bytes = (unsigned)((size_t)cout * cin * 4);
-  PwConvArgs q;
-  memset(&q, 0, sizeof q);
-  q.x = x; q.wp = wp; q.y = y; q.scale = sb; q.shift = sb ? sb + cout : nullptr;
-  q.N = n; q.H = h; q.W = wd; q.Ho = h; q.Wo = wd; q.stride = 1; q.Cin = cin; q.Cout = cout; q.M = M; q.relu = 1;
-  q.dt = DT_F16; q.nb = 2; q.x_bytes = a.x_bytes; q.y_bytes = (unsigned)((size_t)M * cout * 2);
+  const float* sh = sb ? sb + cout : nullptr;
+  const ConvArgs a = spk_conv_args(spk_conv_geom(n, h, wd, cin, cout, 1, 1, 0), x, wp, y, nullptr, sb, sh, 1, DT_F16, 1);
+  const PwConvArgs q = pw_args(a, wp);
   const int r1 = spk_conv1x1_launch(a, q, nullptr);               // not tuned, no tuning: the implicit GEMM, nothing stored
   EXPECT(gpu ? r1 == 0 : r1 != 0);
-  C3Args c;
-  memset(&c, 0, sizeof c);
-  c.x = x; c.wp = wp; c.y = y; c.scale = sb; c.shift = sb ? sb + 256 : nullptr;
-  c.N = n; c.H = h; c.W = wd; c.Cin = cin; c.Cout = 256; c.M = M; c.relu = 1; c.dt = DT_F16; c.nb = 1;
-  c.x_bytes = a.x_bytes; c.y_bytes = (unsigned)((size_t)M * 256 * 2); c.wp_bytes = (unsigned)((size_t)256 * 9 * cin * 2);
+  const C3Args c = c3_args(spk_conv_args(spk_conv_geom(n, h, wd, cin, 256, 3, 1, 1), x, nullptr, y, nullptr, sb,
+                                         sb ? sb + 256 : nullptr, 1, DT_F16, 0), wp, 1);
   const int r3 = spk_conv3x3_launch(c, nullptr);                  // not tuned, no tuning: the first configuration that launches
   EXPECT(gpu ? r3 == 0 : r3 != 0);
   if (gpu) {

@@ -9,7 +9,7 @@ FL="--offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -Wno-unused-result -Wno-unused
 pids=()
 for f in model.hip model_graph.hip model_params.hip model_pack.hip train.hip ops_abi.hip conv_igemm.hip conv_pw.hip conv_pwr.hip conv_c3.hip conv_d3.hip conv_bneck.hip conv_stem.hip conv_wgrad.hip conv_group.hip pointwise.hip effnet.hip pw_fp8.hip dwconv_lds.hip preprocess.hip augment.hip head.hip train_kernels.hip train_effnet.hip zero_sum.hip tta.hip asan_driver.hip; do
   o=build/asan/${f%.hip}.o
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ spk_common.h -nt "$o" ] || [ model.h -nt "$o" ] || [ ../../include/sykepic_hip.h -nt "$o" ] || [ tune_table.h -nt "$o" ] || [ tune_pair.h -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ spk_common.h -nt "$o" ] || [ conv_args.h -nt "$o" ] || [ model.h -nt "$o" ] || [ ../../include/sykepic_hip.h -nt "$o" ] || [ tune_table.h -nt "$o" ] || [ tune_pair.h -nt "$o" ]; then
     hipcc $FL -c "$f" -o "$o" 2> "$o.log" &
     pids+=($!)
   fi

@@ -62,7 +62,7 @@ struct BnCfg {
   static constexpr int DI = (WM * MT1 * 2 + NW - 1) / NW;   // LDS-DMA instructions (8 rows x 128 B) per wave and x chunk
   static constexpr int XSTAGE = DI * NW * 1024;
   // x ring stages (the ring lives in the window's space).  Three only in the 8-wave form: with three stages the weight
-  // fragments of phase 1 are loaded by instructions the compiler does not track (buffer_load_b128_untracked), which must
+  // fragments of phase 1 are loaded by instructions the compiler does not track (buffer_load_b128_untracked, spk_common.h), which must
   // never be spilled - the 4-wave instantiations sit at the 256-register limit and do spill a few values
   static constexpr int NXS = (NW == 8 && 3 * XSTAGE <= cmax(WIN, 96 * 1024)) ? 3 : 2;
   static constexpr int REGION = cmax(WIN, NXS * XSTAGE);
@@ -78,25 +78,13 @@ struct BnCfg {
   static_assert(HW % R == 0, "bands tile the image");
   static_assert(NW % WN == 0 && (NW == 4 || NW == 8), "waves");
   static_assert(LDS <= 160 * 1024 && (NW == 8 || LDS <= 80 * 1024), "LDS");
+  static_assert(DI + 8 <= 63, "vmcnt is a 6-bit counter");
 };
 
 // two clamped floats -> one dword of two fp16 values
 __device__ __forceinline__ unsigned int pack2h(float lo, float hi) {
   const f32x2_t v = {lo, hi};
   return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, f16x2_t));
-}
-
-// A 16-byte buffer load the compiler's s_waitcnt pass does not see (phase 1's weight fragments).  hipcc 7.2 does not count
-// LDS-DMA instructions when it derives the vmcnt of a register load's first use, so with builtin loads next to the DMAs it
-// waits for "all but N" with an N that is too small by the DMAs issued in between - i.e. for the x chunk still in flight.
-// The caller orders these loads with its own s_waitcnt (the same that publishes the DMA pieces).
-__device__ __forceinline__ u32x4_t buffer_load_b128_untracked(u32x4_t rsrc, unsigned voff, unsigned soff, int imm) {
-  u32x4_t d;
-  if (imm == 0) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(d) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-  else if (imm == 1024) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:1024" : "=v"(d) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-  else if (imm == 2048) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:2048" : "=v"(d) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-  else asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:3072" : "=v"(d) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-  return d;
 }
 
 template <int CM, int HW, int R, int NW>

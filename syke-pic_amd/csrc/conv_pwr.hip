@@ -37,18 +37,6 @@ __device__ __forceinline__ unsigned int pack2h_nosat(float lo, float hi) {
   return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, f16x2_t));
 }
 
-// A 16-byte buffer load the compiler's s_waitcnt pass does not see (conv_bneck.hip explains: hipcc 7.2 does not count
-// LDS-DMA instructions when it derives the vmcnt of a register load's first use).  Ordered by the kernel's own s_waitcnt;
-// the destination registers must never be spilled or copied before that wait ("VGPRs Spill: 0" for every instantiation).
-__device__ __forceinline__ u32x4_t buffer_load_b128_untracked(u32x4_t rsrc, unsigned voff, unsigned soff, int imm) {
-  u32x4_t d;
-  if (imm == 0) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(d) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-  else if (imm == 1024) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:1024" : "=v"(d) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-  else if (imm == 2048) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:2048" : "=v"(d) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-  else asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:3072" : "=v"(d) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-  return d;
-}
-
 template <int MT_, int WN_, int D_>
 struct PwrCfg {
   static constexpr int MT = MT_, WN = WN_, D = D_, NW = 8, WM = NW / WN;   // D: chunks the memory system runs ahead of the MFMAs

@@ -3,6 +3,7 @@
 // Public contract and the reference lines each entry point replaces:
 // include/sykepic_hip.h.
 #include "model.h"
+#include "conv_args.h"
 #include "tune_pair.h"
 
 #include <algorithm>
@@ -240,35 +241,32 @@ static int chain_choice(spk_model* m, Layer& L, const PwConvArgs& q, const EvalC
   return choice;
 }
 
-// fills the chained conv's fields of q; false: shapes the kernel does not cover
-static bool chain_args(spk_model* m, const Layer& L, PwConvArgs& q, const EvalCursor& c) {
+// the conv that L's kernel can compute from its own output tile; null: shapes the chained kernels do not cover
+static const Layer* chain_target(spk_model* m, const Layer& L) {
   const Layer& Q = m->layers[L.chain_next];
   const TDim& zo = m->tdims[Q.d.dst];
   const TDim& o = m->tdims[L.d.dst];
-  if (zo.h != o.h || zo.w != o.w || zo.c != Q.d.cout || Q.d.cin != L.d.cout) return false;
-  q.wpz = m->wpack + Q.wpw_off;
-  q.z = (bf16_t*)m->TI(c, Q.d.dst);
-  q.scalez = m->scale_bias + Q.sb_off;
-  q.shiftz = q.scalez + Q.cout_p;
-  q.Coutz = Q.d.cout;
-  q.reluz = Q.d.relu;
-  q.z_bytes = (unsigned)((size_t)c.n * zo.h * zo.w * zo.c * 2);
+  return zo.h != o.h || zo.w != o.w || zo.c != Q.d.cout || Q.d.cin != L.d.cout ? nullptr : &Q;
+}
+
+// fills the chained conv's fields of q; false: shapes the kernel does not cover
+static bool chain_args(spk_model* m, const Layer& L, PwConvArgs& q, const EvalCursor& c) {
+  const Layer* Q = chain_target(m, L);
+  if (!Q) return false;
+  const float* sz = m->scale_bias + Q->sb_off;
+  spk_pw_set_chain(q, m->wpack + Q->wpw_off, (bf16_t*)m->TI(c, Q->d.dst), sz, sz + Q->cout_p, Q->d.cout, Q->d.relu);
   return true;
 }
 
-static void bneck_args(spk_model* m, const Layer& L, BneckArgs& a, const EvalCursor& c) {
+// the identity bottleneck whose first conv is L (pass_bottlenecks: 4 * L.d.cout trunk channels)
+static BneckArgs bneck_args(spk_model* m, const Layer& L, const EvalCursor& c) {
   const Layer& L2 = m->layers[L.bn_c2];
   const Layer& L3 = m->layers[L.bn_c3];
   const TDim& in = m->tdims[L.d.src];
-  memset(&a, 0, sizeof a);
-  a.x = (const bf16_t*)m->TI(c, L.d.src);
-  a.y = (bf16_t*)m->TI(c, L3.d.dst);
-  a.w1 = m->wpack + L.wpw_off; a.w2 = m->wpack + L2.wpw_off; a.w3 = m->wpack + L3.wpw_off;
-  a.s1 = m->scale_bias + L.sb_off; a.b1 = a.s1 + L.cout_p;
-  a.s2 = m->scale_bias + L2.sb_off; a.b2 = a.s2 + L2.cout_p;
-  a.s3 = m->scale_bias + L3.sb_off; a.b3 = a.s3 + L3.cout_p;
-  a.N = c.n; a.H = in.h; a.W = in.w; a.C4 = L.d.cin; a.CM = L.d.cout;
-  a.x_bytes = (unsigned)((size_t)c.n * in.h * in.w * in.c * 2);
+  const float *s1 = m->scale_bias + L.sb_off, *s2 = m->scale_bias + L2.sb_off, *s3 = m->scale_bias + L3.sb_off;
+  return spk_bneck_args((const bf16_t*)m->TI(c, L.d.src), (bf16_t*)m->TI(c, L3.d.dst), m->wpack + L.wpw_off,
+                        m->wpack + L2.wpw_off, m->wpack + L3.wpw_off, s1, s1 + L.cout_p, s2, s2 + L2.cout_p, s3,
+                        s3 + L3.cout_p, c.n, in.h, in.w, L.d.cout);
 }
 
 static int bneck_choice_paired(spk_model* m, Layer& L, const BneckArgs& a, const EvalCursor& c, unsigned allow, int* choice);
@@ -356,18 +354,14 @@ static int conv_block_tail(spk_model* m, Layer& L, const EvalCursor& c, unsigned
   if (!btail_possible(m, L, allow)) return FORM_PASS;
   const Layer& H = m->layers[L.bn_head];
   const Layer& L3 = m->layers[H.bn_c3];
-  BneckArgs ba;
-  bneck_args(m, H, ba, c);   // (the block's input is conv3's shortcut operand; w1 is not used)
+  BneckArgs ba = bneck_args(m, H, c);   // (the block's input is conv3's shortcut operand; w1 is not used)
   ba.y1 = (const bf16_t*)m->TI(c, L.d.src);
-  bool chained = false;
-  if (chain_possible(m, L3, allow)) {   // the next block's first conv from the output tile in registers, as conv_pw.hip's chained flavour
-    PwConvArgs qc;
-    memset(&qc, 0, sizeof qc);
-    if (chain_args(m, L3, qc, c)) {
-      ba.wz = qc.wpz; ba.z = qc.z; ba.sz = qc.scalez; ba.bz = qc.shiftz; ba.Coutz = qc.Coutz; ba.z_bytes = qc.z_bytes;
-      chained = qc.reluz == 1;
-      if (!chained) ba.wz = nullptr;
-    }
+  // the next block's first conv from the output tile in registers, as conv_pw.hip's chained flavour
+  const Layer* Q = chain_possible(m, L3, allow) ? chain_target(m, L3) : nullptr;
+  bool chained = Q && Q->d.relu == 1;
+  if (chained) {
+    const float* sz = m->scale_bias + Q->sb_off;
+    spk_bneck_set_chain(ba, m->wpack + Q->wpw_off, (bf16_t*)m->TI(c, Q->d.dst), sz, sz + Q->cout_p, Q->d.cout);
   }
   int r = spk_btail_launch(ba, c.stream);
   if (r == -3 && chained) {      // (no instantiation with this chained width: without it)
@@ -389,8 +383,7 @@ static int conv_block_tail(spk_model* m, Layer& L, const EvalCursor& c, unsigned
 // the whole identity bottleneck whose first conv is L: conv_bneck.hip
 static int conv_whole_block(spk_model* m, Layer& L, const EvalCursor& c, unsigned allow) {
   if (!bneck_possible(m, L, allow)) return FORM_PASS;
-  BneckArgs ba;
-  bneck_args(m, L, ba, c);
+  BneckArgs ba = bneck_args(m, L, c);
   const int form = bneck_choice(m, L, ba, c, allow);
   if (!form) return FORM_PASS;
   if (form == 2) ba.flags |= 4;
@@ -425,56 +418,19 @@ static int conv_grouped(spk_model* m, const Layer& L, const EvalCursor& c) {
   return SPK_OK;
 }
 
-// the implicit GEMM's arguments: what every dense form below starts from
-static void conv_args(spk_model* m, const Layer& L, const EvalCursor& c, ConvArgs& a) {
+// the implicit GEMM's arguments: what every dense form below starts from (pw_args / c3_args of conv_args.h derive theirs)
+static ConvArgs conv_args(spk_model* m, const Layer& L, const EvalCursor& c) {
   const TDim& in = m->tdims[L.d.src];
   const TDim& o = m->tdims[L.d.dst];
-  memset(&a, 0, sizeof a);
-  a.cfg = a.dma = -1;
-  a.cls_ph = a.cls_pw = -1;
-  a.x = (const bf16_t*)m->TI(c, L.d.src);
-  a.w = m->wpack + L.wpack_off;
-  a.y = (bf16_t*)m->TI(c, L.d.dst);
-  a.res = L.d.res >= 0 ? (const bf16_t*)m->TI(c, L.d.res) : nullptr;
+  const float* scale = m->scale_bias + L.sb_off;
+  const ConvGeom g = {c.n, in.h, in.w, in.c, o.h, o.w, o.c, L.mode == CONV_MODE_GENERIC ? L.cin_p : in.c, L.cout_p, L.kpad,
+                      L.d.k, L.d.stride, L.d.pad};
+  ConvArgs a = spk_conv_args(g, (const bf16_t*)m->TI(c, L.d.src), m->wpack + L.wpack_off, (bf16_t*)m->TI(c, L.d.dst),
+                             L.d.res >= 0 ? (const bf16_t*)m->TI(c, L.d.res) : nullptr, scale, scale + L.cout_p, L.d.relu,
+                             m->infer_dt, layer_split(m, L));
   a.res_lo = L.d.res >= 0 ? (const bf16_t*)m->TLo(L.d.res) : nullptr;
   a.y_lo = (bf16_t*)m->TLo(L.d.dst);
-  a.scale = m->scale_bias + L.sb_off;
-  a.bias = a.scale + L.cout_p;
-  a.N = c.n; a.H = in.h; a.W = in.w; a.Cin = L.mode == CONV_MODE_GENERIC ? L.cin_p : in.c;
-  a.Ho = o.h; a.Wo = o.w; a.Cout = L.cout_p;
-  a.cin_s = in.c != a.Cin ? in.c : 0;       // EfficientNet: tensors are not padded, the GEMM is
-  a.cout_s = o.c != a.Cout ? o.c : 0;
-  a.kh = a.kw = L.d.k; a.stride = L.d.stride; a.pad = L.d.pad;
-  a.M = c.n * o.h * o.w;
-  a.K = L.kpad;
-  a.relu = L.d.relu;
-  a.dt = m->infer_dt;
-  a.splitw = layer_split(m, L);
-  a.x_bytes = (unsigned)((size_t)c.n * in.h * in.w * in.c * 2);
-  a.w_bytes = (unsigned)((size_t)L.cout_p * L.kpad * 2 * (a.splitw ? 2 : 1));
-}
-
-// the same conv for conv_pw.hip (wp: its fragment-ordered weights) ...
-static PwConvArgs pw_args(const ConvArgs& a, const bf16_t* wp) {
-  PwConvArgs q;
-  memset(&q, 0, sizeof q);
-  q.x = a.x; q.wp = wp; q.y = a.y; q.res = a.res; q.scale = a.scale; q.shift = a.bias;
-  q.N = a.N; q.H = a.H; q.W = a.W; q.Ho = a.Ho; q.Wo = a.Wo; q.stride = a.stride;
-  q.Cin = a.Cin; q.Cout = a.Cout; q.M = a.M; q.relu = a.relu; q.dt = DT_F16; q.nb = a.splitw ? 2 : 1;
-  q.x_bytes = a.x_bytes; q.y_bytes = (unsigned)((size_t)a.M * a.Cout * 2);
-  return q;
-}
-
-// ... and for conv_c3.hip / conv_d3.hip (nbw weight images at wp)
-static C3Args c3_args(const ConvArgs& a, const bf16_t* wp, int nbw) {
-  C3Args q;
-  memset(&q, 0, sizeof q);
-  q.x = a.x; q.wp = wp; q.y = a.y; q.scale = a.scale; q.shift = a.bias; q.res = a.res;
-  q.N = a.N; q.H = a.H; q.W = a.W; q.Cin = a.Cin; q.Cout = a.Cout; q.M = a.M; q.relu = a.relu; q.dt = DT_F16;
-  q.nb = nbw;
-  q.x_bytes = a.x_bytes; q.y_bytes = (unsigned)((size_t)a.M * a.Cout * 2);
-  q.wp_bytes = (unsigned)((size_t)a.Cout * 9 * a.Cin * 2 * q.nb);
-  return q;
+  return a;
 }
 
 // the chained flavour of the block-closing conv's launch q: true when it ran - the next block's first conv is done
@@ -499,8 +455,7 @@ static int conv_dual(spk_model* m, Layer& L, const EvalCursor& c, unsigned allow
   PwConvArgs q = pw_args(a, m->wdual + L.wdual_off);   // (stride 1: what the pairing asks of L)
   q.res = nullptr;
   q.scale = m->sdual + L.sdual_off; q.shift = q.scale + L.d.cout;
-  q.x2 = (const bf16_t*)m->TI(c, D.d.src); q.Cin2 = D.d.cin; q.H2 = din.h; q.W2 = din.w; q.stride2 = D.d.stride;
-  q.x2_bytes = (unsigned)((size_t)c.n * din.h * din.w * din.c * 2);
+  spk_pw_set_second(q, (const bf16_t*)m->TI(c, D.d.src), D.d.cin, din.h, din.w, D.d.stride);
   if (conv_chained(m, L, q, c, allow)) return SPK_OK;
   const int r = spk_conv1x1_dual_launch(q, c.stream);
   if (r == 0) {
@@ -554,8 +509,7 @@ static int run_conv_eval(spk_model* m, Layer& L, const EvalCursor& c, unsigned a
   }
   if (L.mode == CONV_MODE_STEM3) return conv_stem3(m, L, c);
   if (L.mode == CONV_MODE_GROUP) return conv_grouped(m, L, c);
-  ConvArgs a;
-  conv_args(m, L, c, a);
+  ConvArgs a = conv_args(m, L, c);
   if (L.gate_from >= 0 && (allow & EVAL_FORWARD) && (carry.ran[L.gate_from].form & EF_GATES)) {
     // the squeeze-excitation layer in front left its gates instead of the scaled tensor: read what IT read
     if (!carry.gate) return spk_fail(SPK_ERR_STATE, std::string("no squeeze-excitation gates for ") + L.d.name);

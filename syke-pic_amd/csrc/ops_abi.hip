@@ -1,6 +1,6 @@
 // Single-operator entry points of the C-ABI (include/sykepic_hip.h, "test hooks: single operators").
-// Each one runs exactly the launches a training step makes for ONE layer (the shared helpers of train.hip and
-// the spk_launch_* functions), on caller-provided device buffers, so that a parity test can hand a kernel
+// Each one runs the launches a training step or the eval executor makes for ONE layer (the shared helpers of train.hip
+// and the spk_launch_* functions), on caller-provided device buffers, so that a parity test can hand a kernel
 // known operands and compare its output with autograd evaluated on the same (bf16-rounded) operands:
 //   conv + train-mode BatchNorm forward   torch Conv2d + BatchNorm2d(+add)(+ReLU), sykepic/train/train.py:240
 //   BatchNorm / conv backward             what loss.backward() runs for that layer,  sykepic/train/train.py:242
@@ -9,8 +9,12 @@
 //                                          spk_op_cross_entropy_pair (the Mixup / CutMix criterion on two label vectors)
 //   MaxPool2d / AdaptiveAvgPool2d(1)       spk_op_maxpool, spk_op_maxpool_backward, spk_op_gavgpool, spk_op_gavgpool_backward
 //                                          (head.hip, pointwise.hip, train_kernels.hip; exact integer and float64 references)
+// The dense conv kernels' argument descriptors come from the builders of conv_args.h, the ones model.hip and train.hip
+// call: a hook resolves its own pointers and shape and derives PwConvArgs / C3Args from the ConvArgs as the executor
+// does, so the extents, the stem's row pitch and the padding rules a test judges are those of a real forward or step.
 // Scratch is allocated and freed inside the call (these are not on any hot path).
 #include "model.h"
+#include "conv_args.h"
 #include "train_effnet.h"
 #include "tune_table.h"
 
@@ -43,6 +47,9 @@ bool stem_shape(int cin, int cout, int k, int stride, int pad) {
   do {                                                                            \
     if ((expr) != 0) return ofail(SPK_ERR_HIP, std::string(what) + " failed");    \
   } while (0)
+
+// the end of a hook: its launches have run when it returns, and a fault in one of them is this hook's error
+#define O_SYNC(s, msg) do { if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, msg); } while (0)
 
 // an implicit-GEMM launch: -3 is a candidate pinned by spk_op_conv_pin that is not instantiated for the problem
 #define O_CONV(expr, what)                                                                                      \
@@ -90,28 +97,17 @@ extern "C" int spk_op_conv_bn_train_forward(const void* x, const float* w_ohwi, 
   const bool stem = stem_shape(cin, cout, k, stride, pad);
   if ((!stem && (cin % 64 || cin < 64)) || cout % 64) return ofail(SPK_ERR_UNSUPPORTED, "channels must be multiples of 64 (or the 7x7/2 stem)");
   hipStream_t s = (hipStream_t)stream;
-  const int oh = (h + 2 * pad - k) / stride + 1, ow = (w + 2 * pad - k) / stride + 1;
-  const int M = n * oh * ow;
-  const int kpad = stem ? 256 : k * k * cin;
+  const ConvGeom g = stem ? spk_stem_geom(n, h, w) : spk_conv_geom(n, h, w, cin, cout, k, stride, pad);
+  const int M = n * g.Ho * g.Wo;
   Scratch sc;
-  bf16_t* wp = sc.get<bf16_t>((size_t)cout * kpad);
+  bf16_t* wp = sc.get<bf16_t>((size_t)cout * g.K);
   float* part = sc.get<float>((size_t)((M + 60) / 61) * 2 * cout);
   float* st = sc.get<float>((size_t)2 * cout);
   float* tmp = sc.get<float>((size_t)cout * 2 * 64);
   if (!wp || !part || !st || !tmp) return ofail(SPK_ERR_HIP, "hipMalloc failed");
   O_TRY(spk_launch_pack_weights(w_ohwi, wp, cout, k, k, cin, stem ? CONV_MODE_STEM : CONV_MODE_GENERIC, DT_BF16, 0, s),
         "pack_weights");
-  ConvArgs a;
-  memset(&a, 0, sizeof a);
-  a.cfg = a.dma = -1;
-  a.cls_ph = a.cls_pw = -1;
-  a.x = (const bf16_t*)x; a.w = wp; a.y = (bf16_t*)raw;
-  const int wst = stem ? (w + 1) & ~1 : w;  // the stem input is stored with an even row pitch (zero pad column)
-  a.N = n; a.H = h; a.W = wst; a.Cin = stem ? 4 : cin; a.Ho = oh; a.Wo = ow; a.Cout = cout;
-  a.kh = a.kw = k; a.stride = stride; a.pad = pad;
-  a.M = M; a.K = kpad; a.dt = DT_BF16;
-  a.x_bytes = (unsigned)((size_t)n * h * wst * a.Cin * 2);
-  a.w_bytes = (unsigned)((size_t)cout * kpad * 2);
+  ConvArgs a = spk_conv_args(g, (const bf16_t*)x, wp, (bf16_t*)raw, nullptr, nullptr, nullptr, 0, DT_BF16, 0);
   a.stats = part;
   int m_tiles = 0;
   O_CONV(spk_conv_launch(a, stem ? CONV_MODE_STEM : CONV_MODE_GENERIC, s, &m_tiles), "conv launch");
@@ -119,7 +115,7 @@ extern "C" int spk_op_conv_bn_train_forward(const void* x, const float* w_ohwi, 
                                mean_invstd + cout, st, st + cout, 1e-5f, 0.1f, tmp, s), "bn_finalize");
   O_TRY(spk_launch_bn_apply((const bf16_t*)raw, st, st + cout, (const bf16_t*)res, (bf16_t*)out, mask,
                             (size_t)M * cout, cout, relu, s), "bn_apply");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_conv_bn_train_forward: kernel failed");
+  O_SYNC(s, "op_conv_bn_train_forward: kernel failed");
   return SPK_OK;
 }
 
@@ -138,7 +134,7 @@ extern "C" int spk_op_bn_backward(const void* g, const unsigned char* mask, cons
   if (!part || !coef || !tmp) return ofail(SPK_ERR_HIP, "hipMalloc failed");
   O_TRY(spk_launch_bn_bwd((const bf16_t*)g, mask, (const bf16_t*)raw, mean, invstd, gamma, part, coef, dgamma, dbeta,
                           (bf16_t*)dy, (bf16_t*)g_res, res_accumulate, M, C, relu, tmp, s), "bn_bwd");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_bn_backward: kernel failed");
+  O_SYNC(s, "op_bn_backward: kernel failed");
   return SPK_OK;
 }
 
@@ -155,7 +151,7 @@ extern "C" int spk_op_conv_dgrad(const void* dy, const float* w_ohwi, void* dx, 
   const int r = spk_conv_dgrad_all((const bf16_t*)dy, wdg, (bf16_t*)dx, accumulate != 0, n, oh, ow, cout, h, w, cin, k,
                                    stride, pad, s);
   if (r != SPK_OK) return r;
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_conv_dgrad: kernel failed");
+  O_SYNC(s, "op_conv_dgrad: kernel failed");
   return SPK_OK;
 }
 
@@ -192,7 +188,7 @@ extern "C" int spk_op_conv_dgrad_bn_backward(const void* dy, const float* w_ohwi
   if (fz.tiles < 1) return ofail(SPK_ERR_HIP, "the dgrad launch reported no partial rows");
   O_TRY(spk_launch_bn_bwd((const bf16_t*)dx, mask, (const bf16_t*)raw, mean, invstd, gamma, part, coef, dgamma, dbeta,
                           (bf16_t*)dy_prod, nullptr, 0, M, cin, relu, tmp, s, fz.tiles), "bn_bwd");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_conv_dgrad_bn_backward: kernel failed");
+  O_SYNC(s, "op_conv_dgrad_bn_backward: kernel failed");
   return SPK_OK;
 }
 
@@ -212,7 +208,7 @@ extern "C" int spk_op_conv_wgrad(const void* x, const void* dy, float* dw_ohwi, 
   if (r != SPK_OK) return r;
   r = spk_conv_wgrad_reduce(slabs, dw_ohwi, M, cin, cout, k, stem, s);
   if (r != SPK_OK) return r;
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_conv_wgrad: kernel failed");
+  O_SYNC(s, "op_conv_wgrad: kernel failed");
   return SPK_OK;
 }
 
@@ -240,7 +236,7 @@ extern "C" int spk_op_pw_fp8(const void* x, int a_fp8, const float* w, void* y, 
                                   kpad, npad, cin, cout, act, 1.f / a_scale, 1.f / y_scale, s);
   if (r == -2) return ofail(SPK_ERR_UNSUPPORTED, "op_pw_fp8: shape not supported (cin % 8 / 16, cout % 8)");
   if (r) return ofail(SPK_ERR_HIP, "op_pw_fp8: launch failed");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_pw_fp8: kernel failed");
+  O_SYNC(s, "op_pw_fp8: kernel failed");
   return SPK_OK;
 }
 
@@ -267,7 +263,7 @@ extern "C" int spk_op_dwconv(const void* x, const float* w, const float* bn_scal
     r = spk_launch_dwconv((const bf16_t*)x, wt, bn_scale, bn_bias, (bf16_t*)y, partial, n, h, wid, c, ho, wo, k, stride, act,
                           DT_F16, s);
   if (r) return ofail(SPK_ERR_HIP, "op_dwconv: launch failed");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_dwconv: kernel failed");
+  O_SYNC(s, "op_dwconv: kernel failed");
   if (pool_out) {
     std::vector<float> hp((size_t)n * chunks * c), out((size_t)n * c, 0.f);
     if (hipMemcpy(hp.data(), partial, hp.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return ofail(SPK_ERR_HIP, "copy failed");
@@ -290,41 +286,25 @@ extern "C" int spk_op_conv1x1(const void* x, const float* w, const float* bn_sca
     return ofail(SPK_ERR_ARG, "op_conv1x1: bad arguments");
   if (cin % 64 || cout % 64) return ofail(SPK_ERR_UNSUPPORTED, "channels must be multiples of 64");
   hipStream_t s = (hipStream_t)stream;
-  const int ho = (h - 1) / stride + 1, wo = (wd - 1) / stride + 1, M = n * ho * wo;
-  // 32-bit buffer offsets in both kernels: every operand below 2 GiB (the model executor micro-batches for this)
-  if ((size_t)n * h * wd * cin * 2 >= 0x80000000ull || (size_t)n * ho * wo * cout * 2 >= 0x80000000ull)
-    return ofail(SPK_ERR_UNSUPPORTED, "op_conv1x1: an operand of 2 GiB or more (split the batch)");
   Scratch sc;
   bf16_t* wp = sc.get<bf16_t>((size_t)2 * cout * cin);
   if (!wp) return ofail(SPK_ERR_HIP, "hipMalloc failed");
+  const ConvArgs a = spk_conv_args(spk_conv_geom(n, h, wd, cin, cout, 1, stride, 0), (const bf16_t*)x, wp, (bf16_t*)y,
+                                   (const bf16_t*)res, bn_scale, bn_bias, relu, DT_F16, split != 0);
+  // 32-bit buffer offsets in both kernels: every operand below 2 GiB (the model executor micro-batches for this)
+  if (!spk_below_2gib(a)) return ofail(SPK_ERR_UNSUPPORTED, "op_conv1x1: an operand of 2 GiB or more (split the batch)");
   int r;
   if (cfg < 0) {
     O_TRY(spk_launch_pack_weights(w, wp, cout, 1, 1, cin, CONV_MODE_GENERIC, DT_F16, split != 0, s), "pack_weights");
-    ConvArgs a;
-    memset(&a, 0, sizeof a);
-    a.cfg = a.dma = -1;
-    a.cls_ph = a.cls_pw = -1;
-    a.x = (const bf16_t*)x; a.w = wp; a.y = (bf16_t*)y; a.res = (const bf16_t*)res; a.scale = bn_scale; a.bias = bn_bias;
-    a.N = n; a.H = h; a.W = wd; a.Cin = cin; a.Ho = ho; a.Wo = wo; a.Cout = cout;
-    a.kh = a.kw = 1; a.stride = stride; a.M = M; a.K = cin; a.relu = relu; a.dt = DT_F16; a.splitw = split != 0;
-    a.x_bytes = (unsigned)((size_t)n * h * wd * cin * 2);
-    a.w_bytes = (unsigned)((size_t)cout * cin * 2 * (split ? 2 : 1));
     O_CONV(spk_conv_launch(a, CONV_MODE_GENERIC, s, nullptr), "conv1x1 launch");
     r = 0;
   } else {
     O_TRY(spk_launch_pack_pw(w, nullptr, wp, cout, cin, DT_F16, split ? 2 : 1, s), "pack_pw");
-    PwConvArgs q;
-    memset(&q, 0, sizeof q);
-    q.x = (const bf16_t*)x; q.wp = wp; q.y = (bf16_t*)y; q.res = (const bf16_t*)res; q.scale = bn_scale; q.shift = bn_bias;
-    q.N = n; q.H = h; q.W = wd; q.Ho = ho; q.Wo = wo; q.stride = stride; q.Cin = cin; q.Cout = cout; q.M = M;
-    q.relu = relu; q.dt = DT_F16; q.nb = split ? 2 : 1;
-    q.x_bytes = (unsigned)((size_t)n * h * wd * cin * 2);
-    q.y_bytes = (unsigned)((size_t)M * cout * 2);
-    r = spk_pw_launch(q, cfg, s);
+    r = spk_pw_launch(pw_args(a, wp), cfg, s);
     if (r == -3) return ofail(SPK_ERR_UNSUPPORTED, "this configuration does not fit the problem");
   }
   if (r) return ofail(SPK_ERR_HIP, "conv1x1 launch failed");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "conv1x1 kernel failed");
+  O_SYNC(s, "conv1x1 kernel failed");
   return SPK_OK;
 }
 extern "C" int spk_op_conv1x1_num_configs(void) { return spk_pw_num_configs(); }
@@ -342,29 +322,23 @@ extern "C" int spk_op_conv1x1_dual(const void* x, const float* w1, const float* 
   if (cin % 64 || cin2 % 64 || cout % 64) return ofail(SPK_ERR_UNSUPPORTED, "channels must be multiples of 64");
   if ((ho - 1) * stride2 >= h2 || (wo - 1) * stride2 >= w2d) return ofail(SPK_ERR_ARG, "op_conv1x1_dual: second source too small");
   hipStream_t s = (hipStream_t)stream;
-  const int M = n * ho * wo, K = cin + cin2;
-  if ((size_t)M * cin * 2 >= 0x80000000ull || (size_t)n * h2 * w2d * cin2 * 2 >= 0x80000000ull || (size_t)M * cout * 2 >= 0x80000000ull)
-    return ofail(SPK_ERR_UNSUPPORTED, "op_conv1x1_dual: an operand of 2 GiB or more");
+  const int K = cin + cin2;
   Scratch sc;
   float* wcat = sc.get<float>((size_t)cout * K);
   float* sb = sc.get<float>((size_t)2 * cout);
   bf16_t* wp = sc.get<bf16_t>((size_t)2 * cout * K);
   if (!wcat || !sb || !wp) return ofail(SPK_ERR_HIP, "hipMalloc failed");
+  // the block-closing conv as the executor's conv_dual derives it (stride 1, the shortcut inside the GEMM), then the source
+  PwConvArgs q = pw_args(spk_conv_args(spk_conv_geom(n, ho, wo, cin, cout, 1, 1, 0), (const bf16_t*)x, nullptr, (bf16_t*)y,
+                                       nullptr, sb, sb + cout, relu, DT_F16, split != 0), wp);
+  spk_pw_set_second(q, (const bf16_t*)x2, cin2, h2, w2d, stride2);
+  if (!spk_below_2gib(q)) return ofail(SPK_ERR_UNSUPPORTED, "op_conv1x1_dual: an operand of 2 GiB or more");
   O_TRY(spk_launch_pw_dual_prep(w1, w2, s1, s2, b1, b2, wcat, sb, sb + cout, cout, cin, cin2, s), "pw_dual_prep");
   O_TRY(spk_launch_pack_pw(wcat, nullptr, wp, cout, K, DT_F16, split ? 2 : 1, s), "pack_pw");
-  PwConvArgs q;
-  memset(&q, 0, sizeof q);
-  q.x = (const bf16_t*)x; q.wp = wp; q.y = (bf16_t*)y; q.scale = sb; q.shift = sb + cout;
-  q.N = n; q.H = ho; q.W = wo; q.Ho = ho; q.Wo = wo; q.stride = 1; q.Cin = cin; q.Cout = cout; q.M = M;
-  q.relu = relu; q.dt = DT_F16; q.nb = split ? 2 : 1;
-  q.x_bytes = (unsigned)((size_t)M * cin * 2);
-  q.y_bytes = (unsigned)((size_t)M * cout * 2);
-  q.x2 = (const bf16_t*)x2; q.Cin2 = cin2; q.H2 = h2; q.W2 = w2d; q.stride2 = stride2;
-  q.x2_bytes = (unsigned)((size_t)n * h2 * w2d * cin2 * 2);
   const int r = spk_pw_launch(q, cfg, s);
   if (r == -3) return ofail(SPK_ERR_UNSUPPORTED, "this configuration does not fit the problem");
   if (r) return ofail(SPK_ERR_HIP, "dual conv1x1 launch failed");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "dual conv1x1 kernel failed");
+  O_SYNC(s, "dual conv1x1 kernel failed");
   return SPK_OK;
 }
 
@@ -378,28 +352,20 @@ extern "C" int spk_op_conv1x1_chain(const void* x, const float* w, const float* 
     return ofail(SPK_ERR_ARG, "op_conv1x1_chain: bad arguments");
   if (cin % 64 || cout % 64 || coutz % 32) return ofail(SPK_ERR_UNSUPPORTED, "channels must be multiples of 64");
   hipStream_t s = (hipStream_t)stream;
-  const int M = n * h * wd;
-  if ((size_t)M * cin * 2 >= 0x80000000ull || (size_t)M * cout * 2 >= 0x80000000ull)
-    return ofail(SPK_ERR_UNSUPPORTED, "op_conv1x1_chain: an operand of 2 GiB or more");
   Scratch sc, scz;
   bf16_t* wp = sc.get<bf16_t>((size_t)cout * cin);
   bf16_t* wpz = scz.get<bf16_t>((size_t)coutz * cout);
   if (!wp || !wpz) return ofail(SPK_ERR_HIP, "hipMalloc failed");
+  PwConvArgs q = pw_args(spk_conv_args(spk_conv_geom(n, h, wd, cin, cout, 1, 1, 0), (const bf16_t*)x, nullptr, (bf16_t*)y,
+                                       (const bf16_t*)res, bn_scale, bn_bias, relu, DT_F16, 0), wp);
+  spk_pw_set_chain(q, wpz, (bf16_t*)z, bnz_scale, bnz_bias, coutz, reluz);
+  if (!spk_below_2gib(q)) return ofail(SPK_ERR_UNSUPPORTED, "op_conv1x1_chain: an operand of 2 GiB or more");
   O_TRY(spk_launch_pack_pw(w, nullptr, wp, cout, cin, DT_F16, 1, s), "pack_pw");
   O_TRY(spk_launch_pack_pw(wz, nullptr, wpz, coutz, cout, DT_F16, 1, s), "pack_pw");
-  PwConvArgs q;
-  memset(&q, 0, sizeof q);
-  q.x = (const bf16_t*)x; q.wp = wp; q.y = (bf16_t*)y; q.res = (const bf16_t*)res; q.scale = bn_scale; q.shift = bn_bias;
-  q.N = n; q.H = h; q.W = wd; q.Ho = h; q.Wo = wd; q.stride = 1; q.Cin = cin; q.Cout = cout; q.M = M;
-  q.relu = relu; q.dt = DT_F16; q.nb = 1;
-  q.x_bytes = (unsigned)((size_t)M * cin * 2);
-  q.y_bytes = (unsigned)((size_t)M * cout * 2);
-  q.wpz = wpz; q.z = (bf16_t*)z; q.scalez = bnz_scale; q.shiftz = bnz_bias; q.Coutz = coutz; q.reluz = reluz;
-  q.z_bytes = (unsigned)((size_t)M * coutz * 2);
   const int r = spk_pw_chain_launch(q, s);
   if (r == -3) return ofail(SPK_ERR_UNSUPPORTED, "no chained kernel for this problem");
   if (r) return ofail(SPK_ERR_HIP, "chained conv1x1 launch failed");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "chained conv1x1 kernel failed");
+  O_SYNC(s, "chained conv1x1 kernel failed");
   return SPK_OK;
 }
 
@@ -412,42 +378,24 @@ extern "C" int spk_op_conv3x3(const void* x, const float* w_ohwi, const float* b
     return ofail(SPK_ERR_ARG, "op_conv3x3: bad arguments");
   if (cin % 64 || cout % 64) return ofail(SPK_ERR_UNSUPPORTED, "channels must be multiples of 64");
   hipStream_t s = (hipStream_t)stream;
-  const int M = n * h * wd;
-  if ((size_t)n * h * wd * cin * 2 >= 0x80000000ull || (size_t)n * h * wd * cout * 2 >= 0x80000000ull)
-    return ofail(SPK_ERR_UNSUPPORTED, "op_conv3x3: an operand of 2 GiB or more (split the batch)");
   Scratch sc;
   bf16_t* wp = sc.get<bf16_t>((size_t)2 * cout * 9 * cin);
   if (!wp) return ofail(SPK_ERR_HIP, "hipMalloc failed");
+  const ConvArgs a = spk_conv_args(spk_conv_geom(n, h, wd, cin, cout, 3, 1, 1), (const bf16_t*)x, wp, (bf16_t*)y,
+                                   (const bf16_t*)res, bn_scale, bn_bias, relu, DT_F16, split != 0);
+  if (!spk_below_2gib(a)) return ofail(SPK_ERR_UNSUPPORTED, "op_conv3x3: an operand of 2 GiB or more (split the batch)");
   int r;
   if (cfg < 0) {
     O_TRY(spk_launch_pack_weights(w_ohwi, wp, cout, 3, 3, cin, CONV_MODE_GENERIC, DT_F16, split != 0, s), "pack_weights");
-    ConvArgs a;
-    memset(&a, 0, sizeof a);
-    a.cfg = a.dma = -1;
-    a.cls_ph = a.cls_pw = -1;
-    a.x = (const bf16_t*)x; a.w = wp; a.y = (bf16_t*)y; a.scale = bn_scale; a.bias = bn_bias;
-    a.res = (const bf16_t*)res;
-    a.N = n; a.H = h; a.W = wd; a.Cin = cin; a.Ho = h; a.Wo = wd; a.Cout = cout;
-    a.kh = a.kw = 3; a.stride = 1; a.pad = 1; a.M = M; a.K = 9 * cin; a.relu = relu; a.dt = DT_F16; a.splitw = split != 0;
-    a.x_bytes = (unsigned)((size_t)M * cin * 2);
-    a.w_bytes = (unsigned)((size_t)cout * 9 * cin * 2 * (split ? 2 : 1));
     O_CONV(spk_conv_launch(a, CONV_MODE_GENERIC, s, nullptr), "conv3x3 launch");
     r = 0;
   } else {
     O_TRY(spk_launch_pack_c3(w_ohwi, wp, cout, cin, split ? 2 : 1, s), "pack_c3");
-    C3Args q;
-    memset(&q, 0, sizeof q);
-    q.x = (const bf16_t*)x; q.wp = wp; q.y = (bf16_t*)y; q.scale = bn_scale; q.shift = bn_bias;
-    q.N = n; q.H = h; q.W = wd; q.Cin = cin; q.Cout = cout; q.M = M; q.relu = relu; q.dt = DT_F16; q.nb = split ? 2 : 1;
-    q.x_bytes = (unsigned)((size_t)M * cin * 2);
-    q.y_bytes = (unsigned)((size_t)M * cout * 2);
-    q.wp_bytes = (unsigned)((size_t)cout * 9 * cin * 2 * q.nb);
-    q.res = (const bf16_t*)res;
-    r = spk_c3_launch(q, cfg, s);
+    r = spk_c3_launch(c3_args(a, wp, split ? 2 : 1), cfg, s);
     if (r == -3) return ofail(SPK_ERR_UNSUPPORTED, "this configuration does not fit the problem");
   }
   if (r) return ofail(SPK_ERR_HIP, "conv3x3 launch failed");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "conv3x3 kernel failed");
+  O_SYNC(s, "conv3x3 kernel failed");
   return SPK_OK;
 }
 extern "C" int spk_op_conv3x3_num_configs(void) { return spk_c3_num_configs(); }
@@ -465,33 +413,21 @@ extern "C" int spk_op_conv3x3_direct(const void* x, const float* w_ohwi, const f
   if (cfg >= 0 && (cin != 64 || cout != 64 || stride != 1 || split))
     return ofail(SPK_ERR_UNSUPPORTED, "this configuration does not fit the problem");
   hipStream_t s = (hipStream_t)stream;
-  const int ho = (h - 1) / stride + 1, wo = (wd - 1) / stride + 1, M = n * ho * wo;
-  if ((size_t)n * h * wd * cin * 2 >= 0x80000000ull || (size_t)M * cout * 2 >= 0x80000000ull)
-    return ofail(SPK_ERR_UNSUPPORTED, "op_conv3x3_direct: an operand of 2 GiB or more (split the batch)");
   Scratch sc;
   bf16_t* wp = sc.get<bf16_t>((size_t)2 * cout * 9 * cin);
   if (!wp) return ofail(SPK_ERR_HIP, "hipMalloc failed");
-  ConvArgs a;
-  memset(&a, 0, sizeof a);
-  a.cfg = a.dma = -1;
-  a.cls_ph = a.cls_pw = -1;
-  a.x = (const bf16_t*)x; a.w = wp; a.y = (bf16_t*)y; a.scale = bn_scale; a.bias = bn_bias; a.res = (const bf16_t*)res;
-  a.N = n; a.H = h; a.W = wd; a.Cin = cin; a.Ho = ho; a.Wo = wo; a.Cout = cout;
-  a.kh = a.kw = 3; a.stride = stride; a.pad = 1; a.M = M; a.K = 9 * cin; a.relu = relu; a.dt = DT_F16; a.splitw = split != 0;
-  a.x_bytes = (unsigned)((size_t)n * h * wd * cin * 2);
-  a.w_bytes = (unsigned)((size_t)cout * 9 * cin * 2 * (split ? 2 : 1));
-  C3Args q;
-  memset(&q, 0, sizeof q);
-  q.x = a.x; q.wp = wp; q.y = a.y; q.scale = bn_scale; q.shift = bn_bias; q.res = a.res;
-  q.N = n; q.H = h; q.W = wd; q.Cin = cin; q.Cout = cout; q.M = M; q.relu = relu; q.dt = DT_F16; q.nb = 1;
-  q.x_bytes = a.x_bytes; q.y_bytes = (unsigned)((size_t)M * cout * 2);
+  const ConvArgs a = spk_conv_args(spk_conv_geom(n, h, wd, cin, cout, 3, stride, 1), (const bf16_t*)x, wp, (bf16_t*)y,
+                                   (const bf16_t*)res, bn_scale, bn_bias, relu, DT_F16, split != 0);
+  if (!spk_below_2gib(a))
+    return ofail(SPK_ERR_UNSUPPORTED, "op_conv3x3_direct: an operand of 2 GiB or more (split the batch)");
+  const C3Args q = c3_args(a, wp, 1);
   if (cfg < 0) O_TRY(spk_launch_pack_weights(w_ohwi, wp, cout, 3, 3, cin, CONV_MODE_GENERIC, DT_F16, split != 0, s), "pack_weights");
   else O_TRY(spk_launch_pack_pw(w_ohwi, nullptr, wp, cout, 9 * cin, DT_F16, 1, s), "pack_pw");
   auto run = [&]() { return cfg < 0 ? spk_conv_launch(a, CONV_MODE_GENERIC, s, nullptr) : spk_d3_launch(q, cfg, s); };
   const int r = run();
   if (r == -3) return ofail(SPK_ERR_UNSUPPORTED, "this configuration does not fit the problem");
   if (r) return ofail(SPK_ERR_HIP, "conv3x3_direct launch failed");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "conv3x3_direct kernel failed");
+  O_SYNC(s, "conv3x3_direct kernel failed");
   if (iters > 0 && ms_out) {
     SpkLaunchTimer timer;
     float ms = 0.f;
@@ -518,7 +454,6 @@ extern "C" int spk_op_bottleneck(const void* x, const float* w1, const float* w2
   if (cm % 64) return ofail(SPK_ERR_UNSUPPORTED, "mid channels must be a multiple of 64");
   hipStream_t s = (hipStream_t)stream;
   const int c4 = 4 * cm, M = n * h * wd;
-  if ((size_t)M * c4 * 2 >= 0x80000000ull) return ofail(SPK_ERR_UNSUPPORTED, "op_bottleneck: an operand of 2 GiB or more");
   Scratch sc;
   bf16_t* p1 = sc.get<bf16_t>((size_t)cm * c4);
   bf16_t* p2 = sc.get<bf16_t>((size_t)9 * cm * cm);
@@ -528,27 +463,22 @@ extern "C" int spk_op_bottleneck(const void* x, const float* w1, const float* w2
   bf16_t* pz = sc.get<bf16_t>((size_t)(wz ? coutz : 1) * c4);
   if (!p1 || !p2 || !p3 || !y1 || !y2 || !pz) return ofail(SPK_ERR_HIP, "hipMalloc failed");
   if (wz && (!sz || !bz || !z || coutz % 32)) return ofail(SPK_ERR_ARG, "op_bottleneck: bad chained-conv arguments");
+  BneckArgs a = spk_bneck_args((const bf16_t*)x, (bf16_t*)y, p1, p2, p3, s1, b1, s2, b2, s3, b3, n, h, wd, cm);
+  a.stamps = stamps_dev;
+  a.y1 = y1;
+  if (wz) spk_bneck_set_chain(a, pz, (bf16_t*)z, sz, bz, coutz);
+  if (!spk_below_2gib(a)) return ofail(SPK_ERR_UNSUPPORTED, "op_bottleneck: an operand of 2 GiB or more");
   if (wz) O_TRY(spk_launch_pack_pw(wz, nullptr, pz, coutz, c4, DT_F16, 1, s), "pack_pw");
   O_TRY(spk_launch_pack_pw(w1, nullptr, p1, cm, c4, DT_F16, 1, s), "pack_pw");
   O_TRY(spk_launch_pack_c3(w2, p2, cm, cm, 1, s), "pack_c3");
   O_TRY(spk_launch_pack_pw(w3, nullptr, p3, c4, cm, DT_F16, 1, s), "pack_pw");
-  BneckArgs a;
-  memset(&a, 0, sizeof a);
-  a.x = (const bf16_t*)x; a.y = (bf16_t*)y; a.w1 = p1; a.w2 = p2; a.w3 = p3;
-  a.s1 = s1; a.b1 = b1; a.s2 = s2; a.b2 = b2; a.s3 = s3; a.b3 = b3;
-  a.N = n; a.H = h; a.W = wd; a.C4 = c4; a.CM = cm; a.x_bytes = (unsigned)((size_t)M * c4 * 2);
-  a.stamps = stamps_dev;
-  a.y1 = y1;
-  if (wz) { a.wz = pz; a.z = (bf16_t*)z; a.sz = sz; a.bz = bz; a.Coutz = coutz; a.z_bytes = (unsigned)((size_t)M * coutz * 2); }
+  // one conv of the three-launch form: k x k, stride 1, ReLU, single weight images - the executor's own derivation
+  auto conv = [&](const bf16_t* in, bf16_t* out, const bf16_t* res, const float* sc_, const float* sh_, int cin, int cout, int k) {
+    return spk_conv_args(spk_conv_geom(n, h, wd, cin, cout, k, 1, k / 2), in, nullptr, out, res, sc_, sh_, 1, DT_F16, 0);
+  };
   auto pw = [&](const bf16_t* in, const bf16_t* wp, bf16_t* out, const bf16_t* res, const float* sc_, const float* sh_, int cin,
                 int cout) {
-    PwConvArgs q;
-    memset(&q, 0, sizeof q);
-    q.x = in; q.wp = wp; q.y = out; q.res = res; q.scale = sc_; q.shift = sh_;
-    q.N = n; q.H = h; q.W = wd; q.Ho = h; q.Wo = wd; q.stride = 1; q.Cin = cin; q.Cout = cout; q.M = M;
-    q.relu = 1; q.dt = DT_F16; q.nb = 1;
-    q.x_bytes = (unsigned)((size_t)M * cin * 2);
-    q.y_bytes = (unsigned)((size_t)M * cout * 2);
+    const PwConvArgs q = pw_args(conv(in, out, res, sc_, sh_, cin, cout, 1), wp);
     for (int cfg : {7, 9, 11, 5, 1, 3, 0, 4})    // (every configuration gives the same bits: tests/test_gpu_pw.py)
       if (const int r = spk_pw_launch(q, cfg, s); r != -3) return r;
     return -3;
@@ -557,12 +487,7 @@ extern "C" int spk_op_bottleneck(const void* x, const float* w1, const float* w2
     if (fused == 1) return wz ? -3 : spk_bneck_launch(a, s);
     if (const int r = pw((const bf16_t*)x, p1, y1, nullptr, s1, b1, c4, cm)) return r;
     if (fused == 2) return spk_btail_launch(a, s);     // conv2 + conv3 + shortcut (+ the chained conv) in one kernel
-    C3Args q;
-    memset(&q, 0, sizeof q);
-    q.x = y1; q.wp = p2; q.y = y2; q.scale = s2; q.shift = b2;
-    q.N = n; q.H = h; q.W = wd; q.Cin = cm; q.Cout = cm; q.M = M; q.relu = 1; q.dt = DT_F16; q.nb = 1;
-    q.x_bytes = q.y_bytes = (unsigned)((size_t)M * cm * 2);
-    q.wp_bytes = (unsigned)((size_t)9 * cm * cm * 2);
+    const C3Args q = c3_args(conv(y1, y2, nullptr, s2, b2, cm, cm, 3), p2, 1);
     int r = -3;
     for (int cfg : {2, 0, 10, 8, 9, 3, 7})       // (likewise: tests/test_gpu_c3.py)
       if ((r = spk_c3_launch(q, cfg, s)) != -3) break;
@@ -586,7 +511,7 @@ extern "C" int spk_op_bottleneck(const void* x, const float* w1, const float* w2
     if (!ok) return ofail(SPK_ERR_HIP, "bottleneck timing failed");
     *ms_out = ms / iters;
   }
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "bottleneck kernel failed");
+  O_SYNC(s, "bottleneck kernel failed");
   return SPK_OK;
 }
 
@@ -599,7 +524,7 @@ extern "C" int spk_op_zero_sum_round(const float* w, const float* mu, float* out
   const int r = spk_launch_zero_sum_round(w, mu, out, (size_t)rows, row_len, mu_period, s);
   if (r == -2) return ofail(SPK_ERR_UNSUPPORTED, "op_zero_sum_round: row too long (8192 elements at most)");
   if (r) return ofail(SPK_ERR_HIP, "zero-sum rounding launch failed");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "zero-sum rounding kernel failed");
+  O_SYNC(s, "zero-sum rounding kernel failed");
   return SPK_OK;
 }
 
@@ -613,7 +538,7 @@ extern "C" int spk_op_conv_group(const void* x, const float* w, const float* bn_
   hipStream_t s = (hipStream_t)stream;
   O_TRY(spk_launch_group_fwd((const bf16_t*)x, w, bn_scale, bn_bias, (bf16_t*)y, n, h, wd, c, groups, stride, relu,
                              bf16 ? DT_BF16 : DT_F16, s), "grouped conv");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_conv_group: kernel failed");
+  O_SYNC(s, "op_conv_group: kernel failed");
   return SPK_OK;
 }
 
@@ -625,7 +550,7 @@ extern "C" int spk_op_conv_group_dgrad(const void* dy, const float* w, void* dx,
   hipStream_t s = (hipStream_t)stream;
   O_TRY(spk_launch_group_dgrad((const bf16_t*)dy, w, (bf16_t*)dx, accumulate != 0, n, h, wd, c, groups, stride, DT_BF16, s),
         "grouped conv dgrad");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_conv_group_dgrad: kernel failed");
+  O_SYNC(s, "op_conv_group_dgrad: kernel failed");
   return SPK_OK;
 }
 
@@ -643,7 +568,7 @@ extern "C" int spk_op_conv_group_wgrad(const void* x, const void* dy, float* dw,
   O_TRY(spk_launch_group_wgrad((const bf16_t*)x, (const bf16_t*)dy, slabs, n, h, wd, c, groups, stride, DT_BF16, &chunks, s),
         "grouped conv wgrad");
   O_TRY(spk_launch_slab_reduce(slabs, dw, (size_t)c * 9 * (c / groups), chunks, s), "grouped conv wgrad reduce");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_conv_group_wgrad: kernel failed");
+  O_SYNC(s, "op_conv_group_wgrad: kernel failed");
   return SPK_OK;
 }
 
@@ -699,7 +624,7 @@ extern "C" int spk_op_dw_train(const void* x, const void* dy, const float* w, vo
                               s), "depthwise wgrad");
     O_TRY(spk_launch_slab_reduce(slabs, dw, (size_t)c_log * taps, rows, s), "depthwise wgrad reduce");
   }
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_dw_train: kernel failed");
+  O_SYNC(s, "op_dw_train: kernel failed");
   return SPK_OK;
 }
 
@@ -728,7 +653,7 @@ extern "C" int spk_op_bna_forward(const void* raw, const float* gamma, const flo
   else
     O_TRY(spk_launch_bna_apply((const bf16_t*)raw, st + 2 * C, st + 3 * C, (const bf16_t*)res, rowscale, (bf16_t*)out, M, C,
                                HW, act, s), "bn_apply");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_bna_forward: kernel failed");
+  O_SYNC(s, "op_bna_forward: kernel failed");
   return SPK_OK;
 }
 
@@ -754,7 +679,7 @@ extern "C" int spk_op_bna_backward(const void* g, const void* raw, const float* 
   O_TRY(spk_launch_bna_bwd_apply((const bf16_t*)g, (const bf16_t*)raw, st + 2 * C, st + 3 * C, st, st + C, coef, rowscale,
                                  (bf16_t*)dy, (bf16_t*)g_res, g_res ? res_accumulate != 0 : 0, M, C, HW, act, s),
         "bn bwd apply");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_bna_backward: kernel failed");
+  O_SYNC(s, "op_bna_backward: kernel failed");
   return SPK_OK;
 }
 
@@ -778,7 +703,7 @@ extern "C" int spk_op_se_train_forward(const void* a, const float* pool_part, co
   O_TRY(spk_launch_se_gate_fwd(pool_part ? pool_part : part, chunks, 1.f / (float)HW, pooled, W1, b1, W2, b2, u1, h1, gate, n,
                                C, Cl, S, s, gate_kind), "se gates");
   if (out) O_TRY(spk_launch_se_scale((const bf16_t*)a, gate, (bf16_t*)out, n, HW, C, s), "se scale");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_se_train_forward: kernel failed");
+  O_SYNC(s, "op_se_train_forward: kernel failed");
   return SPK_OK;
 }
 
@@ -809,7 +734,7 @@ extern "C" int spk_op_se_train_backward(const void* g, const void* a, const floa
   if (spk_launch_se_wgrad(du2, h1, du1, pooled, gW1, gb1, gW2, gb2, n, C, Cl, S, s) != 0)
     return ofail(SPK_ERR_HIP, "se wgrad failed");
   if (g) O_TRY(spk_launch_se_bwd_apply((const bf16_t*)g, gate, dpool, (bf16_t*)da, n, HW, C, s), "se bwd apply");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_se_train_backward: kernel failed");
+  O_SYNC(s, "op_se_train_backward: kernel failed");
   return SPK_OK;
 }
 
@@ -832,10 +757,10 @@ extern "C" int spk_op_stem3_train(const void* x, const float* w, const void* dy,
     O_TRY(spk_launch_stem3_wgrad((const bf16_t*)x, (const bf16_t*)dy, slabs, n, h, wd, wstride, cin, cout, C, ho, wo, &nbk, s),
           "stem3 wgrad");
     O_TRY(spk_launch_slab_reduce(slabs, dw, (size_t)cout * 9 * cin, nbk, s, 1.0f / SPK_INPUT_SCALE), "stem3 wgrad reduce");
-    if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_stem3_train: kernel failed");   // (slabs die here)
+    O_SYNC(s, "op_stem3_train: kernel failed");   // (slabs die here)
     return SPK_OK;
   }
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_stem3_train: kernel failed");
+  O_SYNC(s, "op_stem3_train: kernel failed");
   return SPK_OK;
 }
 
@@ -898,30 +823,23 @@ extern "C" int spk_op_conv1x1_padded(const void* x, const float* w, const float*
   if (!x || !w || !bn_scale || !bn_bias || !y || n < 1 || h < 1 || wd < 1 || cin < 8 || cout < 8 || cin % 8 || cout % 8 ||
       !act_ok(act))
     return ofail(SPK_ERR_ARG, "op_conv1x1_padded: bad arguments (channels multiples of 8, act 0 ... 3)");
-  const int cin_p = pad64(cin), cout_p = pad64(cout), M = n * h * wd;
-  if ((size_t)n * h * wd * cin * 2 >= 0x80000000ull || (size_t)n * h * wd * cout * 2 >= 0x80000000ull)
-    return ofail(SPK_ERR_UNSUPPORTED, "op_conv1x1_padded: an operand of 2 GiB or more (split the batch)");
+  const int cin_p = pad64(cin), cout_p = pad64(cout);
+  ConvGeom g = spk_conv_geom(n, h, wd, cin_p, cout_p, 1, 1, 0);   // the GEMM is padded to 64, ...
+  g.Cs = cin;                                                     // ... the tensors are not
+  g.Cos = cout;
   hipStream_t s = (hipStream_t)stream;
   Scratch sc;
   bf16_t* wp = sc.get<bf16_t>((size_t)2 * cout_p * cin_p);
   if (!wp) return ofail(SPK_ERR_HIP, "hipMalloc failed");
   float* sb = staged_scale_bias(sc, bn_scale, bn_bias, cout, cout_p, 1.f, s);
   if (!sb) return ofail(SPK_ERR_HIP, "op_conv1x1_padded: staging failed");
+  ConvArgs a = spk_conv_args(g, (const bf16_t*)x, wp, (bf16_t*)y, (const bf16_t*)res, sb, sb + cout_p, act, DT_F16, split != 0);
+  if (!spk_below_2gib(a))
+    return ofail(SPK_ERR_UNSUPPORTED, "op_conv1x1_padded: an operand of 2 GiB or more (split the batch)");
   O_TRY(spk_launch_pack_padded(w, wp, cout, 1, cin, cout_p, cin_p, DT_F16, split != 0, s), "pack_padded");
-  ConvArgs a;
-  memset(&a, 0, sizeof a);
-  a.cfg = a.dma = -1;
-  a.cls_ph = a.cls_pw = -1;
-  a.x = (const bf16_t*)x; a.w = wp; a.y = (bf16_t*)y; a.res = (const bf16_t*)res; a.scale = sb; a.bias = sb + cout_p;
-  a.N = n; a.H = h; a.W = wd; a.Cin = cin_p; a.Ho = h; a.Wo = wd; a.Cout = cout_p;
-  a.cin_s = cin != cin_p ? cin : 0;
-  a.cout_s = cout != cout_p ? cout : 0;
-  a.kh = a.kw = 1; a.stride = 1; a.M = M; a.K = cin_p; a.relu = act; a.dt = DT_F16; a.splitw = split != 0;
-  a.x_bytes = (unsigned)((size_t)M * cin * 2);
-  a.w_bytes = (unsigned)((size_t)cout_p * cin_p * 2 * (split ? 2 : 1));
   if (gate) spk_set_gate(a, gate, cin);
   O_CONV(spk_conv_launch(a, CONV_MODE_GENERIC, s, nullptr), "padded conv1x1 launch");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_conv1x1_padded: kernel failed");
+  O_SYNC(s, "op_conv1x1_padded: kernel failed");
   return SPK_OK;
 }
 
@@ -943,7 +861,7 @@ extern "C" int spk_op_se_eval(const void* x, const float* partial, int chunks, c
   O_TRY(spk_launch_pack_tapmajor(w2, w2t, c, sq, c, s), "pack_tapmajor");
   O_TRY(spk_launch_se(y ? (const bf16_t*)x : nullptr, (bf16_t*)y, partial, chunks, scale_out, w1, b1, w2t, b2, n, hw, c, c,
                       sq, DT_F16, s, gate_kind), "squeeze-excitation");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_se_eval: kernel failed");
+  O_SYNC(s, "op_se_eval: kernel failed");
   return SPK_OK;
 }
 
@@ -964,7 +882,7 @@ extern "C" int spk_op_stem3_eval(const void* x, const float* w, const float* bn_
                                    act, DT_F16, s);
   if (r == -2) return ofail(SPK_ERR_UNSUPPORTED, "op_stem3_eval: shape not supported");
   if (r) return ofail(SPK_ERR_HIP, "op_stem3_eval: launch failed");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_stem3_eval: kernel failed");
+  O_SYNC(s, "op_stem3_eval: kernel failed");
   return SPK_OK;
 }
 
@@ -973,31 +891,23 @@ extern "C" int spk_op_stem7_eval(const void* x, const float* w, const float* bn_
   if (!x || !w || !bn_scale || !bn_bias || (!y && !pool_y) || n < 1 || h < 1 || wd < 1)
     return ofail(SPK_ERR_ARG, "op_stem7_eval: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  const int wst = (wd + 1) & ~1, ho = (h - 1) / 2 + 1, wo = (wd - 1) / 2 + 1, kpad = 256;
-  if ((size_t)n * h * wst * 8 >= 0x80000000ull || (size_t)n * ho * wo * 128 >= 0x80000000ull)
-    return ofail(SPK_ERR_UNSUPPORTED, "op_stem7_eval: an operand of 2 GiB or more (split the batch)");
+  const ConvGeom g = spk_stem_geom(n, h, wd);
   Scratch sc;
-  bf16_t* wp = sc.get<bf16_t>((size_t)2 * 64 * kpad);
+  bf16_t* wp = sc.get<bf16_t>((size_t)2 * g.Cout * g.K);
   if (!wp) return ofail(SPK_ERR_HIP, "hipMalloc failed");
   float* sb = staged_scale_bias(sc, bn_scale, bn_bias, 64, 64, 1.0f / SPK_INPUT_SCALE, s);
   if (!sb) return ofail(SPK_ERR_HIP, "op_stem7_eval: staging failed");
+  ConvArgs a = spk_conv_args(g, (const bf16_t*)x, wp, (bf16_t*)y, nullptr, sb, sb + 64, 1, DT_F16, split != 0);
+  if (!spk_below_2gib(a))
+    return ofail(SPK_ERR_UNSUPPORTED, "op_stem7_eval: an operand of 2 GiB or more (split the batch)");
   O_TRY(spk_launch_pack_weights(w, wp, 64, 7, 7, 3, CONV_MODE_STEM, DT_F16, split != 0, s), "pack_weights");
-  ConvArgs a;
-  memset(&a, 0, sizeof a);
-  a.cfg = a.dma = -1;
-  a.cls_ph = a.cls_pw = -1;
-  a.x = (const bf16_t*)x; a.w = wp; a.y = (bf16_t*)y; a.scale = sb; a.bias = sb + 64;
-  a.N = n; a.H = h; a.W = wst; a.Cin = 4; a.Ho = ho; a.Wo = wo; a.Cout = 64;
-  a.kh = a.kw = 7; a.stride = 2; a.pad = 3; a.M = n * ho * wo; a.K = kpad; a.relu = 1; a.dt = DT_F16; a.splitw = split != 0;
-  a.x_bytes = (unsigned)((size_t)n * h * wst * 4 * 2);
-  a.w_bytes = (unsigned)((size_t)64 * kpad * 2 * (split ? 2 : 1));
   if (pool_y) {   // the max-pool layer that follows is computed by the stem kernel: only the pooled tensor is written
     a.pool_y = (bf16_t*)pool_y;
-    a.pool_ho = (ho - 1) / 2 + 1;
-    a.pool_wo = (wo - 1) / 2 + 1;
+    a.pool_ho = (g.Ho - 1) / 2 + 1;
+    a.pool_wo = (g.Wo - 1) / 2 + 1;
   }
   O_CONV(spk_conv_launch(a, CONV_MODE_STEM, s, nullptr), "stem launch");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_stem7_eval: kernel failed");
+  O_SYNC(s, "op_stem7_eval: kernel failed");
   return SPK_OK;
 }
 
@@ -1054,7 +964,7 @@ extern "C" int spk_op_linear(const float* x, const float* w, const float* b, flo
     return ofail(SPK_ERR_UNSUPPORTED, "op_linear: a tensor of 2^31 elements or more");
   hipStream_t s = (hipStream_t)stream;
   O_TRY(spk_launch_linear_fwd(x, w, b, y, n, in, out, s), "linear");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_linear: kernel failed");
+  O_SYNC(s, "op_linear: kernel failed");
   return SPK_OK;
 }
 
@@ -1066,7 +976,7 @@ extern "C" int spk_op_linear_backward(const float* gy, const float* x, const flo
     return ofail(SPK_ERR_UNSUPPORTED, "op_linear_backward: a tensor of 2^31 elements or more");
   hipStream_t s = (hipStream_t)stream;
   O_TRY(spk_linear_backward(gy, x, w, dw, db, dx, n, in, out, form, s), "linear backward");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_linear_backward: kernel failed");
+  O_SYNC(s, "op_linear_backward: kernel failed");
   return SPK_OK;
 }
 
@@ -1075,7 +985,7 @@ extern "C" int spk_op_softmax(const float* z, float* p, int n, int c, float base
   if (!below_2g(n, c)) return ofail(SPK_ERR_UNSUPPORTED, "op_softmax: a tensor of 2^31 elements or more");
   hipStream_t s = (hipStream_t)stream;
   O_TRY(spk_launch_softmax(z, p, n, c, logf(base), s), "softmax");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_softmax: kernel failed");
+  O_SYNC(s, "op_softmax: kernel failed");
   return SPK_OK;
 }
 
@@ -1085,7 +995,7 @@ extern "C" int spk_op_cross_entropy(const float* z, const int64_t* labels, int n
   if (!below_2g(n, c)) return ofail(SPK_ERR_UNSUPPORTED, "op_cross_entropy: a tensor of 2^31 elements or more");
   hipStream_t s = (hipStream_t)stream;
   O_TRY(spk_launch_ce(z, labels, n, c, stats, dz, s), "cross-entropy");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_cross_entropy: kernel failed");
+  O_SYNC(s, "op_cross_entropy: kernel failed");
   return SPK_OK;
 }
 
@@ -1097,7 +1007,7 @@ extern "C" int spk_op_cross_entropy_ex(const float* z, const int64_t* labels, in
   if (!below_2g(n, c)) return ofail(SPK_ERR_UNSUPPORTED, "op_cross_entropy_ex: a tensor of 2^31 elements or more");
   hipStream_t s = (hipStream_t)stream;
   O_TRY(spk_launch_ce_ex(z, labels, n, c, w, label_smoothing, stats, counts, dz, s), "cross-entropy");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_cross_entropy_ex: kernel failed");
+  O_SYNC(s, "op_cross_entropy_ex: kernel failed");
   return SPK_OK;
 }
 
@@ -1111,7 +1021,7 @@ extern "C" int spk_op_cross_entropy_pair(const float* z, const int64_t* ya, cons
   if (!below_2g(n, c)) return ofail(SPK_ERR_UNSUPPORTED, "op_cross_entropy_pair: a tensor of 2^31 elements or more");
   hipStream_t s = (hipStream_t)stream;
   O_TRY(spk_launch_ce_pair(z, ya, yb, lam, n, c, w, label_smoothing, stats, counts, dz, s), "cross-entropy");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_cross_entropy_pair: kernel failed");
+  O_SYNC(s, "op_cross_entropy_pair: kernel failed");
   return SPK_OK;
 }
 
@@ -1142,7 +1052,7 @@ extern "C" int spk_op_maxpool(const void* x, void* y, unsigned char* idx, int n,
     O_TRY(spk_launch_maxpool_idx((const bf16_t*)x, (bf16_t*)y, idx, n, h, w, c, k, stride, pad, ho, wo, s), "maxpool");
   else
     O_TRY(spk_launch_maxpool((const bf16_t*)x, (bf16_t*)y, n, h, w, c, k, stride, pad, ho, wo, dtype, s), "maxpool");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_maxpool: kernel failed");
+  O_SYNC(s, "op_maxpool: kernel failed");
   return SPK_OK;
 }
 
@@ -1160,7 +1070,7 @@ extern "C" int spk_op_maxpool_backward(const void* gy, const unsigned char* idx,
   else
     O_TRY(spk_launch_maxpool_bwd_form((const bf16_t*)gy, idx, (bf16_t*)gx, n, h, w, c, k, stride, pad, ho, wo, form == 1, s),
           "maxpool bwd");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_maxpool_backward: kernel failed");
+  O_SYNC(s, "op_maxpool_backward: kernel failed");
   return SPK_OK;
 }
 
@@ -1171,7 +1081,7 @@ extern "C" int spk_op_gavgpool(const void* x, float* y, int n, int hw, int c, in
     return ofail(SPK_ERR_UNSUPPORTED, "op_gavgpool: more than 65535 images or a tensor of 2^31 elements or more");
   hipStream_t s = (hipStream_t)stream;
   O_TRY(spk_launch_gavgpool((const bf16_t*)x, y, n, hw, c, dtype, s), "avgpool");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_gavgpool: kernel failed");
+  O_SYNC(s, "op_gavgpool: kernel failed");
   return SPK_OK;
 }
 
@@ -1181,7 +1091,7 @@ extern "C" int spk_op_gavgpool_backward(const float* gy, void* gx, int n, int hw
   if (!below_2g(n, hw, c)) return ofail(SPK_ERR_UNSUPPORTED, "op_gavgpool_backward: a tensor of 2^31 elements or more");
   hipStream_t s = (hipStream_t)stream;
   O_TRY(spk_launch_gavgpool_bwd(gy, (bf16_t*)gx, n, hw, c, s), "avgpool bwd");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_gavgpool_backward: kernel failed");
+  O_SYNC(s, "op_gavgpool_backward: kernel failed");
   return SPK_OK;
 }
 
@@ -1204,7 +1114,7 @@ extern "C" int spk_op_ema_lerp(float* e, const float* p, int64_t n, float w, voi
   if (!(w > 0.f && w < 1.f)) return ofail(SPK_ERR_ARG, "op_ema_lerp: w must be finite and inside (0, 1)");
   hipStream_t s = (hipStream_t)stream;
   O_TRY(spk_launch_ema_lerp(e, p, (size_t)n, w, s), "ema lerp");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_ema_lerp: kernel failed");
+  O_SYNC(s, "op_ema_lerp: kernel failed");
   return SPK_OK;
 }
 
@@ -1212,6 +1122,6 @@ extern "C" int spk_op_swap_f32(float* a, float* b, int64_t n, void* stream) {
   if (const int r = stream_pair_args("op_swap_f32", a, b, n)) return r;
   hipStream_t s = (hipStream_t)stream;
   O_TRY(spk_launch_swap_f32(a, b, (size_t)n, s), "swap");
-  if (hipStreamSynchronize(s) != hipSuccess) return ofail(SPK_ERR_HIP, "op_swap_f32: kernel failed");
+  O_SYNC(s, "op_swap_f32: kernel failed");
   return SPK_OK;
 }

@@ -95,6 +95,21 @@ template <int DT> __device__ __forceinline__ f32x4_t mfma16(const u32x4_t a, con
                                                 __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
 }
 
+// A 16-byte buffer load the compiler's s_waitcnt pass does not see (conv_bneck.hip: phase 1's weight fragments;
+// conv_pwr.hip: the weight fragments of a chunk).  hipcc 7.2 does not count LDS-DMA instructions when it derives the vmcnt of
+// a register load's first use, so with builtin loads next to the DMAs it waits for "all but N" with an N that is too small
+// by the DMAs issued in between - i.e. for the x chunk still in flight.  The caller orders these loads with its own
+// s_waitcnt (the same that publishes the DMA pieces); the destination registers must never be spilled or copied before
+// that wait ("VGPRs Spill: 0" for every instantiation that uses it).
+__device__ __forceinline__ u32x4_t buffer_load_b128_untracked(u32x4_t rsrc, unsigned voff, unsigned soff, int imm) {
+  u32x4_t d;
+  if (imm == 0) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(d) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+  else if (imm == 1024) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:1024" : "=v"(d) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+  else if (imm == 2048) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:2048" : "=v"(d) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+  else asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:3072" : "=v"(d) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+  return d;
+}
+
 // ---------------------------------------------------------------------------
 // Implicit-GEMM convolution (conv_igemm.hip).
 //   M = N*Ho*Wo output pixels, N = Cout, K = kh*kw*Cin (tap-major, channel

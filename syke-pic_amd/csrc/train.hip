@@ -7,6 +7,7 @@
 // stem's BatchNorm, weight gradients only where requires_grad is set
 // (sykepic/train/network.py:133-172).
 #include "model.h"
+#include "conv_args.h"
 #include "train_effnet.h"
 
 #include <algorithm>
@@ -360,22 +361,6 @@ void spk_train_mark_dirty(spk_model* m) {
   if (m->train) m->train->weights_dirty = true;
 }
 
-static void fill_conv(ConvArgs& a, const bf16_t* x, const bf16_t* w, bf16_t* y, int N, int H, int W,
-                      int Cin, int Ho, int Wo, int Cout, int k, int stride, int pad, int K) {
-  memset(&a, 0, sizeof a);
-  a.cfg = a.dma = -1;
-  a.cls_ph = a.cls_pw = -1;
-  a.x = x; a.w = w; a.y = y;
-  a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;
-  a.kh = a.kw = k; a.stride = stride; a.pad = pad;
-  a.M = N * Ho * Wo;
-  a.K = K;
-  a.dt = DT_BF16;
-  a.x_bytes = (unsigned)((size_t)N * H * W * Cin * 2);
-  a.w_bytes = (unsigned)((size_t)Cout * K * 2);
-}
-
-
 // ---------------------------------------------------------------------------
 // Backward of one convolution, shared by the training step below and by the single-operator test hooks
 // (ops_abi.hip), so that the isolation tests exercise exactly the launches a training step makes.
@@ -390,9 +375,9 @@ static int dgrad_rc(int r, const char* what) {
 // dx (+)= conv_transpose(dy, w): dy [n,oh,ow,cout], wdg = the [Cin][kh][kw][Cout] bf16 image, dx [n,ih,iw,cin]
 int spk_conv_dgrad_all(const bf16_t* dy, const bf16_t* wdg, bf16_t* dx, bool accumulate, int n, int oh, int ow,
                        int cout, int ih, int iw, int cin, int k, int stride, int pad, hipStream_t s, BnbFuse* fuse) {
-  ConvArgs a;
-  fill_conv(a, dy, wdg, dx, n, oh, ow, cout, ih, iw, cin, k, stride, pad, k * k * cout);
-  a.res = accumulate ? (const bf16_t*)dx : nullptr;
+  // the transposed conv as an implicit GEMM: dy is the input, cout the reduction
+  const ConvGeom g = {n, oh, ow, cout, ih, iw, cin, cout, cin, k * k * cout, k, stride, pad};
+  ConvArgs a = spk_conv_args(g, dy, wdg, dx, accumulate ? (const bf16_t*)dx : nullptr, nullptr, nullptr, 0, DT_BF16, 0);
   if (stride == 1) {
     if (fuse) {
       spk_set_bnb(a, fuse->partials, fuse->raw, fuse->mask, fuse->mean, fuse->invstd, fuse->res_src ? fuse->res_bits : nullptr);
@@ -606,9 +591,9 @@ static int conv_forward(StepCtx& c, int i) {
                                C, L.groups, L.d.stride, 0, DT_BF16, s), "grouped conv fwd");
     K_TRY(spk_launch_col_stats(t->RAW(i), c.part, M, C, &m_tiles, s), "col_stats");
   } else {
-    ConvArgs a;
-    fill_conv(a, (const bf16_t*)m->T(L.d.src), t->wpack + t->conv[i].wfwd_off, t->RAW(i), n, in.h, in.w,
-              in.c, o.h, o.w, C, L.d.k, L.d.stride, L.d.pad, L.kpad);
+    const ConvGeom g = {n, in.h, in.w, in.c, o.h, o.w, C, in.c, C, L.kpad, L.d.k, L.d.stride, L.d.pad};
+    ConvArgs a = spk_conv_args(g, (const bf16_t*)m->T(L.d.src), t->wpack + t->conv[i].wfwd_off, t->RAW(i), nullptr, nullptr,
+                               nullptr, 0, DT_BF16, 0);
     a.stats = c.part;
     K_TRY(spk_conv_launch(a, L.mode, s, &m_tiles), "conv");
   }
