@@ -251,6 +251,20 @@ int spk_train_forward_backward(spk_model* m, const void* x_dev, int n, int h, in
 int spk_train_forward_backward_pair(spk_model* m, const void* x_dev, int n, int h, int w, int layout, int dtype,
                                     const int64_t* ya_dev, const int64_t* yb_dev, float lam,
                                     float* stats_dev, float* logits_dev);
+/* The same step with knowledge distillation from a teacher (not in the reference): teacher_logits_dev is a float32
+ * [n][num_classes] device buffer of the teacher's logits for this very batch, and
+ *   loss = (1 - alpha) L_hard + alpha T^2 KL(softmax(teacher / T) || softmax(out / T))      ("batchmean", T = temperature)
+ * with L_hard the loss of spk_train_forward_backward_pair (one or two label vectors, the model's weights and smoothing),
+ * 1 - alpha formed in float32.  stats[0] += n * loss; stats[1] and the per-class counters as in the pair step.
+ * kd_stats_dev (may be NULL): float32 [2], [0] += n * KD (the KL term with its T^2), [1] += rows whose arg-max equals
+ * the teacher's (lowest index among the maxima on both sides).  teacher_logits_dev == NULL or alpha == 0:
+ * spk_train_forward_backward_pair, bit for bit; the teacher is not read and kd_stats_dev not written.  Checked before
+ * any HIP call: what the pair step checks, alpha outside [0, 1], temperature not finite or <= 0, and a kd_stats_dev
+ * without teacher_logits_dev are SPK_ERR_ARG. */
+int spk_train_forward_backward_distill(spk_model* m, const void* x_dev, int n, int h, int w, int layout, int dtype,
+                                       const int64_t* ya_dev, const int64_t* yb_dev, float lam,
+                                       const float* teacher_logits_dev, float alpha, float temperature,
+                                       float* stats_dev, float* kd_stats_dev, float* logits_dev);
 /* optimizer.step() — sykepic/train/train.py:243 */
 int spk_optim_step(spk_model* m, const spk_optim_desc* opt);
 
@@ -652,6 +666,18 @@ int spk_op_cross_entropy_ex(const float* z_dev, const int64_t* labels_dev, int n
 int spk_op_cross_entropy_pair(const float* z_dev, const int64_t* ya_dev, const int64_t* yb_dev, float lam, int n, int c,
                               const float* w_dev, float label_smoothing, float* stats_dev, int* counts_dev, float* dz_dev,
                               void* hip_stream);
+/* That criterion distilled against a teacher's logits t_dev [n][c], the kernel spk_train_forward_backward_distill runs:
+ * L = (1 - alpha) L_hard + alpha KD, KD = T^2 / n sum_i KL(softmax(t_i / T) || softmax(z_i / T)), L_hard the loss of
+ * spk_op_cross_entropy_pair (yb_dev == NULL or lam == 1: of spk_op_cross_entropy_ex on ya), 1 - alpha formed in float32.
+ * stats[0] += n * L; stats[1] and counts_dev as there; dz [n][c] (may be NULL) = (1 - alpha) dL_hard/dz + (alpha T / n)
+ * (softmax(z / T) - softmax(t / T)); kd_stats_dev float32 [2] (may be NULL): [0] += n * KD, [1] += rows whose arg-max
+ * of z equals that of t (lowest index among the maxima).  t_dev == NULL or alpha == 0: the bits of
+ * spk_op_cross_entropy_pair, t_dev not read, kd_stats_dev not written.  lam, label_smoothing or alpha outside [0, 1],
+ * temperature not finite or <= 0, kd_stats_dev without t_dev: SPK_ERR_ARG.  Equal inputs give equal bits. */
+int spk_op_cross_entropy_distill(const float* z_dev, const int64_t* ya_dev, const int64_t* yb_dev, float lam,
+                                 const float* t_dev, float alpha, float temperature, int n, int c, const float* w_dev,
+                                 float label_smoothing, float* stats_dev, int* counts_dev, float* kd_stats_dev,
+                                 float* dz_dev, void* hip_stream);
 /* MaxPool2d(k, stride, pad): x [n,h,w,c] -> y [n,ho,wo,c].  idx == NULL: the eval path's kernel, dtype 0 bf16 / 1 fp16.
  * idx [n,ho,wo,c] bytes: the training step's kernel (bf16 only), which also saves the tap r * k + s of each maximum (the
  * first in that order among equal values).  c % 8 != 0: SPK_ERR_ARG; k * k > 255 or pad > k / 2: SPK_ERR_UNSUPPORTED. */

@@ -444,6 +444,13 @@ int main(int argc, char** argv) {
     EXPECT(spk_op_cross_entropy_pair(f, labels, nullptr, NAN, 1, 4, nullptr, 0.f, f, nullptr, nullptr, nullptr) == SPK_ERR_ARG);
     EXPECT(spk_op_cross_entropy_pair(f, nullptr, labels, 0.5f, 1, 4, nullptr, 0.f, f, nullptr, nullptr, nullptr) == SPK_ERR_ARG);
     EXPECT(spk_train_forward_backward_pair(nullptr, f, 1, 4, 4, SPK_LAYOUT_NCHW, SPK_DTYPE_F32, labels, labels, 0.5f, f, nullptr) == SPK_ERR_ARG);
+    // ... the distillation criterion: alpha, the temperature, statistics without a teacher
+    EXPECT(spk_op_cross_entropy_distill(f, labels, nullptr, 1.f, f, 1.5f, 2.f, 1, 4, nullptr, 0.f, f, nullptr, f, nullptr, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_op_cross_entropy_distill(f, labels, nullptr, 1.f, f, NAN, 2.f, 1, 4, nullptr, 0.f, f, nullptr, f, nullptr, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_op_cross_entropy_distill(f, labels, nullptr, 1.f, f, 0.5f, 0.f, 1, 4, nullptr, 0.f, f, nullptr, f, nullptr, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_op_cross_entropy_distill(f, labels, nullptr, 1.f, f, 0.5f, INFINITY, 1, 4, nullptr, 0.f, f, nullptr, f, nullptr, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_op_cross_entropy_distill(f, labels, nullptr, 1.f, nullptr, 0.5f, 2.f, 1, 4, nullptr, 0.f, f, nullptr, f, nullptr, nullptr) == SPK_ERR_ARG);
+    EXPECT(spk_train_forward_backward_distill(nullptr, f, 1, 4, 4, SPK_LAYOUT_NCHW, SPK_DTYPE_F32, labels, nullptr, 1.f, f, 0.5f, 2.f, f, f, nullptr) == SPK_ERR_ARG);
     EXPECT(spk_mix_batch(img_a, img_b, 2, 4, 4, 3, SPK_LAYOUT_NHWC, SPK_DTYPE_U8, 2, 0.5f, 0.5f, 0, 0, 4, 4, nullptr) == SPK_ERR_ARG);
     EXPECT(spk_mix_batch(img_a, img_b, 2, 4, 4, 3, SPK_LAYOUT_NHWC, SPK_DTYPE_U8, 1, 0.5f, 0.5f, 0, 0, 5, 4, nullptr) == SPK_ERR_ARG);
     EXPECT(spk_mix_batch(img_a, img_b, 2, 4, 4, 3, SPK_LAYOUT_NHWC, SPK_DTYPE_U8, 1, NAN, 0.5f, 0, 0, 4, 4, nullptr) == SPK_ERR_ARG);

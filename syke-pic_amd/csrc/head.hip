@@ -427,6 +427,156 @@ __global__ __launch_bounds__(1024) void ce_pair_kernel(const float* __restrict__
   }
 }
 
+// Knowledge distillation: L = (1 - alpha) L_hard + alpha KD against the logits t [n][c] of a teacher, with
+//   KD = T^2 / n  sum_i KL(q_i || pT_i),   pT = softmax(z / T),   q = softmax(t / T)       ("batchmean")
+//   dz[i][j] = (1 - alpha) g_hard[i][j] + (alpha T / n) (pT[i][j] - q[i][j])
+// L_hard is the loss of ce_ex_kernel (PAIR false: one label vector) or of ce_pair_kernel (PAIR true), and the hard row
+// losses and g_hard are formed with exactly their expressions before anything is combined, so their rounding bounds
+// carry over.  The same one block of a row per wave and the same fixed summation orders; integer atomics only.  Per row
+// three soft-maxes: of z (the hard part), of z / T and of t / T, each logit divided by T once (a correctly rounded
+// division; T = 1 leaves the bits) and the maximum taken of the quotients.  The KD row sum is formed term by term as
+//   q[j] ((t[j] / T - lseT_t) - (z[j] / T - lseT_z)):
+// q log q is never formed, a q that underflows to 0 contributes exactly 0, and a row whose two soft-maxes sit on
+// different classes gives the finite difference of the logits.  (A quotient is rounded before the maximum is subtracted -
+// a division does not contract - so the largest exponent is exactly 0, which softmax_kernel needs a pragma for.)
+//   stats[0] += (1 - alpha) (n L_hard) + alpha (n KD),  n KD = (T T) sum of the KD rows,  1 - alpha formed in float32
+//   stats[1], counts: ce_pair_kernel's rule (arg-max = lowest index among the maxima of z, against the dominant label)
+//   kd_stats (may be null): [0] += n KD, [1] += rows whose arg-max of z equals the arg-max of t (the same tie rule)
+template <bool PAIR>
+__global__ __launch_bounds__(1024) void ce_distill_kernel(const float* __restrict__ z, const int64_t* __restrict__ ya,
+                                                         const int64_t* __restrict__ yb, float lam,
+                                                         const float* __restrict__ tz, float alpha, float T, int n, int c,
+                                                         const float* __restrict__ w, float eps, float* __restrict__ stats,
+                                                         int* __restrict__ counts, float* __restrict__ kd_stats,
+                                                         float* __restrict__ dz) {
+  constexpr int WAVES = 16;
+  __shared__ float s_wa[WAVES];
+  __shared__ float s_wb[WAVES];
+  __shared__ float s_la[WAVES];
+  __shared__ float s_lb[WAVES];
+  __shared__ float s_corr[WAVES];
+  __shared__ float s_kd[WAVES];
+  __shared__ float s_agree[WAVES];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  // W_a (W_b): as ce_ex_kernel forms W; every thread ends with the same bits
+  float Wa = (float)n, Wb = (float)n, Sw = (float)c;
+  if (w) {
+    float pa = 0.f, pb = 0.f;
+    for (int i = threadIdx.x; i < n; i += WAVES * 64) {
+      pa += w[(int)ya[i]];
+      if (PAIR) pb += w[(int)yb[i]];
+    }
+    pa = wave_sum(pa);
+    if (PAIR) pb = wave_sum(pb);
+    if (lane == 0) { s_wa[wave] = pa; s_wb[wave] = pb; }
+    __syncthreads();
+    Wa = Wb = 0.f;
+    for (int q = 0; q < WAVES; ++q) { Wa += s_wa[q]; Wb += s_wb[q]; }
+    float sp = 0.f;
+    for (int j = lane; j < c; j += 64) sp += w[j];
+    Sw = wave_sum(sp);
+  }
+  const bool smooth = eps > 0.f;
+  const bool first = !PAIR || lam >= 0.5f;   // the dominant label
+  const float invWa = 1.0f / Wa, invWb = 1.0f / Wb;
+  const float a = 1.0f - eps, b = eps / (float)c;
+  const float cba = b * invWa, cbb = b * invWb;
+  const float lamb = 1.0f - lam;
+  const float hard = 1.0f - alpha;           // the weight of the hard part
+  const float ck = alpha * T / (float)n;     // the coefficient of pT - q
+  float loss_a = 0.f, loss_b = 0.f, corr = 0.f, kd = 0.f, agree = 0.f;
+  for (int row = wave; row < n; row += WAVES) {
+    const float* zr = z + (size_t)row * c;
+    const float* tr = tz + (size_t)row * c;
+    const int la = (int)ya[row], lb = PAIR ? (int)yb[row] : la;
+    float mx = -INFINITY, mt = -INFINITY;
+    int arg = 0x7fffffff, argt = 0x7fffffff;
+    for (int j = lane; j < c; j += 64) {
+      const float v = zr[j], u = tr[j];
+      if (v > mx) { mx = v; arg = j; }
+      if (u > mt) { mt = u; argt = j; }
+    }
+    // arg-max with torch's tie rule on both: lowest index among the maxima
+    for (int d = 32; d; d >>= 1) {
+      const float om = __shfl_xor(mx, d), ot = __shfl_xor(mt, d);
+      const int oa = __shfl_xor(arg, d), oat = __shfl_xor(argt, d);
+      if (om > mx || (om == mx && oa < arg)) { mx = om; arg = oa; }
+      if (ot > mt || (ot == mt && oat < argt)) { mt = ot; argt = oat; }
+    }
+    // T > 0 and a correctly rounded division are monotone: the quotient of the maximum is the maximum of the quotients
+    const float mxT = mx / T, mtT = mt / T;
+    float s = 0.f, sz = 0.f, st = 0.f;
+    for (int j = lane; j < c; j += 64) {
+      s += expf(zr[j] - mx);
+      sz += expf(zr[j] / T - mxT);
+      st += expf(tr[j] / T - mtT);
+    }
+    s = wave_sum(s);
+    sz = wave_sum(sz);
+    st = wave_sum(st);
+    const float lse = mx + logf(s);
+    const float lsez = mxT + logf(sz), lset = mtT + logf(st);
+    const float invz = 1.0f / sz, invt = 1.0f / st;
+    float sm = 0.f;
+    if (smooth) {
+      for (int j = lane; j < c; j += 64) sm += (w ? w[j] : 1.f) * (lse - zr[j]);
+      sm = wave_sum(sm);
+    }
+    float kr = 0.f;
+    for (int j = lane; j < c; j += 64) {
+      const float q = expf(tr[j] / T - mtT) * invt;
+      kr += q * ((tr[j] / T - lset) - (zr[j] / T - lsez));
+    }
+    kr = wave_sum(kr);
+    const float awa = a * (w ? w[la] : 1.f), awb = a * (w ? w[lb] : 1.f);
+    if (lane == 0) {
+      const int label = first ? la : lb;
+      const bool hit = arg == label;
+      loss_a += awa * (lse - zr[la]) + b * sm;
+      if (PAIR) loss_b += awb * (lse - zr[lb]) + b * sm;
+      corr += hit ? 1.f : 0.f;
+      kd += kr;
+      agree += (arg == argt) ? 1.f : 0.f;
+      if (counts && (unsigned)label < (unsigned)c) {
+        atomicAdd(counts + 2 * label, 1);
+        if (hit) atomicAdd(counts + 2 * label + 1, 1);
+      }
+    }
+    if (dz) {
+      const float inv = 1.0f / s;
+      const float caa = awa * invWa, cab = awb * invWb;
+      for (int j = lane; j < c; j += 64) {
+        const float p = expf(zr[j] - mx) * inv;
+        float ga = caa * (p - (j == la ? 1.f : 0.f));
+        float gb = cab * (p - (j == lb ? 1.f : 0.f));
+        if (smooth) {
+          const float t = p * Sw - (w ? w[j] : 1.f);
+          ga += cba * t;
+          gb += cbb * t;
+        }
+        const float g = PAIR ? lam * ga + lamb * gb : ga;
+        const float pT = expf(zr[j] / T - mxT) * invz;
+        const float q = expf(tr[j] / T - mtT) * invt;
+        dz[(size_t)row * c + j] = hard * g + ck * (pT - q);
+      }
+    }
+  }
+  if (lane == 0) { s_la[wave] = loss_a; s_lb[wave] = loss_b; s_corr[wave] = corr; s_kd[wave] = kd; s_agree[wave] = agree; }
+  __syncthreads();
+  if (threadIdx.x == 0) {   // fixed order
+    float ta = 0.f, tb = 0.f, tc = 0.f, tk = 0.f, tg = 0.f;
+    for (int q = 0; q < WAVES; ++q) { ta += s_la[q]; tb += s_lb[q]; tc += s_corr[q]; tk += s_kd[q]; tg += s_agree[q]; }
+    const float nhard = PAIR ? lam * (ta * invWa * (float)n) + lamb * (tb * invWb * (float)n) : ta * invWa * (float)n;
+    const float nkd = (T * T) * tk;
+    stats[0] += hard * nhard + alpha * nkd;
+    stats[1] += tc;
+    if (kd_stats) {
+      kd_stats[0] += nkd;
+      kd_stats[1] += tg;
+    }
+  }
+}
+
 // SURVEY.md §8f rank 2 — per-ROI prediction from probabilities and per-class
 // thresholds (reference sykepic/compute/prediction.py:49-71): the
 // highest-probability class that clears ITS OWN threshold wins (lowest index on
@@ -538,5 +688,20 @@ int spk_launch_ce_pair(const float* z, const int64_t* ya, const int64_t* yb, flo
   if (!yb || lam == 1.0f) return spk_launch_ce_ex(z, ya, n, c, w, label_smoothing, stats, counts, dlogits, s);
   hipLaunchKernelGGL(ce_pair_kernel, dim3(1), dim3(1024), 0, s, z, ya, yb, lam, n, c, w, label_smoothing, stats, counts,
                      dlogits);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// (1 - alpha) L_hard + alpha T^2 KL(softmax(t / T) || softmax(z / T)); t == nullptr or alpha == 0: spk_launch_ce_pair
+// unchanged (the teacher is not read, kd_stats not written), bit for bit
+int spk_launch_ce_distill(const float* z, const int64_t* ya, const int64_t* yb, float lam, const float* t, float alpha,
+                          float temperature, int n, int c, const float* w, float label_smoothing, float* stats, int* counts,
+                          float* kd_stats, float* dlogits, hipStream_t s) {
+  if (!t || alpha == 0.0f) return spk_launch_ce_pair(z, ya, yb, lam, n, c, w, label_smoothing, stats, counts, dlogits, s);
+  if (!yb || lam == 1.0f)
+    hipLaunchKernelGGL(ce_distill_kernel<false>, dim3(1), dim3(1024), 0, s, z, ya, (const int64_t*)nullptr, 1.0f, t, alpha, temperature, n, c,
+                       w, label_smoothing, stats, counts, kd_stats, dlogits);
+  else
+    hipLaunchKernelGGL(ce_distill_kernel<true>, dim3(1), dim3(1024), 0, s, z, ya, yb, lam, t, alpha, temperature, n, c, w,
+                       label_smoothing, stats, counts, kd_stats, dlogits);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -7,6 +7,7 @@
 //   Linear / softmax / CrossEntropyLoss    spk_op_linear, spk_op_linear_backward, spk_op_softmax, spk_op_cross_entropy,
 //                                          spk_op_cross_entropy_ex (class weights, label smoothing, per-class counters),
 //                                          spk_op_cross_entropy_pair (the Mixup / CutMix criterion on two label vectors)
+//                                          spk_op_cross_entropy_distill (that criterion distilled against a teacher's logits)
 //   MaxPool2d / AdaptiveAvgPool2d(1)       spk_op_maxpool, spk_op_maxpool_backward, spk_op_gavgpool, spk_op_gavgpool_backward
 //                                          (head.hip, pointwise.hip, train_kernels.hip; exact integer and float64 references)
 // The dense conv kernels' argument descriptors come from the builders of conv_args.h, the ones model.hip and train.hip
@@ -1022,6 +1023,26 @@ extern "C" int spk_op_cross_entropy_pair(const float* z, const int64_t* ya, cons
   hipStream_t s = (hipStream_t)stream;
   O_TRY(spk_launch_ce_pair(z, ya, yb, lam, n, c, w, label_smoothing, stats, counts, dz, s), "cross-entropy");
   O_SYNC(s, "op_cross_entropy_pair: kernel failed");
+  return SPK_OK;
+}
+
+extern "C" int spk_op_cross_entropy_distill(const float* z, const int64_t* ya, const int64_t* yb, float lam, const float* t,
+                                            float alpha, float temperature, int n, int c, const float* w,
+                                            float label_smoothing, float* stats, int* counts, float* kd_stats, float* dz,
+                                            void* stream) {
+  if (!z || !ya || !stats || n < 1 || c < 1) return ofail(SPK_ERR_ARG, "op_cross_entropy_distill: bad arguments");
+  if (!(lam >= 0.f && lam <= 1.f)) return ofail(SPK_ERR_ARG, "op_cross_entropy_distill: lam must be in [0, 1]");
+  if (!(label_smoothing >= 0.f && label_smoothing <= 1.f))
+    return ofail(SPK_ERR_ARG, "op_cross_entropy_distill: label_smoothing must be in [0, 1]");
+  if (!(alpha >= 0.f && alpha <= 1.f)) return ofail(SPK_ERR_ARG, "op_cross_entropy_distill: alpha must be in [0, 1]");
+  if (!(temperature > 0.f) || !(temperature <= 3.4e38f))
+    return ofail(SPK_ERR_ARG, "op_cross_entropy_distill: temperature must be a finite number above 0");
+  if (kd_stats && !t) return ofail(SPK_ERR_ARG, "op_cross_entropy_distill: kd_stats without teacher logits");
+  if (!below_2g(n, c)) return ofail(SPK_ERR_UNSUPPORTED, "op_cross_entropy_distill: a tensor of 2^31 elements or more");
+  hipStream_t s = (hipStream_t)stream;
+  O_TRY(spk_launch_ce_distill(z, ya, yb, lam, t, alpha, temperature, n, c, w, label_smoothing, stats, counts, kd_stats, dz, s),
+        "cross-entropy");
+  O_SYNC(s, "op_cross_entropy_distill: kernel failed");
   return SPK_OK;
 }
 

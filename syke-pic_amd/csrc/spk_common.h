@@ -413,6 +413,12 @@ int spk_launch_ce_ex(const float* z, const int64_t* y, int n, int c, const float
 // (ya when lam >= 0.5); yb == nullptr or lam == 1 launches the kernel of spk_launch_ce_ex on ya
 int spk_launch_ce_pair(const float* z, const int64_t* ya, const int64_t* yb, float lam, int n, int c, const float* w,
                        float label_smoothing, float* stats, int* counts, float* dlogits, hipStream_t s);
+// knowledge distillation on top of that criterion: (1 - alpha) L_hard + alpha T^2 KL(softmax(t / T) || softmax(z / T)),
+// t [n][c] the teacher's logits; kd_stats [2] (may be null) += (n KD, rows whose arg-max equals the teacher's).
+// t == nullptr or alpha == 0: spk_launch_ce_pair unchanged, t and kd_stats untouched
+int spk_launch_ce_distill(const float* z, const int64_t* ya, const int64_t* yb, float lam, const float* t, float alpha,
+                          float temperature, int n, int c, const float* w, float label_smoothing, float* stats, int* counts,
+                          float* kd_stats, float* dlogits, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // Training kernels (train_kernels.hip, conv_wgrad.hip)

@@ -948,10 +948,12 @@ static StepCtx step_begin(spk_model* m, int n, int w) {
   return c;
 }
 
-// The training step of both entry points.  y2 == nullptr: the loss on y, as ever; else the Mixup / CutMix criterion
-// lam CE(y) + (1 - lam) CE(y2) - the loss launch is all that differs.
+// The training step of the three entry points.  y2 == nullptr: the loss on y, as ever; else the Mixup / CutMix criterion
+// lam CE(y) + (1 - lam) CE(y2); teacher != nullptr and alpha != 0: that loss distilled against the teacher's logits
+// (spk_launch_ce_distill) - the loss launch is all that differs.
 static int train_step(spk_model* m, const void* x, int n, int h, int w, int layout, int dtype, const int64_t* y,
-                      const int64_t* y2, float lam, float* stats, float* logits_out) {
+                      const int64_t* y2, float lam, float* stats, float* logits_out, const float* teacher = nullptr,
+                      float alpha = 0.f, float temperature = 1.f, float* kd_stats = nullptr) {
   if (!m || !x || !y || !stats || n < 1) return spk_fail(SPK_ERR_ARG, "train step: bad arguments");
   if (dtype != SPK_DTYPE_F32 && dtype != SPK_DTYPE_U8) return spk_fail(SPK_ERR_ARG, "train step: dtype must be f32 or u8");
   // pbuf holds the average (spk_model_ema_swap): a step would train it, and update running statistics that are not the model's
@@ -1022,7 +1024,10 @@ static int train_step(spk_model* m, const void* x, int n, int h, int w, int layo
 
   // ------------------------- loss + dlogits -------------------------
   const float* logits = (const float*)m->T(last);
-  if (y2)   // the model's weights and smoothing (none and 0 for the default loss); counters when they are kept
+  if (teacher && alpha != 0.f)
+    K_TRY(spk_launch_ce_distill(logits, y, y2, lam, teacher, alpha, temperature, n, m->num_classes, m->loss_w, m->loss_eps,
+                                stats, m->class_counts, kd_stats, (float*)t->G(last), s), "cross-entropy");
+  else if (y2)   // the model's weights and smoothing (none and 0 for the default loss); counters when they are kept
     K_TRY(spk_launch_ce_pair(logits, y, y2, lam, n, m->num_classes, m->loss_w, m->loss_eps, stats, m->class_counts,
                              (float*)t->G(last), s), "cross-entropy");
   else if (m->loss_ex())
@@ -1120,6 +1125,22 @@ extern "C" int spk_train_forward_backward_pair(spk_model* m, const void* x, int 
   if (!(lam >= 0.f && lam <= 1.f)) return spk_fail(SPK_ERR_ARG, "train_forward_backward_pair: lam must be in [0, 1]");
   // one label vector, or all the weight on the first: the step of spk_train_forward_backward, plain kernel included
   return train_step(m, x, n, h, w, layout, dtype, ya, lam == 1.f ? nullptr : yb, lam, stats, logits_out);
+}
+
+extern "C" int spk_train_forward_backward_distill(spk_model* m, const void* x, int n, int h, int w, int layout, int dtype,
+                                                  const int64_t* ya, const int64_t* yb, float lam,
+                                                  const float* teacher_logits, float alpha, float temperature,
+                                                  float* stats, float* kd_stats, float* logits_out) {
+  if (!m || !x || !ya || !stats || n < 1) return spk_fail(SPK_ERR_ARG, "train_forward_backward_distill: bad arguments");
+  if (!(lam >= 0.f && lam <= 1.f)) return spk_fail(SPK_ERR_ARG, "train_forward_backward_distill: lam must be in [0, 1]");
+  if (!(alpha >= 0.f && alpha <= 1.f)) return spk_fail(SPK_ERR_ARG, "train_forward_backward_distill: alpha must be in [0, 1]");
+  if (!(temperature > 0.f) || !std::isfinite(temperature))
+    return spk_fail(SPK_ERR_ARG, "train_forward_backward_distill: temperature must be a finite number above 0");
+  if (kd_stats && !teacher_logits)
+    return spk_fail(SPK_ERR_ARG, "train_forward_backward_distill: kd_stats without teacher logits");
+  // no teacher, or no weight on it: the step of spk_train_forward_backward_pair, plain kernel included
+  return train_step(m, x, n, h, w, layout, dtype, ya, lam == 1.f ? nullptr : yb, lam, stats, logits_out, teacher_logits,
+                    alpha, temperature, kd_stats);
 }
 
 // Makes the model's stream wait for whatever the last training step left running on the side stream (the deferred tail

@@ -102,6 +102,43 @@ def get_model_ema(config, net):
     return ModelEma(net, tr.ema_decay, tr.ema_warmup)
 
 
+def _distill_alpha(s):
+    """``distill_alpha``: the weight of the distillation term (distill.py); read only with ``distill_from`` set."""
+    v = float(s) if s.strip() else 0.5
+    if not 0.0 <= v <= 1.0:
+        raise ValueError(f"distill_alpha must be between 0.0 and 1.0. Got: {v}")
+    return v
+
+
+def _distill_temperature(s):
+    v = float(s) if s.strip() else 2.0
+    if not (v > 0.0 and v != float("inf")):
+        raise ValueError(f"distill_temperature must be a finite number above 0.0. Got: {v}")
+    return v
+
+
+def get_distill_info(config, classes, img_shape):
+    """`Distiller.describe()` of those keys without building the teacher (no GPU), or None when off: what a resumed run
+    is checked against before any network exists.  Raises what `get_distiller` would raise for the directory."""
+    tr = Settings(config).train
+    if not tr.distill_from:
+        return None
+    from .distill import describe_dir
+    return describe_dir(tr.distill_from, classes, img_shape, tr.distill_alpha, tr.distill_temperature)
+
+
+def get_distiller(config, classes, img_shape, device):
+    """The `distill.Distiller` of ``[train] distill_from / distill_alpha / distill_temperature``, or None when
+    ``distill_from`` is empty (the default): no teacher, no second handle - the run of a file without the keys.  A teacher
+    with other classes or another image shape is a ValueError here, before any training."""
+    tr = Settings(config).train
+    if not tr.distill_from:
+        return None
+    from .distill import Distiller, load_teacher
+    alpha, temperature = tr.distill_alpha, tr.distill_temperature     # (a bad number: before the teacher is built)
+    return Distiller(load_teacher(tr.distill_from, classes, img_shape, device), alpha, temperature)
+
+
 def _test_tta(s):
     """``test_tta``: the test-time augmentation mode (tta.py) of a second report per test set, empty = none."""
     from .tta import MODES
@@ -153,6 +190,10 @@ KEYS = {
         # test-time augmentation (tta.py) of the test split(s): a second report, test_report*_tta.txt, beside the plain one;
         # none: the run of a file without the key
         "test_tta": (_test_tta, "none"),
+        # knowledge distillation from a trained model directory (distill.py): the training loss becomes (1 - alpha) * hard +
+        # alpha * T^2 * KL(teacher || student); empty distill_from: off, the run of a file without the keys
+        "distill_from": (lambda s: s.strip(), ""), "distill_alpha": (_distill_alpha, "0.5"),
+        "distill_temperature": (_distill_temperature, "2"),
     },
     "lr_warmup": {
         "use": (_flag, REQUIRED), "factor_1": (float, REQUIRED), "factor_2": (float, REQUIRED), "step_1": (int, REQUIRED),

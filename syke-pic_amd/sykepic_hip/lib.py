@@ -94,6 +94,8 @@ SYMBOLS = {
                                              _P, _P, _P]),
     "spk_train_forward_backward_pair": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                   _P, _P, C.c_float, _P, _P]),
+    "spk_train_forward_backward_distill": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                     _P, _P, C.c_float, _P, C.c_float, C.c_float, _P, _P, _P]),
     "spk_optim_step": (C.c_int, [_P, C.POINTER(OptimDesc)]),
     "spk_model_grad_buffer": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),
     "spk_model_set_grad_ready_callback": (C.c_int, [_P, _P, _P, _P, C.c_int]),
@@ -146,6 +148,8 @@ SYMBOLS = {
     "spk_op_cross_entropy": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "spk_op_cross_entropy_ex": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_float, _P, _P, _P, _P]),
     "spk_op_cross_entropy_pair": (C.c_int, [_P, _P, _P, C.c_float, C.c_int, C.c_int, _P, C.c_float, _P, _P, _P, _P]),
+    "spk_op_cross_entropy_distill": (C.c_int, [_P, _P, _P, C.c_float, _P, C.c_float, C.c_float, C.c_int, C.c_int, _P,
+                                               C.c_float, _P, _P, _P, _P, _P]),
     "spk_op_maxpool": (C.c_int, [_P] * 3 + [C.c_int] * 8 + [_P]),
     "spk_op_maxpool_backward": (C.c_int, [_P] * 3 + [C.c_int] * 8 + [_P]),
     "spk_op_gavgpool": (C.c_int, [_P, _P] + [C.c_int] * 4 + [_P]),

@@ -163,6 +163,7 @@ class HipNet:
         self._params = OrderedDict()
         self._build_views()
         self._stats = None
+        self._kd_stats = None
         # Random start: the seed is drawn from torch's global generator NOW (so `torch.manual_seed` before the
         # constructor reproduces the network, as for the reference), the tensors themselves are generated at
         # first use — a `load_state_dict` of a full checkpoint in between makes them unnecessary.
@@ -516,6 +517,21 @@ class HipNet:
 
     def reset_stats(self):
         self._stats_buf().zero_()
+        if self._kd_stats is not None:
+            self._kd_stats.zero_()
+
+    def _kd_stats_buf(self):
+        if self._kd_stats is None:
+            self._kd_stats = torch.zeros(2, dtype=torch.float32, device=self.device)
+        return self._kd_stats
+
+    def read_distill_stats(self):
+        """(sum of KD*n, rows whose arg-max equals the teacher's) of the distilled steps since reset_stats(); KD is the
+        distillation term T^2 * KL(teacher || student) without its weight alpha.  (0, 0) before the first such step."""
+        if self._kd_stats is None:
+            return 0.0, 0.0
+        s = self._kd_stats.tolist()
+        return float(s[0]), float(s[1])
 
     def read_stats(self):
         """(sum of loss*n, number correct) accumulated since reset_stats();
@@ -560,12 +576,18 @@ class HipNet:
                 C.c_void_p(logits.data_ptr()) if want_logits else None))
         return logits
 
-    def forward_backward(self, x, y, want_logits=False, y2=None, lam=1.0):
+    def forward_backward(self, x, y, want_logits=False, y2=None, lam=1.0, teacher_logits=None, distill_alpha=0.0,
+                         distill_temperature=1.0):
         """zero_grad + train-mode forward + CrossEntropyLoss + backward
         (reference sykepic/train/train.py:239-242) in one library call.
         y2, lam: the Mixup / CutMix criterion ``lam * CE(out, y) + (1 - lam) * CE(out, y2)`` on a batch mixed by
         `mix.BatchMix` (spk_train_forward_backward_pair); accuracy and the per-class counters then count against the
-        dominant label (y when lam >= 0.5, else y2).  y2 None or lam == 1: the step on y alone, bit for bit."""
+        dominant label (y when lam >= 0.5, else y2).  y2 None or lam == 1: the step on y alone, bit for bit.
+        teacher_logits, distill_alpha, distill_temperature: knowledge distillation (distill.py,
+        spk_train_forward_backward_distill): the loss is ``(1 - alpha) * hard + alpha * T^2 * KL(softmax(teacher / T) ||
+        softmax(out / T))`` with `hard` the criterion above; teacher_logits is a contiguous float32 [n, classes] device
+        tensor, `read_distill_stats` accumulates the KL term and the agreement with the teacher.  teacher_logits None or
+        alpha == 0: the step without a teacher, bit for bit."""
         self._ensure_init()
         x, n, h, w, layout, dtype = self._prep(x)
         y = y.to(self.device, dtype=torch.int64).contiguous()
@@ -573,15 +595,29 @@ class HipNet:
             y2 = y2.to(self.device, dtype=torch.int64).contiguous()
             if y2.numel() != y.numel():
                 raise ValueError(f"y2 has {y2.numel()} labels, y has {y.numel()}")
+        distill = teacher_logits is not None and float(distill_alpha) != 0.0
+        if distill and not (isinstance(teacher_logits, torch.Tensor) and teacher_logits.is_cuda
+                            and teacher_logits.device == self.device and teacher_logits.is_contiguous()
+                            and teacher_logits.dtype == torch.float32
+                            and tuple(teacher_logits.shape) == (n, self.num_classes)):
+            raise ValueError(f"teacher_logits must be a contiguous float32 [{n}, {self.num_classes}] tensor on {self.device}")
         logits = torch.empty((n, self.num_classes), dtype=torch.float32, device=self.device) if want_logits else None
         with torch.cuda.device(self.device):
             lib.check(self._lib.spk_model_set_stream(self._h, self._stream()))
             try:
-                lib.check(self._lib.spk_train_forward_backward_pair(
-                    self._h, C.c_void_p(x.data_ptr()), n, h, w, layout, dtype, C.c_void_p(y.data_ptr()),
-                    C.c_void_p(y2.data_ptr()) if y2 is not None else None, float(lam),
-                    C.c_void_p(self._stats_buf().data_ptr()),
-                    C.c_void_p(logits.data_ptr()) if want_logits else None))
+                if distill:
+                    lib.check(self._lib.spk_train_forward_backward_distill(
+                        self._h, C.c_void_p(x.data_ptr()), n, h, w, layout, dtype, C.c_void_p(y.data_ptr()),
+                        C.c_void_p(y2.data_ptr()) if y2 is not None else None, float(lam),
+                        C.c_void_p(teacher_logits.data_ptr()), float(distill_alpha), float(distill_temperature),
+                        C.c_void_p(self._stats_buf().data_ptr()), C.c_void_p(self._kd_stats_buf().data_ptr()),
+                        C.c_void_p(logits.data_ptr()) if want_logits else None))
+                else:
+                    lib.check(self._lib.spk_train_forward_backward_pair(
+                        self._h, C.c_void_p(x.data_ptr()), n, h, w, layout, dtype, C.c_void_p(y.data_ptr()),
+                        C.c_void_p(y2.data_ptr()) if y2 is not None else None, float(lam),
+                        C.c_void_p(self._stats_buf().data_ptr()),
+                        C.c_void_p(logits.data_ptr()) if want_logits else None))
             except RuntimeError as e:
                 if "Expected more than 1 value per channel" in str(e):   # torch raises ValueError for this
                     raise ValueError(str(e).split(": ", 1)[-1]) from None

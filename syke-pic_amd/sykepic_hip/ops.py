@@ -769,6 +769,30 @@ def cross_entropy_pair(z, ya, yb, lam, stats, weight=None, label_smoothing=0.0, 
                                                _stream(dev)))
 
 
+def cross_entropy_distill(z, ya, yb, lam, teacher, alpha, temperature, stats, weight=None, label_smoothing=0.0,
+                          counts=None, kd_stats=None, dz=None):
+    """spk_op_cross_entropy_distill: (1 - alpha) * L_hard + alpha * T^2 * KL(softmax(teacher / T) || softmax(z / T)),
+    L_hard the criterion of `cross_entropy_pair` (yb None: of `cross_entropy_ex` on ya), T = temperature.  Adds (n * loss,
+    correct rows) to stats [2] and the per-class counters to counts as there, and (n * KD, rows whose arg-max equals the
+    teacher's) to kd_stats [2] float32 (None: not kept); writes dz [N,c] (None: no gradient).  teacher: float32 [N,c] on
+    the device; None (or alpha == 0): the bits of `cross_entropy_pair`, kd_stats untouched."""
+    so = lib.load()
+    dev = z.device
+    n, c = z.shape
+    for y in (ya, yb):
+        assert y is None or (y.dtype == torch.int64 and y.is_contiguous() and y.is_cuda and y.numel() == n)
+    assert teacher is None or (teacher.is_cuda and tuple(teacher.shape) == (n, c))
+    assert weight is None or weight.numel() == c
+    assert counts is None or (counts.dtype == torch.int32 and counts.is_contiguous() and counts.is_cuda
+                              and counts.numel() == 2 * c)
+    assert kd_stats is None or kd_stats.numel() == 2
+    with torch.cuda.device(dev):
+        lib.check(so.spk_op_cross_entropy_distill(_p(_f32c(z)), _p(ya), _p(yb), float(lam), _p(_f32c(teacher)), float(alpha),
+                                                  float(temperature), n, c, _p(_f32c(weight)), float(label_smoothing),
+                                                  _p(_f32c(stats)), _p(counts), _p(_f32c(kd_stats)), _p(_f32c(dz)),
+                                                  _stream(dev)))
+
+
 def mix_batch(x, ca, cb, box, shift=1, out=None):
     """spk_mix_batch: x mixed with itself rolled by `shift` images along the batch.  x: a contiguous device batch, uint8
     [N,H,W,C] or float32 [N,C,H,W], C 1 or 3.  Inside box = (y1, x1, y2, x2) the result is ca * x[i] + cb * x[(i - shift)

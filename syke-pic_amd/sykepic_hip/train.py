@@ -25,10 +25,12 @@ from pathlib import Path
 import torch
 
 from . import arch, data, schedule
+from . import distill as distill_mod
 from . import ema as ema_mod
 from . import loss as loss_mod
 from . import tta as tta_mod
-from .config import Settings, get_batch_mix, get_model_ema, get_network, get_transforms
+from .config import (Settings, get_batch_mix, get_distill_info, get_distiller, get_model_ema, get_network,
+                     get_transforms)
 from . import dp
 from .dp import GradSync
 from .optim import HipOptimizer
@@ -119,6 +121,10 @@ def main(args):
     external_test = ds.external_test
     if external_test:
         extra_loader = data.extra_eval_dataloader(external_test, model_data, exclude=["Unclassified"])
+    # knowledge distillation (distill.py): None unless `distill_from` names a model directory.  Its settings now, for the
+    # resume check - a teacher with other classes or another image shape ends the run here; the teacher itself once the
+    # network exists
+    distill_info = get_distill_info(config, classes, img_shape)
 
     # `--resume MODEL_DIR`: that directory as it is (no `auto` id, no `exist_ok` complaint, its config.ini / class_names.txt /
     # class_distribution.csv stay), everything else rebuilt from CONFIG as for a fresh run
@@ -129,7 +135,8 @@ def main(args):
         state = load_train_state(model_dir)
         check_train_state(state, network=mo.network, classes=classes, img_shape=img_shape, optimizer=tr.optimizer,
                           world=world, loss=loss_fn.describe(), checkpoint_on=checkpoint_on,
-                          mix=batch_mix.describe() if batch_mix is not None else None, ema=ema_info)
+                          mix=batch_mix.describe() if batch_mix is not None else None, ema=ema_info,
+                          distill=distill_info)
     else:
         # model directory <path>/<network>[_<id>]; id "auto" = next free number, picked by rank 0 for the whole job
         # (another rank could already see the directory rank 0 has just made)
@@ -181,6 +188,8 @@ def main(args):
         run_info["mix"] = batch_mix.describe()
     if ema_info is not None:         # (likewise)
         run_info["ema"] = ema_info
+    if distill_info is not None:     # (likewise)
+        run_info["distill"] = distill_info
     if state is not None and (state["early_stopped"] or state["epoch"] >= tr.max_epochs):
         # nothing left to train (raise `max_epochs` to extend a run that reached it): the reports of the best model
         if chief:
@@ -189,10 +198,13 @@ def main(args):
     else:
         # the average starts as a copy of the tensors every replica holds now (a resumed run loads its own over it)
         model_ema = get_model_ema(config, net)
+        # every rank loads its own teacher: a second library handle on its device
+        distiller = get_distiller(config, classes, img_shape, device)
         best_state = train_net(net, model_data.train_loader, model_data.val_loader, optimizer, loss_fn, tr.max_epochs,
                                tr.early_stop_patience, model_dir, device, lr_scheduler, lr_warmup, dist=dist,
                                run_info=run_info if tr.save_train_state else None, resume=state,
-                               checkpoint_on=checkpoint_on, batch_mix=batch_mix, model_ema=model_ema)
+                               checkpoint_on=checkpoint_on, batch_mix=batch_mix, model_ema=model_ema,
+                               distiller=distiller)
     if dist is not None:
         dist.barrier()
     net.load_state_dict(torch.load(best_state, map_location="cpu"))
@@ -258,12 +270,13 @@ def _same_mix(a, b):
 
 
 def check_train_state(state, network, classes, img_shape, optimizer, world, loss=None, checkpoint_on="accuracy", mix=None,
-                      ema=None):
+                      ema=None, distill=None):
     """A resumed run must be the run that wrote the file: one line naming the first thing that differs.
     loss: `CrossEntropyLoss.describe()` of the config (None: the defaults); a file without the key - every file written
     before the loss had options - was trained with the defaults, and likewise for `checkpoint_on`.
     mix: `BatchMix.describe()` of the config (None: no mixing); a file without the key was written without mixing.
-    ema: `ModelEma.describe()` of the config (None: no moving average); a file without the key was written without one."""
+    ema: `ModelEma.describe()` of the config (None: no moving average); a file without the key was written without one.
+    distill: `Distiller.describe()` of the config (None: no distillation); a file without the key was written without it."""
     if state.get("format") != TRAIN_STATE_FORMAT:
         raise ValueError(f"cannot resume: train_state.pth has format number {state.get('format')}, this version reads "
                          f"{TRAIN_STATE_FORMAT}")
@@ -295,6 +308,10 @@ def check_train_state(state, network, classes, img_shape, optimizer, world, loss
     if not ema_mod.same_settings(state.get("ema"), ema):
         raise ValueError(f"cannot resume: ema differs, train_state.pth has {ema_mod.show_settings(state.get('ema'))}, "
                          f"the config gives {ema_mod.show_settings(ema)}")
+    if not distill_mod.same_settings(state.get("distill"), distill):
+        raise ValueError(f"cannot resume: distill differs, train_state.pth has "
+                         f"{distill_mod.show_settings(state.get('distill'))}, the config gives "
+                         f"{distill_mod.show_settings(distill)}")
 
 
 def _rank_state(net, batch_mix=None):
@@ -364,7 +381,7 @@ def restore_train_state(state, net, optimizer, lr_scheduler, rank, train_loader,
 
 def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epochs, early_stop_patience,
               model_dir, device, lr_scheduler=None, lr_warmup=None, dist=None, run_info=None, resume=None,
-              checkpoint_on="accuracy", batch_mix=None, model_ema=None):
+              checkpoint_on="accuracy", batch_mix=None, model_ema=None, distiller=None):
     """loss_fn: None (nn.CrossEntropyLoss() as the reference constructs it), a `loss.CrossEntropyLoss` or a
     `torch.nn.CrossEntropyLoss`: its `weight` and `label_smoothing` go to the loss kernel fused into the training and
     validation steps (`HipNet.set_loss`); another reduction than "mean" is a ValueError.
@@ -385,7 +402,11 @@ def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epo
     checkpoint rule, early stopping and the plateau scheduler see the averaged model, while the `[STAT] Train` lines stay
     those of the raw training forward.  Every rank keeps its own average: the parameters are equal on all ranks by
     construction, the averaged running statistics are averaged over the ranks in front of the validation pass, as the
-    raw ones are.  `train_state.pth` is written after swapping back and carries both."""
+    raw ones are.  `train_state.pth` is written after swapping back and carries both.
+    distiller: a `distill.Distiller` (or None): its teacher classifies every TRAINING batch as the step gets it (behind
+    `batch_mix`), and the step's loss is (1 - alpha) * hard + alpha * T^2 * KL(teacher || student); the `[STAT] Train`
+    line reports that loss, and a `[STAT] Distill` line behind it the KL term alone and the share of rows whose arg-max
+    is the teacher's.  Validation and test run the hard loss alone, so `Val Loss` stays comparable between runs."""
     loss = loss_mod.from_loss_fn(loss_fn)
     if checkpoint_on not in ("accuracy", "balanced_accuracy"):
         raise ValueError(f"checkpoint_on must be accuracy or balanced_accuracy. Got: {checkpoint_on}")
@@ -432,23 +453,34 @@ def train_net(net, train_dataloader, val_dataloader, optimizer, loss_fn, max_epo
             for batch in (tqdm(train_dataloader) if chief else train_dataloader):
                 x, y = batch[0], batch[1]
                 optimizer.zero_grad()
-                if batch_mix is None:
+                if batch_mix is None and distiller is None:
                     net.forward_backward(x, y)
                 else:       # on the device batch: a CPU batch of the host loader is transferred first
-                    xm, ya, yb, lam = batch_mix(x.to(device, non_blocking=True), torch.as_tensor(y).to(device))
-                    net.forward_backward(xm, ya, y2=yb, lam=lam)
+                    xm, ya, yb, lam = x.to(device, non_blocking=True), torch.as_tensor(y).to(device), None, 1.0
+                    if batch_mix is not None:
+                        xm, ya, yb, lam = batch_mix(xm, ya)
+                    if distiller is None:
+                        net.forward_backward(xm, ya, y2=yb, lam=lam)
+                    else:   # the teacher sees what the student is about to see
+                        net.forward_backward(xm, ya, y2=yb, lam=lam, teacher_logits=distiller.logits(xm),
+                                             distill_alpha=distiller.alpha, distill_temperature=distiller.temperature)
                 sync.all_reduce(optimizer)
                 optimizer.step()
                 if model_ema is not None:
                     model_ema.update()
                 seen += len(y)
             loss_sum, correct = net.read_stats()          # one device sync per epoch
+            if distiller is not None:
+                kd_sum, agree = net.read_distill_stats()
+                kd_sum, agree, _ = sync.reduce_stats(kd_sum, agree, seen)
             loss_sum, correct, seen = sync.reduce_stats(loss_sum, correct, seen)
             train_acc, train_loss = correct / seen, loss_sum / seen
             train_accs.append(train_acc)
             train_losses.append(train_loss)
             if chief:
                 print(f"[STAT] Train Acc: {train_acc:.3f}, Train Loss: {train_loss:.3f}")
+                if distiller is not None:
+                    print(f"[STAT] Distill Loss: {kd_sum / seen:.3f}, Teacher Agreement: {agree / seen:.3f}")
 
             # validation: every rank holds the same model (running statistics averaged), evaluates ITS shard of
             # the validation set, and the counters are summed: checkpoint, early-stop and learning-rate decisions
