@@ -180,304 +180,159 @@ __global__ void softmax_kernel(const float* __restrict__ z, float* __restrict__ 
   for (int j = lane; j < c; j += 64) p[(size_t)row * c + j] = expf(zr[j] * scale - mx) * inv;
 }
 
-// Mean cross-entropy + arg-max accuracy + dlogits in ONE block so that the
-// loss sum has a fixed summation order (bitwise reproducible).
-__global__ __launch_bounds__(1024) void ce_kernel(const float* __restrict__ z,
-                                                 const int64_t* __restrict__ y, int n, int c,
-                                                 float* __restrict__ stats,
-                                                 float* __restrict__ dz) {
-  constexpr int WAVES = 16;   // a row per wave at a time: 4 waves walked 64 rows each, one latency chain per row (92 us)
-  __shared__ float s_loss[WAVES];
-  __shared__ float s_corr[WAVES];
+// The cross-entropy loss: ce_loss_kernel<EX, PAIR, KD> below, assembled from the pieces in front of it.  ONE block, a row
+// per wave at a time (4 waves walked 64 rows each, one latency chain per row: 92 us), so that every float sum has a fixed
+// order - a thread's own terms in ascending index, the xor butterfly of a wave, then the 16 waves in ascending order - and
+// equal inputs give equal bits; the only atomics are the integer adds of the per-class counters.
+constexpr int CE_WAVES = 16;
+
+// the per-wave partial sums of one quantity, in ascending wave order (after a __syncthreads)
+__device__ __forceinline__ float sum_waves(const float* part) {
+  float t = 0.f;
+  for (int q = 0; q < CE_WAVES; ++q) t += part[q];
+  return t;
+}
+
+// The label-weight sums W_a = sum_i w[ya_i] (PAIR: W_b = sum_i w[yb_i] too) and Sw = sum_c w[c], in one pass over the labels
+// in front of the row loop; every thread ends with the same bits.  w == nullptr: all ones, the caller's W = n, Sw = c stand.
+template <bool PAIR>
+__device__ __forceinline__ void label_weight_sums(const float* w, const int64_t* ya, const int64_t* yb, int n, int c,
+                                                  float* s_wa, float* s_wb, float& Wa, float& Wb, float& Sw) {
+  if (!w) return;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  float loss = 0.f, corr = 0.f;
-  const float invn = 1.0f / (float)n;
-  for (int row = wave; row < n; row += WAVES) {
-    const float* zr = z + (size_t)row * c;
-    const int label = (int)y[row];
-    float mx = -INFINITY;
-    int arg = 0x7fffffff;
-    for (int j = lane; j < c; j += 64) {
-      const float v = zr[j];
-      if (v > mx) { mx = v; arg = j; }
-    }
-    // arg-max with torch's tie rule: lowest index among the maxima
-    for (int d = 32; d; d >>= 1) {
-      const float om = __shfl_xor(mx, d);
-      const int oa = __shfl_xor(arg, d);
-      if (om > mx || (om == mx && oa < arg)) { mx = om; arg = oa; }
-    }
-    float s = 0.f;
-    for (int j = lane; j < c; j += 64) s += expf(zr[j] - mx);
-    s = wave_sum(s);
-    const float lse = mx + logf(s);
-    if (lane == 0) {
-      loss += lse - zr[label];
-      corr += (arg == label) ? 1.f : 0.f;
-    }
-    if (dz) {
-      const float inv = 1.0f / s;
-      for (int j = lane; j < c; j += 64)
-        dz[(size_t)row * c + j] = (expf(zr[j] - mx) * inv - (j == label ? 1.f : 0.f)) * invn;
-    }
+  float pa = 0.f, pb = 0.f;
+  for (int i = threadIdx.x; i < n; i += CE_WAVES * 64) {
+    pa += w[(int)ya[i]];
+    if constexpr (PAIR) pb += w[(int)yb[i]];
   }
-  if (lane == 0) { s_loss[wave] = loss; s_corr[wave] = corr; }
+  pa = wave_sum(pa);
+  if constexpr (PAIR) pb = wave_sum(pb);
+  if (lane == 0) { s_wa[wave] = pa; if constexpr (PAIR) s_wb[wave] = pb; }
   __syncthreads();
-  if (threadIdx.x == 0) {   // fixed order
-    float tl = 0.f, tc = 0.f;
-    for (int q = 0; q < WAVES; ++q) { tl += s_loss[q]; tc += s_corr[q]; }
-    stats[0] += tl;
-    stats[1] += tc;
+  Wa = sum_waves(s_wa);
+  if constexpr (PAIR) Wb = sum_waves(s_wb);
+  float sp = 0.f;
+  for (int j = lane; j < c; j += 64) sp += w[j];
+  Sw = wave_sum(sp);
+}
+
+// the maximum of a row and its index: a lane takes its elements in ascending index, then the wave reduces
+struct RowArgMax {
+  float mx = -INFINITY;
+  int arg = 0x7fffffff;
+  __device__ __forceinline__ void take(float v, int j) { if (v > mx) { mx = v; arg = j; } }
+};
+// arg-max with torch's tie rule: lowest index among the maxima.  N rows share the steps of one butterfly: a step is a
+// round trip through the cross-lane network, and a second butterfly behind the first doubled the wait (+2 us with a teacher).
+template <int N>
+__device__ __forceinline__ void reduce(RowArgMax (&m)[N]) {
+  for (int d = 32; d; d >>= 1) {
+    float om[N];
+    int oa[N];
+    for (int k = 0; k < N; ++k) om[k] = __shfl_xor(m[k].mx, d);
+    for (int k = 0; k < N; ++k) oa[k] = __shfl_xor(m[k].arg, d);
+    for (int k = 0; k < N; ++k)
+      if (om[k] > m[k].mx || (om[k] == m[k].mx && oa[k] < m[k].arg)) { m[k].mx = om[k]; m[k].arg = oa[k]; }
   }
 }
 
-// F.cross_entropy(z, y, weight = w, label_smoothing = eps, reduction = "mean") with the same fused extras, in the same one
-// block of a row per wave.  With p = softmax(z_i), W = sum_i w[y_i], Sw = sum_c w[c]:
+// The soft-max of a row about its maximum mx: s = sum_j exp(v_j - mx), lse = mx + log s, p_j = exp(v_j - mx) / s.  For a
+// temperature the caller hands in the quotients v_j / T and mx / T, each logit divided by T once (a correctly rounded
+// division; T = 1 leaves the bits).  T > 0 and a correctly rounded division are monotone, so the quotient of the maximum
+// is the maximum of the quotients; and a quotient is rounded before the maximum is subtracted - a division does not
+// contract - so the largest exponent is exactly 0, which softmax_kernel needs a pragma for.
+struct RowSoftmax {
+  float mx, s = 0.f;
+  __device__ __forceinline__ void add(float v) { s += expf(v - mx); }
+  __device__ __forceinline__ void reduce() { s = wave_sum(s); }
+  __device__ __forceinline__ float lse() const { return mx + logf(s); }
+  __device__ __forceinline__ float inv() const { return 1.0f / s; }
+  __device__ __forceinline__ float p(float v, float inv) const { return expf(v - mx) * inv; }
+};
+
+// The smoothing sum of a row, sum_j w[j] (lse - z[j]), formed term by term: lse Sw - sum w z would cancel.
+__device__ __forceinline__ float smoothing_sum(const float* zr, const float* w, int c, float lse) {
+  float sm = 0.f;
+  for (int j = threadIdx.x & 63; j < c; j += 64) sm += (w ? w[j] : 1.f) * (lse - zr[j]);
+  return wave_sum(sm);
+}
+
+// The weighted, smoothed row loss aw (lse - z[label]) + b sm of one label before the division by W: aw = (1 - eps) w[label],
+// b = eps / c.  FUSED: one fused multiply-add onto the rounded b sm; else both products and their sum are rounded.  Which
+// of the two the compiler made of this one expression hung on how it packed a kernel's statistics - fused, except for the
+// first label of two - and is pinned here because the statistics are kept bit for bit.
+template <bool FUSED>
+__device__ __forceinline__ float hard_row_loss(float aw, float lse, float zl, float b, float sm) {
+#pragma clang fp contract(off)
+  const float d = lse - zl, bs = b * sm;
+  if constexpr (FUSED) return fmaf(aw, d, bs);
+  return aw * d + bs;
+}
+
+// ... and the gradient of that label's loss at class j, ca = aw / W, without its smoothing term
+__device__ __forceinline__ float hard_grad(float ca, float p, int j, int label) {
+  return ca * (p - (j == label ? 1.f : 0.f));
+}
+
+// the per-class counters [c][2] (may be null) += (rows, correct rows) of the row's dominant label
+__device__ __forceinline__ void count_row(int* counts, int c, int label, bool hit) {
+  if (counts && (unsigned)label < (unsigned)c) {
+    atomicAdd(counts + 2 * label, 1);
+    if (hit) atomicAdd(counts + 2 * label + 1, 1);
+  }
+}
+
+// Mean cross-entropy + arg-max accuracy + dlogits, in five instantiations.
+// plain (EX false): nn.CrossEntropyLoss(), the reference's loss.  stats[0] += sum_i (lse_i - z[i][y_i]) (the caller's
+// running sum of loss * n), dz = (p - onehot) / n.  No weights, no smoothing, no counters: w, eps and counts are not read.
+// EX: F.cross_entropy(z, y, weight = w, label_smoothing = eps, reduction = "mean") with the same fused extras.  With
+// p = softmax(z_i), W = sum_i w[y_i], Sw = sum_c w[c]:
 //   loss     = [ (1 - eps) sum_i w[y_i] (lse_i - z[i][y_i]) + (eps / c) sum_i sum_j w[j] (lse_i - z[i][j]) ] / W
 //   dz[i][j] = [ (1 - eps) w[y_i] (p[i][j] - [j == y_i]) + (eps / c) (p[i][j] Sw - w[j]) ] / W
-// w == nullptr: all ones (W = n, Sw = c, exactly).  Every float sum has a fixed order (a thread's own terms in ascending
-// index, the xor butterfly of a wave, then the 16 waves in ascending order), so equal inputs give equal bits; the only
-// atomics are the integer adds of the per-class counters.  The smoothing sum is formed term by term as w[j] (lse - z[j]):
-// lse Sw - sum w z would cancel.  stats[0] += n loss (the reference accumulates loss.item() * len(y)), stats[1] += rows
-// whose arg-max (lowest index among the maxima) is the label; counts [c][2] (may be null) += per class (rows, correct rows).
-__global__ __launch_bounds__(1024) void ce_ex_kernel(const float* __restrict__ z, const int64_t* __restrict__ y, int n,
-                                                    int c, const float* __restrict__ w, float eps,
-                                                    float* __restrict__ stats, int* __restrict__ counts,
-                                                    float* __restrict__ dz) {
-  constexpr int WAVES = 16;
-  __shared__ float s_w[WAVES];
-  __shared__ float s_loss[WAVES];
-  __shared__ float s_corr[WAVES];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  // W: the pass over the labels in front of the row loop; every thread ends with the same bits
-  float W = (float)n, Sw = (float)c;
-  if (w) {
-    float part = 0.f;
-    for (int i = threadIdx.x; i < n; i += WAVES * 64) part += w[(int)y[i]];
-    part = wave_sum(part);
-    if (lane == 0) s_w[wave] = part;
-    __syncthreads();
-    W = 0.f;
-    for (int q = 0; q < WAVES; ++q) W += s_w[q];
-    float sp = 0.f;
-    for (int j = lane; j < c; j += 64) sp += w[j];
-    Sw = wave_sum(sp);
-  }
-  const bool smooth = eps > 0.f;
-  const float invW = 1.0f / W;
-  const float a = 1.0f - eps, b = eps / (float)c;
-  const float cb = b * invW;
-  float loss = 0.f, corr = 0.f;
-  for (int row = wave; row < n; row += WAVES) {
-    const float* zr = z + (size_t)row * c;
-    const int label = (int)y[row];
-    float mx = -INFINITY;
-    int arg = 0x7fffffff;
-    for (int j = lane; j < c; j += 64) {
-      const float v = zr[j];
-      if (v > mx) { mx = v; arg = j; }
-    }
-    // arg-max with torch's tie rule: lowest index among the maxima
-    for (int d = 32; d; d >>= 1) {
-      const float om = __shfl_xor(mx, d);
-      const int oa = __shfl_xor(arg, d);
-      if (om > mx || (om == mx && oa < arg)) { mx = om; arg = oa; }
-    }
-    float s = 0.f;
-    for (int j = lane; j < c; j += 64) s += expf(zr[j] - mx);
-    s = wave_sum(s);
-    const float lse = mx + logf(s);
-    float sm = 0.f;
-    if (smooth) {
-      for (int j = lane; j < c; j += 64) sm += (w ? w[j] : 1.f) * (lse - zr[j]);
-      sm = wave_sum(sm);
-    }
-    const float aw = a * (w ? w[label] : 1.f);
-    if (lane == 0) {
-      const bool hit = arg == label;
-      loss += aw * (lse - zr[label]) + b * sm;
-      corr += hit ? 1.f : 0.f;
-      if (counts && (unsigned)label < (unsigned)c) {
-        atomicAdd(counts + 2 * label, 1);
-        if (hit) atomicAdd(counts + 2 * label + 1, 1);
-      }
-    }
-    if (dz) {
-      const float inv = 1.0f / s;
-      const float ca = aw * invW;
-      for (int j = lane; j < c; j += 64) {
-        const float p = expf(zr[j] - mx) * inv;
-        float g = ca * (p - (j == label ? 1.f : 0.f));
-        if (smooth) g += cb * (p * Sw - (w ? w[j] : 1.f));
-        dz[(size_t)row * c + j] = g;
-      }
-    }
-  }
-  if (lane == 0) { s_loss[wave] = loss; s_corr[wave] = corr; }
-  __syncthreads();
-  if (threadIdx.x == 0) {   // fixed order
-    float tl = 0.f, tc = 0.f;
-    for (int q = 0; q < WAVES; ++q) { tl += s_loss[q]; tc += s_corr[q]; }
-    stats[0] += tl * invW * (float)n;
-    stats[1] += tc;
-  }
-}
-
-// The Mixup / CutMix criterion on two label vectors: L = lam CE(z, ya; w, eps) + (1 - lam) CE(z, yb; w, eps), each CE the
-// loss of ce_ex_kernel with its own W (W_a = sum_i w[ya_i], W_b = sum_i w[yb_i]), dz = lam dCE_a + (1 - lam) dCE_b.  The
-// same one block of a row per wave and the same fixed summation orders.  Per row the soft-max, lse and the smoothing sum
-// (term by term, w[j] (lse - z[j])) are computed once; the two row losses and the two gradients are then formed with
-// exactly the expressions of ce_ex_kernel, each with its own label and 1 / W, and only combined at the end:
+// w == nullptr: all ones.  stats[0] += n loss (the reference accumulates loss.item() * len(y)), stats[1] += rows whose
+// arg-max is the label; counts [c][2] (may be null) += per class (rows, correct rows).
+// PAIR: the Mixup / CutMix criterion on two label vectors, L = lam CE(z, ya; w, eps) + (1 - lam) CE(z, yb; w, eps), each
+// CE the loss above with its own W.  Per row the soft-max, lse and the smoothing sum are computed once; the two row
+// losses and the two gradients are formed by the same pieces as the single label's (hard_row_loss says where one of them
+// rounds a product more), each with its own label and 1 / W, and only combined at the end:
 //   dz[i][j]  = lam g_a + (1 - lam) g_b,       stats[0] += lam (n CE_a) + (1 - lam) (n CE_b),    1 - lam formed in float32
-// so the extra roundings over ce_ex_kernel are the two products, 1 - lam and the sum (tests/test_gpu_loss_pair_ops.py);
-// no combined smoothing coefficient is formed.  stats[1] and the per-class counters go by the dominant label: ya when
-// lam >= 0.5, else yb.  The launcher sends lam == 1 (and yb == nullptr) to ce_ex_kernel itself.
-__global__ __launch_bounds__(1024) void ce_pair_kernel(const float* __restrict__ z, const int64_t* __restrict__ ya,
-                                                      const int64_t* __restrict__ yb, float lam, int n, int c,
-                                                      const float* __restrict__ w, float eps, float* __restrict__ stats,
-                                                      int* __restrict__ counts, float* __restrict__ dz) {
-  constexpr int WAVES = 16;
-  __shared__ float s_wa[WAVES];
-  __shared__ float s_wb[WAVES];
-  __shared__ float s_la[WAVES];
-  __shared__ float s_lb[WAVES];
-  __shared__ float s_corr[WAVES];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  // W_a, W_b: each as ce_ex_kernel forms W; every thread ends with the same bits
-  float Wa = (float)n, Wb = (float)n, Sw = (float)c;
-  if (w) {
-    float pa = 0.f, pb = 0.f;
-    for (int i = threadIdx.x; i < n; i += WAVES * 64) { pa += w[(int)ya[i]]; pb += w[(int)yb[i]]; }
-    pa = wave_sum(pa);
-    pb = wave_sum(pb);
-    if (lane == 0) { s_wa[wave] = pa; s_wb[wave] = pb; }
-    __syncthreads();
-    Wa = Wb = 0.f;
-    for (int q = 0; q < WAVES; ++q) { Wa += s_wa[q]; Wb += s_wb[q]; }
-    float sp = 0.f;
-    for (int j = lane; j < c; j += 64) sp += w[j];
-    Sw = wave_sum(sp);
-  }
-  const bool smooth = eps > 0.f;
-  const bool first = lam >= 0.5f;   // the dominant label
-  const float invWa = 1.0f / Wa, invWb = 1.0f / Wb;
-  const float a = 1.0f - eps, b = eps / (float)c;
-  const float cba = b * invWa, cbb = b * invWb;
-  const float lamb = 1.0f - lam;
-  float loss_a = 0.f, loss_b = 0.f, corr = 0.f;
-  for (int row = wave; row < n; row += WAVES) {
-    const float* zr = z + (size_t)row * c;
-    const int la = (int)ya[row], lb = (int)yb[row];
-    float mx = -INFINITY;
-    int arg = 0x7fffffff;
-    for (int j = lane; j < c; j += 64) {
-      const float v = zr[j];
-      if (v > mx) { mx = v; arg = j; }
-    }
-    // arg-max with torch's tie rule: lowest index among the maxima
-    for (int d = 32; d; d >>= 1) {
-      const float om = __shfl_xor(mx, d);
-      const int oa = __shfl_xor(arg, d);
-      if (om > mx || (om == mx && oa < arg)) { mx = om; arg = oa; }
-    }
-    float s = 0.f;
-    for (int j = lane; j < c; j += 64) s += expf(zr[j] - mx);
-    s = wave_sum(s);
-    const float lse = mx + logf(s);
-    float sm = 0.f;
-    if (smooth) {
-      for (int j = lane; j < c; j += 64) sm += (w ? w[j] : 1.f) * (lse - zr[j]);
-      sm = wave_sum(sm);
-    }
-    const float awa = a * (w ? w[la] : 1.f), awb = a * (w ? w[lb] : 1.f);
-    if (lane == 0) {
-      const int label = first ? la : lb;
-      const bool hit = arg == label;
-      loss_a += awa * (lse - zr[la]) + b * sm;
-      loss_b += awb * (lse - zr[lb]) + b * sm;
-      corr += hit ? 1.f : 0.f;
-      if (counts && (unsigned)label < (unsigned)c) {
-        atomicAdd(counts + 2 * label, 1);
-        if (hit) atomicAdd(counts + 2 * label + 1, 1);
-      }
-    }
-    if (dz) {
-      const float inv = 1.0f / s;
-      const float caa = awa * invWa, cab = awb * invWb;
-      for (int j = lane; j < c; j += 64) {
-        const float p = expf(zr[j] - mx) * inv;
-        float ga = caa * (p - (j == la ? 1.f : 0.f));
-        float gb = cab * (p - (j == lb ? 1.f : 0.f));
-        if (smooth) {
-          const float t = p * Sw - (w ? w[j] : 1.f);
-          ga += cba * t;
-          gb += cbb * t;
-        }
-        dz[(size_t)row * c + j] = lam * ga + lamb * gb;
-      }
-    }
-  }
-  if (lane == 0) { s_la[wave] = loss_a; s_lb[wave] = loss_b; s_corr[wave] = corr; }
-  __syncthreads();
-  if (threadIdx.x == 0) {   // fixed order
-    float ta = 0.f, tb = 0.f, tc = 0.f;
-    for (int q = 0; q < WAVES; ++q) { ta += s_la[q]; tb += s_lb[q]; tc += s_corr[q]; }
-    stats[0] += lam * (ta * invWa * (float)n) + lamb * (tb * invWb * (float)n);
-    stats[1] += tc;
-  }
-}
-
-// Knowledge distillation: L = (1 - alpha) L_hard + alpha KD against the logits t [n][c] of a teacher, with
+// so the extra roundings over one label are the two products, 1 - lam and the sum (tests/test_gpu_loss_pair_ops.py); no
+// combined smoothing coefficient is formed.  stats[1] and the counters go by the dominant label: ya when lam >= 0.5, else yb.
+// KD: knowledge distillation, L = (1 - alpha) L_hard + alpha KD against the logits t [n][c] of a teacher, with
 //   KD = T^2 / n  sum_i KL(q_i || pT_i),   pT = softmax(z / T),   q = softmax(t / T)       ("batchmean")
 //   dz[i][j] = (1 - alpha) g_hard[i][j] + (alpha T / n) (pT[i][j] - q[i][j])
-// L_hard is the loss of ce_ex_kernel (PAIR false: one label vector) or of ce_pair_kernel (PAIR true), and the hard row
-// losses and g_hard are formed with exactly their expressions before anything is combined, so their rounding bounds
-// carry over.  The same one block of a row per wave and the same fixed summation orders; integer atomics only.  Per row
-// three soft-maxes: of z (the hard part), of z / T and of t / T, each logit divided by T once (a correctly rounded
-// division; T = 1 leaves the bits) and the maximum taken of the quotients.  The KD row sum is formed term by term as
+// L_hard is the loss of one label vector or of two (PAIR), and the hard row losses and g_hard are complete before anything
+// is combined, so their rounding bounds carry over (tests/test_gpu_distill_ops.py).  Per row three soft-maxes: of z (the
+// hard part), of z / T and of t / T.  The KD row sum is formed term by term as
 //   q[j] ((t[j] / T - lseT_t) - (z[j] / T - lseT_z)):
 // q log q is never formed, a q that underflows to 0 contributes exactly 0, and a row whose two soft-maxes sit on
-// different classes gives the finite difference of the logits.  (A quotient is rounded before the maximum is subtracted -
-// a division does not contract - so the largest exponent is exactly 0, which softmax_kernel needs a pragma for.)
+// different classes gives the finite difference of the logits.
 //   stats[0] += (1 - alpha) (n L_hard) + alpha (n KD),  n KD = (T T) sum of the KD rows,  1 - alpha formed in float32
-//   stats[1], counts: ce_pair_kernel's rule (arg-max = lowest index among the maxima of z, against the dominant label)
 //   kd_stats (may be null): [0] += n KD, [1] += rows whose arg-max of z equals the arg-max of t (the same tie rule)
-template <bool PAIR>
-__global__ __launch_bounds__(1024) void ce_distill_kernel(const float* __restrict__ z, const int64_t* __restrict__ ya,
-                                                         const int64_t* __restrict__ yb, float lam,
-                                                         const float* __restrict__ tz, float alpha, float T, int n, int c,
-                                                         const float* __restrict__ w, float eps, float* __restrict__ stats,
-                                                         int* __restrict__ counts, float* __restrict__ kd_stats,
-                                                         float* __restrict__ dz) {
-  constexpr int WAVES = 16;
-  __shared__ float s_wa[WAVES];
-  __shared__ float s_wb[WAVES];
-  __shared__ float s_la[WAVES];
-  __shared__ float s_lb[WAVES];
-  __shared__ float s_corr[WAVES];
-  __shared__ float s_kd[WAVES];
-  __shared__ float s_agree[WAVES];
+// What a mode does not need it does not form: `if constexpr`, never arithmetic with neutral elements, so each
+// instantiation's float expressions are those of its mode alone and the launcher's fall-throughs are bit for bit.
+template <bool EX, bool PAIR, bool KD>
+__global__ __launch_bounds__(1024) void ce_loss_kernel(const float* __restrict__ z, const int64_t* __restrict__ ya,
+                                                      const int64_t* __restrict__ yb, float lam,
+                                                      const float* __restrict__ tz, float alpha, float T, int n, int c,
+                                                      const float* __restrict__ w, float eps, float* __restrict__ stats,
+                                                      int* __restrict__ counts, float* __restrict__ kd_stats,
+                                                      float* __restrict__ dz) {
+  static_assert(EX || (!PAIR && !KD), "the plain loss has one label vector and no teacher");
+  // (an array that an instantiation does not use takes no LDS in it)
+  __shared__ float s_wa[CE_WAVES];
+  __shared__ float s_wb[CE_WAVES];
+  __shared__ float s_la[CE_WAVES];
+  __shared__ float s_lb[CE_WAVES];
+  __shared__ float s_corr[CE_WAVES];
+  __shared__ float s_kd[CE_WAVES];
+  __shared__ float s_agree[CE_WAVES];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  // W_a (W_b): as ce_ex_kernel forms W; every thread ends with the same bits
   float Wa = (float)n, Wb = (float)n, Sw = (float)c;
-  if (w) {
-    float pa = 0.f, pb = 0.f;
-    for (int i = threadIdx.x; i < n; i += WAVES * 64) {
-      pa += w[(int)ya[i]];
-      if (PAIR) pb += w[(int)yb[i]];
-    }
-    pa = wave_sum(pa);
-    if (PAIR) pb = wave_sum(pb);
-    if (lane == 0) { s_wa[wave] = pa; s_wb[wave] = pb; }
-    __syncthreads();
-    Wa = Wb = 0.f;
-    for (int q = 0; q < WAVES; ++q) { Wa += s_wa[q]; Wb += s_wb[q]; }
-    float sp = 0.f;
-    for (int j = lane; j < c; j += 64) sp += w[j];
-    Sw = wave_sum(sp);
-  }
-  const bool smooth = eps > 0.f;
+  if constexpr (EX) label_weight_sums<PAIR>(w, ya, yb, n, c, s_wa, s_wb, Wa, Wb, Sw);
+  const bool smooth = EX && eps > 0.f;
   const bool first = !PAIR || lam >= 0.5f;   // the dominant label
+  const float invn = 1.0f / (float)n;        // plain
   const float invWa = 1.0f / Wa, invWb = 1.0f / Wb;
   const float a = 1.0f - eps, b = eps / (float)c;
   const float cba = b * invWa, cbb = b * invWb;
@@ -485,94 +340,106 @@ __global__ __launch_bounds__(1024) void ce_distill_kernel(const float* __restric
   const float hard = 1.0f - alpha;           // the weight of the hard part
   const float ck = alpha * T / (float)n;     // the coefficient of pT - q
   float loss_a = 0.f, loss_b = 0.f, corr = 0.f, kd = 0.f, agree = 0.f;
-  for (int row = wave; row < n; row += WAVES) {
+  for (int row = wave; row < n; row += CE_WAVES) {
     const float* zr = z + (size_t)row * c;
-    const float* tr = tz + (size_t)row * c;
-    const int la = (int)ya[row], lb = PAIR ? (int)yb[row] : la;
-    float mx = -INFINITY, mt = -INFINITY;
-    int arg = 0x7fffffff, argt = 0x7fffffff;
+    const float* tr = KD ? tz + (size_t)row * c : nullptr;
+    const int la = (int)ya[row];
+    int lb = la;
+    if constexpr (PAIR) lb = (int)yb[row];
+    RowArgMax m[KD ? 2 : 1];   // of z and, at [KD], of the teacher's row
     for (int j = lane; j < c; j += 64) {
-      const float v = zr[j], u = tr[j];
-      if (v > mx) { mx = v; arg = j; }
-      if (u > mt) { mt = u; argt = j; }
+      m[0].take(zr[j], j);
+      if constexpr (KD) m[KD].take(tr[j], j);
     }
-    // arg-max with torch's tie rule on both: lowest index among the maxima
-    for (int d = 32; d; d >>= 1) {
-      const float om = __shfl_xor(mx, d), ot = __shfl_xor(mt, d);
-      const int oa = __shfl_xor(arg, d), oat = __shfl_xor(argt, d);
-      if (om > mx || (om == mx && oa < arg)) { mx = om; arg = oa; }
-      if (ot > mt || (ot == mt && oat < argt)) { mt = ot; argt = oat; }
-    }
-    // T > 0 and a correctly rounded division are monotone: the quotient of the maximum is the maximum of the quotients
-    const float mxT = mx / T, mtT = mt / T;
-    float s = 0.f, sz = 0.f, st = 0.f;
+    reduce(m);
+    const RowArgMax mz = m[0], mt = m[KD];
+    RowSoftmax sz{mz.mx}, szT{mz.mx / T}, stT{mt.mx / T};
     for (int j = lane; j < c; j += 64) {
-      s += expf(zr[j] - mx);
-      sz += expf(zr[j] / T - mxT);
-      st += expf(tr[j] / T - mtT);
+      sz.add(zr[j]);
+      if constexpr (KD) { szT.add(zr[j] / T); stT.add(tr[j] / T); }
     }
-    s = wave_sum(s);
-    sz = wave_sum(sz);
-    st = wave_sum(st);
-    const float lse = mx + logf(s);
-    const float lsez = mxT + logf(sz), lset = mtT + logf(st);
-    const float invz = 1.0f / sz, invt = 1.0f / st;
+    sz.reduce();
+    const float lse = sz.lse();
+    float lsez = 0.f, lset = 0.f, invz = 0.f, invt = 0.f;
+    if constexpr (KD) {
+      szT.reduce(), stT.reduce();
+      lsez = szT.lse(), lset = stT.lse(), invz = szT.inv(), invt = stT.inv();
+    }
     float sm = 0.f;
-    if (smooth) {
-      for (int j = lane; j < c; j += 64) sm += (w ? w[j] : 1.f) * (lse - zr[j]);
-      sm = wave_sum(sm);
-    }
+    if (smooth) sm = smoothing_sum(zr, w, c, lse);
     float kr = 0.f;
-    for (int j = lane; j < c; j += 64) {
-      const float q = expf(tr[j] / T - mtT) * invt;
-      kr += q * ((tr[j] / T - lset) - (zr[j] / T - lsez));
+    if constexpr (KD) {
+      for (int j = lane; j < c; j += 64) {
+        const float q = stT.p(tr[j] / T, invt);
+        kr += q * ((tr[j] / T - lset) - (zr[j] / T - lsez));
+      }
+      kr = wave_sum(kr);
     }
-    kr = wave_sum(kr);
-    const float awa = a * (w ? w[la] : 1.f), awb = a * (w ? w[lb] : 1.f);
+    const float awa = a * (w ? w[la] : 1.f), awb = a * (w ? w[lb] : 1.f);   // EX
     if (lane == 0) {
       const int label = first ? la : lb;
-      const bool hit = arg == label;
-      loss_a += awa * (lse - zr[la]) + b * sm;
-      if (PAIR) loss_b += awb * (lse - zr[lb]) + b * sm;
+      const bool hit = mz.arg == label;
       corr += hit ? 1.f : 0.f;
-      kd += kr;
-      agree += (arg == argt) ? 1.f : 0.f;
-      if (counts && (unsigned)label < (unsigned)c) {
-        atomicAdd(counts + 2 * label, 1);
-        if (hit) atomicAdd(counts + 2 * label + 1, 1);
+      if constexpr (!EX) {
+        loss_a += lse - zr[la];
+      } else {
+        loss_a += hard_row_loss<!PAIR>(awa, lse, zr[la], b, sm);
+        if constexpr (PAIR) loss_b += hard_row_loss<true>(awb, lse, zr[lb], b, sm);
+        count_row(counts, c, label, hit);
       }
+      if constexpr (KD) { kd += kr; agree += (mz.arg == mt.arg) ? 1.f : 0.f; }
     }
     if (dz) {
-      const float inv = 1.0f / s;
-      const float caa = awa * invWa, cab = awb * invWb;
+      const float inv = sz.inv();
+      const float caa = awa * invWa, cab = awb * invWb;   // EX
       for (int j = lane; j < c; j += 64) {
-        const float p = expf(zr[j] - mx) * inv;
-        float ga = caa * (p - (j == la ? 1.f : 0.f));
-        float gb = cab * (p - (j == lb ? 1.f : 0.f));
-        if (smooth) {
-          const float t = p * Sw - (w ? w[j] : 1.f);
-          ga += cba * t;
-          gb += cbb * t;
+        const float p = sz.p(zr[j], inv);
+        float g;
+        if constexpr (!EX) {
+          g = (p - (j == la ? 1.f : 0.f)) * invn;
+        } else {
+          g = hard_grad(caa, p, j, la);
+          float gb = 0.f;
+          if constexpr (PAIR) gb = hard_grad(cab, p, j, lb);
+          if (smooth) {
+            const float t = p * Sw - (w ? w[j] : 1.f);
+            g += cba * t;
+            if constexpr (PAIR) gb += cbb * t;
+          }
+          if constexpr (PAIR) g = lam * g + lamb * gb;
         }
-        const float g = PAIR ? lam * ga + lamb * gb : ga;
-        const float pT = expf(zr[j] / T - mxT) * invz;
-        const float q = expf(tr[j] / T - mtT) * invt;
-        dz[(size_t)row * c + j] = hard * g + ck * (pT - q);
+        if constexpr (KD) {
+          const float pT = szT.p(zr[j] / T, invz);
+          const float q = stT.p(tr[j] / T, invt);
+          g = hard * g + ck * (pT - q);
+        }
+        dz[(size_t)row * c + j] = g;
       }
     }
   }
-  if (lane == 0) { s_la[wave] = loss_a; s_lb[wave] = loss_b; s_corr[wave] = corr; s_kd[wave] = kd; s_agree[wave] = agree; }
+  if (lane == 0) {
+    s_la[wave] = loss_a;
+    s_corr[wave] = corr;
+    if constexpr (PAIR) s_lb[wave] = loss_b;
+    if constexpr (KD) { s_kd[wave] = kd; s_agree[wave] = agree; }
+  }
   __syncthreads();
   if (threadIdx.x == 0) {   // fixed order
-    float ta = 0.f, tb = 0.f, tc = 0.f, tk = 0.f, tg = 0.f;
-    for (int q = 0; q < WAVES; ++q) { ta += s_la[q]; tb += s_lb[q]; tc += s_corr[q]; tk += s_kd[q]; tg += s_agree[q]; }
-    const float nhard = PAIR ? lam * (ta * invWa * (float)n) + lamb * (tb * invWb * (float)n) : ta * invWa * (float)n;
-    const float nkd = (T * T) * tk;
-    stats[0] += hard * nhard + alpha * nkd;
-    stats[1] += tc;
-    if (kd_stats) {
-      kd_stats[0] += nkd;
-      kd_stats[1] += tg;
+    // Every product and sum of the combine is rounded on its own, as the tests count them: left to the compiler, whether
+    // lam A + (1 - lam) B or (1 - alpha) H + alpha KD became a fused multiply-add hung on how it packed the two statistics.
+#pragma clang fp contract(off)
+    float nloss = sum_waves(s_la);                       // plain: the sum of the row losses is n loss
+    if constexpr (EX) nloss = nloss * invWa * (float)n;
+    if constexpr (PAIR) nloss = lam * nloss + lamb * (sum_waves(s_lb) * invWb * (float)n);
+    float nkd = 0.f;
+    if constexpr (KD) {
+      nkd = (T * T) * sum_waves(s_kd);
+      nloss = hard * nloss + alpha * nkd;
+    }
+    stats[0] += nloss;
+    stats[1] += sum_waves(s_corr);
+    if constexpr (KD) {
+      if (kd_stats) { kd_stats[0] += nkd; kd_stats[1] += sum_waves(s_agree); }
     }
   }
 }
@@ -670,38 +537,16 @@ int spk_launch_softmax(const float* z, float* p, int n, int c, float scale, hipS
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int spk_launch_ce(const float* z, const int64_t* y, int n, int c, float* stats, float* dlogits,
-                  hipStream_t s) {
-  hipLaunchKernelGGL(ce_kernel, dim3(1), dim3(1024), 0, s, z, y, n, c, stats, dlogits);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int spk_launch_ce_ex(const float* z, const int64_t* y, int n, int c, const float* w, float label_smoothing, float* stats,
-                     int* counts, float* dlogits, hipStream_t s) {
-  hipLaunchKernelGGL(ce_ex_kernel, dim3(1), dim3(1024), 0, s, z, y, n, c, w, label_smoothing, stats, counts, dlogits);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// lam CE(z, ya) + (1 - lam) CE(z, yb); yb == nullptr or lam == 1: ce_ex_kernel on ya, bit for bit
-int spk_launch_ce_pair(const float* z, const int64_t* ya, const int64_t* yb, float lam, int n, int c, const float* w,
-                       float label_smoothing, float* stats, int* counts, float* dlogits, hipStream_t s) {
-  if (!yb || lam == 1.0f) return spk_launch_ce_ex(z, ya, n, c, w, label_smoothing, stats, counts, dlogits, s);
-  hipLaunchKernelGGL(ce_pair_kernel, dim3(1), dim3(1024), 0, s, z, ya, yb, lam, n, c, w, label_smoothing, stats, counts,
-                     dlogits);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// (1 - alpha) L_hard + alpha T^2 KL(softmax(t / T) || softmax(z / T)); t == nullptr or alpha == 0: spk_launch_ce_pair
-// unchanged (the teacher is not read, kd_stats not written), bit for bit
-int spk_launch_ce_distill(const float* z, const int64_t* ya, const int64_t* yb, float lam, const float* t, float alpha,
-                          float temperature, int n, int c, const float* w, float label_smoothing, float* stats, int* counts,
-                          float* kd_stats, float* dlogits, hipStream_t s) {
-  if (!t || alpha == 0.0f) return spk_launch_ce_pair(z, ya, yb, lam, n, c, w, label_smoothing, stats, counts, dlogits, s);
-  if (!yb || lam == 1.0f)
-    hipLaunchKernelGGL(ce_distill_kernel<false>, dim3(1), dim3(1024), 0, s, z, ya, (const int64_t*)nullptr, 1.0f, t, alpha, temperature, n, c,
-                       w, label_smoothing, stats, counts, kd_stats, dlogits);
-  else
-    hipLaunchKernelGGL(ce_distill_kernel<true>, dim3(1), dim3(1024), 0, s, z, ya, yb, lam, t, alpha, temperature, n, c, w,
-                       label_smoothing, stats, counts, kd_stats, dlogits);
+// The one way to the loss kernel.  The fall-throughs are bit for bit because the instantiation that a rule picks does not
+// form what the rule found missing: no teacher or alpha == 0 -> no KD (the teacher is not read, kd_stats not written);
+// then no yb or lam == 1 -> no pair.  plain is the caller's word alone, never inferred from w and eps.
+int spk_launch_ce(const CeArgs& a, hipStream_t s) {
+  const bool kd = a.teacher && a.alpha != 0.0f;
+  const bool pair = a.yb && a.lam != 1.0f;
+  auto kernel = a.plain ? ce_loss_kernel<false, false, false>
+                : kd    ? (pair ? ce_loss_kernel<true, true, true> : ce_loss_kernel<true, false, true>)
+                        : (pair ? ce_loss_kernel<true, true, false> : ce_loss_kernel<true, false, false>);
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(CE_WAVES * 64), 0, s, a.z, a.ya, a.yb, a.lam, a.teacher, a.alpha, a.T, a.n, a.c,
+                     a.w, a.eps, a.stats, a.counts, a.kd_stats, a.dz);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

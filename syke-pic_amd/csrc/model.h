@@ -198,7 +198,8 @@ struct spk_model {
   hipEvent_t grad_ev[3] = {nullptr, nullptr, nullptr};
 
   // the loss of spk_train_forward_backward and spk_eval_step (spk_model_set_loss): with neither weights nor smoothing
-  // the steps launch ce_kernel, otherwise ce_ex_kernel, which also fills the per-class counters
+  // the steps launch the plain instantiation of ce_loss_kernel (CeArgs::plain), otherwise the weighted one, which also
+  // fills the per-class counters
   float* loss_w = nullptr;      // class weights [num_classes] on the device, or null
   float loss_eps = 0.f;         // label smoothing
   int* class_counts = nullptr;  // int32 [num_classes][2] on the device: (rows seen, rows correct) since the last reset

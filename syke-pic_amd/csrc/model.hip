@@ -872,10 +872,11 @@ extern "C" int spk_eval_step(spk_model* m, const void* x, int n, int h, int w, i
   SPK_TRY(spk_forward_eval_logits(m, x, n, h, w, layout, dtype, logits));
   // CrossEntropyLoss is a batch mean; the caller accumulates loss*n (train.py:269)
   // validation uses the loss the training step uses, as the reference's single loss_fn (spk_model_set_loss)
-  if (m->loss_ex() ? spk_launch_ce_ex(logits, y, n, m->num_classes, m->loss_w, m->loss_eps, stats, m->class_counts, nullptr,
-                                      m->stream)
-                   : spk_launch_ce(logits, y, n, m->num_classes, stats, nullptr, m->stream))
-    return spk_fail(SPK_ERR_HIP, "cross-entropy launch failed");
+  CeArgs ce;
+  ce.z = logits, ce.ya = y, ce.n = n, ce.c = m->num_classes, ce.stats = stats;
+  ce.w = m->loss_w, ce.eps = m->loss_eps, ce.counts = m->class_counts;
+  ce.plain = !m->loss_ex();
+  if (spk_launch_ce(ce, m->stream)) return spk_fail(SPK_ERR_HIP, "cross-entropy launch failed");
   return SPK_OK;
 }
 

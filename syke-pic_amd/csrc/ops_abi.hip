@@ -990,12 +990,21 @@ extern "C" int spk_op_softmax(const float* z, float* p, int n, int c, float base
   return SPK_OK;
 }
 
+namespace {
+// what every cross-entropy hook passes on; the rest of CeArgs keeps its defaults unless the hook has it
+CeArgs ce_args(const float* z, const int64_t* y, int n, int c, float* stats, float* dz, bool plain) {
+  CeArgs a;
+  a.z = z, a.ya = y, a.n = n, a.c = c, a.stats = stats, a.dz = dz, a.plain = plain;
+  return a;
+}
+}  // namespace
+
 extern "C" int spk_op_cross_entropy(const float* z, const int64_t* labels, int n, int c, float* stats, float* dz,
                                     void* stream) {
   if (!z || !labels || !stats || n < 1 || c < 1) return ofail(SPK_ERR_ARG, "op_cross_entropy: bad arguments");
   if (!below_2g(n, c)) return ofail(SPK_ERR_UNSUPPORTED, "op_cross_entropy: a tensor of 2^31 elements or more");
   hipStream_t s = (hipStream_t)stream;
-  O_TRY(spk_launch_ce(z, labels, n, c, stats, dz, s), "cross-entropy");
+  O_TRY(spk_launch_ce(ce_args(z, labels, n, c, stats, dz, true), s), "cross-entropy");
   O_SYNC(s, "op_cross_entropy: kernel failed");
   return SPK_OK;
 }
@@ -1007,7 +1016,9 @@ extern "C" int spk_op_cross_entropy_ex(const float* z, const int64_t* labels, in
     return ofail(SPK_ERR_ARG, "op_cross_entropy_ex: label_smoothing must be in [0, 1]");
   if (!below_2g(n, c)) return ofail(SPK_ERR_UNSUPPORTED, "op_cross_entropy_ex: a tensor of 2^31 elements or more");
   hipStream_t s = (hipStream_t)stream;
-  O_TRY(spk_launch_ce_ex(z, labels, n, c, w, label_smoothing, stats, counts, dz, s), "cross-entropy");
+  CeArgs a = ce_args(z, labels, n, c, stats, dz, false);
+  a.w = w, a.eps = label_smoothing, a.counts = counts;
+  O_TRY(spk_launch_ce(a, s), "cross-entropy");
   O_SYNC(s, "op_cross_entropy_ex: kernel failed");
   return SPK_OK;
 }
@@ -1021,7 +1032,9 @@ extern "C" int spk_op_cross_entropy_pair(const float* z, const int64_t* ya, cons
     return ofail(SPK_ERR_ARG, "op_cross_entropy_pair: label_smoothing must be in [0, 1]");
   if (!below_2g(n, c)) return ofail(SPK_ERR_UNSUPPORTED, "op_cross_entropy_pair: a tensor of 2^31 elements or more");
   hipStream_t s = (hipStream_t)stream;
-  O_TRY(spk_launch_ce_pair(z, ya, yb, lam, n, c, w, label_smoothing, stats, counts, dz, s), "cross-entropy");
+  CeArgs a = ce_args(z, ya, n, c, stats, dz, false);
+  a.yb = yb, a.lam = lam, a.w = w, a.eps = label_smoothing, a.counts = counts;
+  O_TRY(spk_launch_ce(a, s), "cross-entropy");
   O_SYNC(s, "op_cross_entropy_pair: kernel failed");
   return SPK_OK;
 }
@@ -1040,8 +1053,10 @@ extern "C" int spk_op_cross_entropy_distill(const float* z, const int64_t* ya, c
   if (kd_stats && !t) return ofail(SPK_ERR_ARG, "op_cross_entropy_distill: kd_stats without teacher logits");
   if (!below_2g(n, c)) return ofail(SPK_ERR_UNSUPPORTED, "op_cross_entropy_distill: a tensor of 2^31 elements or more");
   hipStream_t s = (hipStream_t)stream;
-  O_TRY(spk_launch_ce_distill(z, ya, yb, lam, t, alpha, temperature, n, c, w, label_smoothing, stats, counts, kd_stats, dz, s),
-        "cross-entropy");
+  CeArgs a = ce_args(z, ya, n, c, stats, dz, false);
+  a.yb = yb, a.lam = lam, a.teacher = t, a.alpha = alpha, a.T = temperature;
+  a.w = w, a.eps = label_smoothing, a.counts = counts, a.kd_stats = kd_stats;
+  O_TRY(spk_launch_ce(a, s), "cross-entropy");
   O_SYNC(s, "op_cross_entropy_distill: kernel failed");
   return SPK_OK;
 }

@@ -402,23 +402,26 @@ int spk_linear_backward(const float* gy, const float* x, const float* w, float* 
 int spk_launch_linear_fwd(const float* x, const float* w, const float* b, float* y, int n, int in,
                           int out, hipStream_t s);
 int spk_launch_softmax(const float* z, float* p, int n, int c, float scale, hipStream_t s);
-// stats[0] += sum_i CE_i ; stats[1] += #(argmax == y); dlogits (may be null) = (softmax - onehot)/n
-int spk_launch_ce(const float* z, const int64_t* y, int n, int c, float* stats, float* dlogits,
-                  hipStream_t s);
-// the same with class weights w [c] (null: ones) and label smoothing: stats[0] += n * loss (the weighted mean), dlogits its
-// gradient; counts [c][2] int32 (may be null) += per class (rows seen, rows correct)
-int spk_launch_ce_ex(const float* z, const int64_t* y, int n, int c, const float* w, float label_smoothing, float* stats,
-                     int* counts, float* dlogits, hipStream_t s);
-// the Mixup / CutMix criterion lam CE(z, ya) + (1 - lam) CE(z, yb) of that loss, statistics by the dominant label
-// (ya when lam >= 0.5); yb == nullptr or lam == 1 launches the kernel of spk_launch_ce_ex on ya
-int spk_launch_ce_pair(const float* z, const int64_t* ya, const int64_t* yb, float lam, int n, int c, const float* w,
-                       float label_smoothing, float* stats, int* counts, float* dlogits, hipStream_t s);
-// knowledge distillation on top of that criterion: (1 - alpha) L_hard + alpha T^2 KL(softmax(t / T) || softmax(z / T)),
-// t [n][c] the teacher's logits; kd_stats [2] (may be null) += (n KD, rows whose arg-max equals the teacher's).
-// t == nullptr or alpha == 0: spk_launch_ce_pair unchanged, t and kd_stats untouched
-int spk_launch_ce_distill(const float* z, const int64_t* ya, const int64_t* yb, float lam, const float* t, float alpha,
-                          float temperature, int n, int c, const float* w, float label_smoothing, float* stats, int* counts,
-                          float* kd_stats, float* dlogits, hipStream_t s);
+// The cross-entropy loss of a batch of logits, one launch of ce_loss_kernel (head.hip), which states the formulas.
+struct CeArgs {
+  const float* z = nullptr;         // logits [n][c]
+  const int64_t* ya = nullptr;      // labels [n]
+  const int64_t* yb = nullptr;      // the second labels of the Mixup / CutMix criterion lam CE(z, ya) + (1 - lam) CE(z, yb),
+  float lam = 1.f;                  //   statistics by the dominant label (ya when lam >= 0.5); null or lam == 1: one label
+  const float* teacher = nullptr;   // a teacher's logits [n][c]: (1 - alpha) L_hard + alpha T^2 KL(softmax(t / T) || softmax(z / T));
+  float alpha = 0.f, T = 1.f;       //   null or alpha == 0: no distillation, teacher and kd_stats untouched
+  int n = 0, c = 0;
+  const float* w = nullptr;         // class weights [c] (null: ones)
+  float eps = 0.f;                  // label smoothing
+  float* stats = nullptr;           // [0] += n * loss (the weighted mean), [1] += #(argmax == dominant label)
+  int* counts = nullptr;            // [c][2] int32 (may be null) += per class (rows seen, rows correct)
+  float* kd_stats = nullptr;        // [2] (may be null) += (n KD, rows whose arg-max equals the teacher's)
+  float* dz = nullptr;              // dlogits [n][c] (may be null): the gradient of the loss
+  // nn.CrossEntropyLoss() as the reference hard-codes it: stats[0] += sum_i CE_i, dz = (softmax - onehot) / n; w, eps
+  // and counts are not read.  The caller says so; w == nullptr and eps == 0 without it is the weighted loss with ones.
+  bool plain = false;
+};
+int spk_launch_ce(const CeArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // Training kernels (train_kernels.hip, conv_wgrad.hip)

@@ -950,7 +950,7 @@ static StepCtx step_begin(spk_model* m, int n, int w) {
 
 // The training step of the three entry points.  y2 == nullptr: the loss on y, as ever; else the Mixup / CutMix criterion
 // lam CE(y) + (1 - lam) CE(y2); teacher != nullptr and alpha != 0: that loss distilled against the teacher's logits
-// (spk_launch_ce_distill) - the loss launch is all that differs.
+// - the arguments of the loss launch (spk_launch_ce) are all that differs.
 static int train_step(spk_model* m, const void* x, int n, int h, int w, int layout, int dtype, const int64_t* y,
                       const int64_t* y2, float lam, float* stats, float* logits_out, const float* teacher = nullptr,
                       float alpha = 0.f, float temperature = 1.f, float* kd_stats = nullptr) {
@@ -1024,17 +1024,14 @@ static int train_step(spk_model* m, const void* x, int n, int h, int w, int layo
 
   // ------------------------- loss + dlogits -------------------------
   const float* logits = (const float*)m->T(last);
-  if (teacher && alpha != 0.f)
-    K_TRY(spk_launch_ce_distill(logits, y, y2, lam, teacher, alpha, temperature, n, m->num_classes, m->loss_w, m->loss_eps,
-                                stats, m->class_counts, kd_stats, (float*)t->G(last), s), "cross-entropy");
-  else if (y2)   // the model's weights and smoothing (none and 0 for the default loss); counters when they are kept
-    K_TRY(spk_launch_ce_pair(logits, y, y2, lam, n, m->num_classes, m->loss_w, m->loss_eps, stats, m->class_counts,
-                             (float*)t->G(last), s), "cross-entropy");
-  else if (m->loss_ex())
-    K_TRY(spk_launch_ce_ex(logits, y, n, m->num_classes, m->loss_w, m->loss_eps, stats, m->class_counts,
-                           (float*)t->G(last), s), "cross-entropy");
-  else
-    K_TRY(spk_launch_ce(logits, y, n, m->num_classes, stats, (float*)t->G(last), s), "cross-entropy");
+  CeArgs ce;
+  ce.z = logits, ce.ya = y, ce.yb = y2, ce.lam = lam, ce.n = n, ce.c = m->num_classes;
+  ce.teacher = teacher, ce.alpha = alpha, ce.T = temperature, ce.kd_stats = kd_stats;
+  // the model's weights and smoothing (none and 0 for the default loss); counters when they are kept
+  ce.w = m->loss_w, ce.eps = m->loss_eps, ce.counts = m->class_counts;
+  ce.stats = stats, ce.dz = (float*)t->G(last);
+  ce.plain = !m->loss_ex() && !y2 && !(teacher && alpha != 0.f);   // the step of the default loss, bit for bit
+  K_TRY(spk_launch_ce(ce, s), "cross-entropy");
   mark(m, PH_LOSS);
   if (logits_out)
     HIP_TRY(hipMemcpyAsync(logits_out, logits, (size_t)n * m->num_classes * 4, hipMemcpyDeviceToDevice, s));
@@ -1376,7 +1373,7 @@ extern "C" int spk_model_train_counters_set(spk_model* m, uint64_t steps, uint64
 }
 
 // loss_fn = nn.CrossEntropyLoss(weight, label_smoothing) of the training and validation steps (train.py:127).  The
-// arguments are checked before any HIP call; (NULL, 0) frees the buffers and the steps launch ce_kernel again.
+// arguments are checked before any HIP call; (NULL, 0) frees the buffers and the steps launch the plain loss again.
 extern "C" int spk_model_set_loss(spk_model* m, const float* class_weights, float label_smoothing) {
   if (!m) return spk_fail(SPK_ERR_ARG, "model_set_loss: null model");
   if (!(label_smoothing >= 0.f && label_smoothing <= 1.f))

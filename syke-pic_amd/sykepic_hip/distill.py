@@ -4,7 +4,7 @@ not in sykefi/syke-pic): a small network learns from the logits of a trained lar
 The teacher is a model directory as `sykepic train` leaves it.  It is loaded into a second `HipNet` in eval mode, on
 the student's device, and sees exactly the tensor the student's step gets - behind the GPU augmentations, the train
 pipeline's normalisation and Mixup / CutMix.  Its logits go into one reused buffer, and the student's step runs the
-distillation criterion in its loss kernel (csrc/head.hip `ce_distill_kernel`):
+distillation criterion in its loss kernel (csrc/head.hip `ce_loss_kernel<.., KD>`):
 
     L = (1 - alpha) L_hard + alpha T^2 KL(softmax(teacher / T) || softmax(student / T))          ("batchmean")
 

@@ -1,4 +1,4 @@
-"""`ce_distill_kernel` (csrc/head.hip) through `spk_op_cross_entropy_distill`: knowledge distillation
+"""`ce_loss_kernel<EX, PAIR, KD>` (csrc/head.hip) through `spk_op_cross_entropy_distill`: knowledge distillation
     L  = (1 - alpha) L_hard + alpha KD,      KD = T^2 / n sum_i KL(softmax(t_i / T) || softmax(z_i / T)),
     dz = (1 - alpha) g_hard + (alpha T / n) (pT - q),     pT = softmax(z / T),  q = softmax(t / T)
 against float64 `(1 - a) * L_hard + a * T * T * F.kl_div(F.log_softmax(z / T, 1), F.softmax(t / T, 1), reduction=
@@ -15,8 +15,8 @@ test_gpu_head_pool_ops.py.  Every first-order sum below is multiplied by SECOND 
 the (1 + x) factors: every relative error x here is below 2^-13 (asserted in `_soft`).  TINY = 2^-126 is added wherever a
 relative bound is claimed for a number that may be subnormal or flushed to 0 (an underflowing exp, a product with it).
 
-The hard part.  g_hard^ and H^ = n L_hard^ are formed with exactly the expressions of `ce_ex_kernel` (one label vector)
-or `ce_pair_kernel` (two), so they carry `test_gpu_loss_ops._bounds` (bg, bH) or `test_gpu_loss_pair_ops._pair_bounds`.
+The hard part.  g_hard^ and H^ = n L_hard^ are formed by the very code of the undistilled instantiations (one label vector
+or two: the same kernel template, the KD terms under `if constexpr`), so they carry `test_gpu_loss_ops._bounds` (bg, bH) or `test_gpu_loss_pair_ops._pair_bounds`.
 (A fused multiply-add rounds once where a count has two: contraction can only lower the error.)
 
 The two extra soft-maxes.  u_j = z_j / T is divided once, u^_j = u_j (1 + d_j), |d_j| <= d (T = 1: exact), and the
@@ -33,7 +33,7 @@ KD.  A term is q^_j fl(fl(u^t_j - lse^_t) - fl(u^z_j - lse^_z)).  With lq_j = lo
   their difference:      + d |D_j|                       -> eD_j = d (|u_t_j| + |u_z_j| + |lq_j| + |lp_j| + |D_j|) + el_t + el_z
   the product with q^_j: q_j ((ep_t + d) |D_j| + eD_j) + TINY (|D_j| + eD_j + 1)
 The row sum: a thread's own terms (ceil(c / 64) - 1 additions) and the 6 levels of the butterfly, kS = ceil(c / 64) + 5
-roundings over terms of either sign: kS d sum_j (|q_j D_j| + term bound).  The rows as `ce_kernel` sums them:
+roundings over terms of either sign: kS d sum_j (|q_j D_j| + term bound).  The rows as every loss sums them:
 (n / 16 + 17) d sum_i (|row_i| + row bound).  n KD^ = fl(fl(T T) tk): two more roundings.  So
   |n KD^ - n KD| <= T^2 [ sum of the row bounds + (n / 16 + 17) d sum_i (|row_i| + row bound_i) + 2 d |sum of the rows| ].
 stats[0] = fl(fl(fl(1 - alpha) H^) + fl(alpha nKD^)): the combination `_pair_bounds` counts, with alpha in the place of

@@ -1,6 +1,6 @@
 """The classifier head, the loss and the pooling kernels one operator at a time, at the shapes where their tails are.
 
-`linear_mfma_kernel`, `sgemm_mfma_strided_kernel`, `sgemm_strided_kernel`, `softmax_kernel`, `ce_kernel` (csrc/head.hip),
+`linear_mfma_kernel`, `sgemm_mfma_strided_kernel`, `sgemm_strided_kernel`, `softmax_kernel`, the plain `ce_loss_kernel` (csrc/head.hip),
 `maxpool_kernel` / `gavgpool_kernel` in bf16 and fp16 (csrc/pointwise.hip), `maxpool_idx_kernel`, `maxpool_bwd_kernel<3,2,1>`,
 `maxpool_bwd_kernel<0,0,0>`, `maxpool3s2_bwd_pair_kernel`, `gavgpool_bwd_kernel` and `colsum_kernel`
 (csrc/train_kernels.hip) run here through the single-operator hooks `spk_op_linear`, `spk_op_linear_backward`,

@@ -1,4 +1,4 @@
-"""`ce_ex_kernel` (csrc/head.hip) through `spk_op_cross_entropy_ex`: CrossEntropyLoss with class weights and label
+"""`ce_loss_kernel<EX>` (csrc/head.hip) through `spk_op_cross_entropy_ex`: CrossEntropyLoss with class weights and label
 smoothing against `F.cross_entropy(weight=, label_smoothing=)` and its autograd gradient in float64 on the CPU.
 
 Shapes: every n of {1, 2, 16, 17, 33} (below / at / above the 16 rows a pass of the 16 waves takes, a third pass) x
@@ -31,7 +31,7 @@ loss: lse = mx + logf(s) has |err| <= el = (e1 + t) + E |log s| + d |lse| (head_
                                                          kS = ceil(c / 64) + 5 here whether or not there are weights)
       second part: (eps / c) [Sw el + (kS + 4) d S_i]  (eps / c and the product two more)
       their sum:   d row_i
-  The rows are summed as ce_kernel sums them, (n / 16 + 17) d sum rows (head_pool), and stats[0] = sum (1 / W) n adds
+  The rows are summed as the plain loss sums them, (n / 16 + 17) d sum rows (head_pool), and stats[0] = sum (1 / W) n adds
   eW + 2 d:  |stats[0] - n loss| <= (n / W) [sum of the row bounds + (n / 16 + 17 + kW + 3) d sum rows].
 Worst observed error / bound on an MI355X (printed by every bounded test): dz 0.33, n loss 0.08, row sums of dz 0.07.
 Exactness: correct rows and the per-class counters are integers and must EQUAL the reference (arg-max = lowest index
@@ -200,7 +200,7 @@ PLAIN_CASES = [(n, c, ones) for n in NS for c in CS for ones in (True, False)]
 @pytest.mark.parametrize("n,c,ones", PLAIN_CASES, ids=[f"{n}x{c}-{'ones' if o else 'null'}" for n, c, o in PLAIN_CASES])
 def test_unit_weights_without_smoothing_agree_with_the_plain_kernel(n, c, ones):
     """w = ones (and w = NULL), eps = 0 is the plain loss: both kernels lie within their own bound of the float64 value
-    (head_pool's for `ce_kernel`), so they lie within the sum of the two bounds of each other."""
+    (head_pool's for the plain instantiation), so they lie within the sum of the two bounds of each other."""
     from sykepic_hip import ops
     z = H._normal((n, c), 2000 * n + c, 3.0)
     labels = H._ints((n,), 0, c - 1, 2000 * n + c + 1)
@@ -210,7 +210,7 @@ def test_unit_weights_without_smoothing_agree_with_the_plain_kernel(n, c, ones):
     plain_stats = torch.zeros(2, dtype=torch.float32, device="cuda")
     plain_dz = torch.full((n, c), float("nan"), dtype=torch.float32, device="cuda")
     ops.cross_entropy(H._dev(z), labels.cuda(), plain_stats, plain_dz)
-    # ce_kernel's bounds, as test_random_cross_entropy states them (dz there is (p - onehot) / n)
+    # the plain loss's bounds, as test_random_cross_entropy states them (dz there is (p - onehot) / n)
     p, e1, t, zs, s = H._softmax_ref(z, 1.0)
     onehot = F.one_hot(labels, c).double()
     plain_dz_bound = ((2 * e1 + t) * p + 3 * EPS * (p - onehot).abs()) / n

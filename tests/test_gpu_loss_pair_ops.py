@@ -1,4 +1,4 @@
-"""`ce_pair_kernel` (csrc/head.hip) through `spk_op_cross_entropy_pair`: the Mixup / CutMix criterion
+"""`ce_loss_kernel<EX, PAIR>` (csrc/head.hip) through `spk_op_cross_entropy_pair`: the Mixup / CutMix criterion
     L = lam CE(z, ya; w, eps) + (1 - lam) CE(z, yb; w, eps)
 against float64 `lam * F.cross_entropy(z, ya, ...) + (1 - lam) * F.cross_entropy(z, yb, ...)` and its autograd
 gradient on the CPU; lam is the float32 the hook is handed, as a double, and 1 - lam exact in the reference.
@@ -7,7 +7,8 @@ Shapes: every n of {1, 2, 16, 17, 33} x every c of {1, 2, 50, 65, 130} (the row 
 test_gpu_loss_ops.py) x the four modes of that file plus "no weights, no smoothing" x lam of {0, float32(0.3), 0.5, 1}.
 
 BOUNDS.  None is fitted to what the kernel gives.  The kernel forms, per row, the soft-max, lse and the smoothing sum
-once and then the two row losses and the two gradients g_a, g_b with exactly the expressions of `ce_ex_kernel`, each
+once and then the two row losses and the two gradients g_a, g_b by the pieces that form the single label's (`hard_row_loss`,
+`hard_grad` and the shared smoothing term: one kernel template, so the expressions are the same by construction), each
 with its own label and its own 1 / W (W_a = sum_i w[ya_i], W_b = sum_i w[yb_i], summed as W is there).  So the computed
 g_a^ and A^ = n CE_a^ carry the roundings `test_gpu_loss_ops._bounds` counts for the label vector ya - call its two
 results bg_a (per element of dz) and bA (of n * loss) - and g_b^, B^ those of yb: bg_b, bB.  (A fused multiply-add
@@ -21,8 +22,8 @@ and the same three operations on A^, B^ for stats[0].  No combined smoothing coe
                                       + 2 d (1 - lam) G_b                              (1 - lam, and the product with it)
                                       + d (lam G_a + (1 - lam) G_b)                    (the sum)
 with G_a = |g_a| + bg_a >= |g_a^| and G_b likewise; the three d terms are multiplied by 1 + 2^-20, which covers the
-products of two or three of the (1 + d) factors.  stats[0] the same with A, B, bA, bB.  lam = 1 runs `ce_ex_kernel`
-itself (bg_a, bA alone: the formula gives that too, the d terms only add).  Summed over a row the dz bounds bound the
+products of two or three of the (1 + d) factors.  stats[0] the same with A, B, bA, bB.  lam = 1 runs the one-label
+instantiation itself (bg_a, bA alone: the formula gives that too, the d terms only add).  Summed over a row the dz bounds bound the
 row's sum, which is 0 in exact arithmetic.
 Worst observed error / bound on an MI355X (printed by every bounded test, 500 combinations): dz 0.35, n loss 0.08, row
 sums of dz 0.06.
